@@ -17,9 +17,13 @@ the worst case (every sequence at its maximum length); --varlen draws realistic 
 --inbatch adds BASELINE configs[2]: RCCL all-gather of the [CLS] embeddings and the in-batch NLL term
 (MASTER fused loss, KL + 0.2*NLL) over the global score matrix.
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
-Prints ONE compact JSON line (rank 0) on stdout -- the headline, roofline, cpu_baseline and {value, ms_per_step, frac} per side
+A plain run sets up, warms up, times the K steps and reports them; --full adds everything else (the profiled roofline pass,
+realistic-length and all-rows runs, the parity report, the side lines, the CPU baseline; --no-* flags take parts away again).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32/float64, < 64 MB; same arguments =>
+same inputs), so that two builds can be compared output for output.
+Prints ONE compact JSON line (rank 0) on stdout -- the headline; with --full also roofline, cpu_baseline and {value, ms_per_step, frac} per side
 line, < 6 KB; the full record (side-line kernel tables, prose) goes to stderr and gpurun_out/bench_full.json.
 """
 import argparse
@@ -104,7 +108,15 @@ def main():
     ap.add_argument("--no-prof", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the bf16-vs-reference-golden error report")
     ap.add_argument("--no-fp32-side", action="store_true", help="skip the fp32-mode throughput side line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiled roofline pass, realistic-length / all-rows runs, parity report, side lines and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32/float64, < 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:                  # a plain run: set-up, warm-up, the timed steps, the result line -- nothing else
+        args.no_prof = args.no_cpu_baseline = args.no_realistic = args.no_parity = args.no_fp32_side = True
     if args.side:
         args.no_cpu_baseline = args.no_realistic = args.no_parity = args.no_fp32_side = True
     is16 = args.dtype in ("fp16", "fp16_plain", "bf16")
@@ -224,8 +236,9 @@ def main():
     fwd_cus = fwd_cus if fwd_cus[0] or fwd_cus[1] else None
     teacher_stream = torch.cuda.Stream(device=dev) if os.environ.get("SIMX_TEACHER_STREAM", "1") == "1" else None
 
-    def micro_step(mi):
+    def micro_step(mi, keep=None):
         # S1+S2 on the GPU, then device-side batch assembly (gather of pre-tokenised passages)
+        # (keep: a dict that receives this micro-step's results for --dump-outputs; None in every other step)
         neg = ops.simans_sample(d_scores, d_spos, N, form=ops.LAPLACE, tau=3.0, seed=42 + rank, offset=step_no[0] * args.accum + mi)
         sel = torch.cat([zero_col, neg.long() + 1], dim=1)                         # [B,1+N] rows of the query's pool
         batch = ops.assemble_batch(pool["q"], pool["p"], q_rows, (row_base + sel).to(torch.int32), 1 + N, pad_id=0, sep_id=102, ce_len=CL)
@@ -235,6 +248,8 @@ def main():
         if args.teacher_step:
             z = teacher(batch["teacher"][0], batch["teacher"][1])
             loss, _ = ops.teacher_ce_loss(z, args.accum)
+            if keep is not None:
+                keep.update(negatives=neg, teacher_logits=z)
             loss.backward()
             return loss
         if args.no_teacher:
@@ -266,14 +281,18 @@ def main():
             loss = loss + 0.2 * parallel.inbatch_nll_allgather(q, c, 1 + N)
         if fwd_cus:
             L.call("simx_set_compute_cus", 0)
+        if keep is not None:
+            keep.update(negatives=neg, teacher_logits=z, query_embeddings=q, passage_embeddings=c)
+            if args.loss == "kl":
+                keep["student_scores"] = sim
         loss.backward()
         return loss
 
-    def one_step():
+    def one_step(keep=None):
         step_no[0] += 1
         for mi in range(args.accum):
             opt.armed = mi == args.accum - 1       # an accumulated buffer is all-reduced once, by the last micro-step's backward
-            loss = micro_step(mi)
+            loss = micro_step(mi, keep)
         opt.step(max_grad_norm=2.0, world_size=world)      # optimizer first, scheduler second (co_training_marco_train.py:250-252)
         sch.step()
         return loss
@@ -297,9 +316,10 @@ def main():
                 raise SystemExit("bench.py --gpus %d: replicas diverged after the first step (relative checksum deviation %.3e)" % (world, dev_max))
     sync()
     # the timed region carries no instrumentation (HIP events around ~1700 launches per step cost 1.1 % of the step)
+    last = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = one_step()
+    for i in range(args.steps):
+        loss = one_step(last if i == args.steps - 1 else None)
     sync()
     dt = time.perf_counter() - t0
     final_loss = float(loss.item())
@@ -307,6 +327,15 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if last is not None and rank == 0:
+        # what a caller of the step receives: its loss, embeddings and scores, and the weights after the optimiser update
+        # (written before any --full pass runs more steps on them)
+        last["loss"] = loss
+        trained = [("teacher_tower", teacher.encoder)] if args.teacher_step else [("question_tower", bi.question_model), ("passage_tower", bi.ctx_model)]
+        for name, m in trained:
+            last[name + "_weights"] = m.engine.flat
+        dump_outputs(args.dump_outputs, last)
+        last = None
     # Roofline / kernel breakdown: a second pass of the SAME steps right after the timed region, with HIP events around
     # every launch (on the launch's stream) and the two student towers on ONE stream: in the timed region the towers run on
     # two HIP streams, kernels of different towers share the CUs, and a kernel's event-to-event time there would not be
@@ -448,7 +477,7 @@ def main():
         if out["comm"] is None or any(k not in out["comm"] for k in need):
             raise SystemExit("bench.py --gpus %d: no communication record (%r): the gradient all-reduce did not run" % (world, out["comm"]))
         out["comm"]["replica_check"] = "parameter checksums of all ranks agree to 1e-6 after the first optimiser step"
-    busy = pmc_mfma_busy()
+    busy = pmc_mfma_busy() if args.full else None
     if busy is not None and is16:
         busy["source"] = pmc_source("r*_mfma_busy.json")
         busy["stale"] = bool(busy["source"] and busy["source"]["stale"])
@@ -577,6 +606,30 @@ def main():
         emit(out)
     if world > 1 or forced:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, tensors, per_array=8 << 20):
+    """--dump-outputs: every tensor as path/<name>.npy, float32 (float64 for integer tensors, exact).  A tensor over
+    `per_array` bytes is replaced by <name>_sample.npy, a fixed sample of its flattened elements (sorted indices drawn from
+    RandomState(0): the same for every build at the same arguments)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name in sorted(tensors):
+        t = tensors[name].detach()
+        dtype = torch.float32 if t.is_floating_point() else torch.float64
+        n_max = per_array // (4 if dtype == torch.float32 else 8)
+        if t.numel() > n_max:
+            idx = np.unique(np.random.RandomState(0).randint(0, t.numel(), n_max))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT, "--dump-outputs wrote %d bytes" % total
 
 
 SIDE_KEYS = ("fp32_mode", "recipe_fp32_gradckpt", "recipe_shapes", "recipe_of_record", "recipe_shapes_folded", "recipe_of_record_folded",
@@ -716,7 +769,7 @@ def p3_algorithmic_bytes(B, P, QL, PL, CE, teacher, full_last, L=L_, H=H_, F=F_)
 def side_line(args, argv, what, timeout_s=300, env=None):
     """`python bench.py <argv> --side` on the same GPU in a child process; returns its headline numbers (never `value`)."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--side", "--cands", str(args.cands)] + argv
+    cmd = [sys.executable, os.path.abspath(__file__), "--side", "--full", "--cands", str(args.cands)] + argv
     if "--negs" not in argv:
         cmd += ["--negs", str(args.negs)]
     if "--batch" not in argv:

@@ -258,7 +258,7 @@ def test_bench_two_ranks_share_one_gpu(dev, launcher):
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    r = subprocess.run(cmd + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
+    r = subprocess.run(cmd + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--full",
                               "--no-cpu-baseline", "--no-realistic", "--no-parity", "--no-fp32-side"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
