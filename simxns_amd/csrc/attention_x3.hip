@@ -1165,7 +1165,7 @@ extern "C" int simx_mha_bwd_x3_bias(simx_stream_t stream, int nseq, int heads, i
   SIMX_PROF(SIMX_K_MHA_BWD, s, 8.0 * T * max_len * heads * d);
   SIMX_REQUIRE(nseq > 0 && heads > 0 && T > 0 && qkv_planes && ctx_planes && lse && dctx && dqkv_planes && cu, SIMX_ERR_BAD_SHAPE, "mha_bwd_x3: bad arguments");
   SIMX_REQUIRE(simx_mha_x3_ok(d, max_len) && qkv_plane_stride % 8 == 0 && ctx_plane_stride % 8 == 0 && dqkv_plane_stride % 4 == 0 &&
-                   (heads * 64) % 8 == 0 && (((uintptr_t)dctx) & 15) == 0, SIMX_ERR_UNSUPPORTED,
+                   (heads * 64) % 8 == 0 && simx_al16(dctx), SIMX_ERR_UNSUPPORTED,
                "mha_bwd_x3: needs head size 64, max_len <= 4096, aligned plane strides");
   // (probabilities travel as 2^10 p / (1 - p_drop) in fp16 halves: finite only while 1 / (1 - p_drop) stays small)
   SIMX_REQUIRE(!dropd || dropd->p <= 0.9f, SIMX_ERR_UNSUPPORTED, "mha_x3: attention dropout above 0.9 is not supported by the plane-pair kernels");

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
+#include <mutex>
 #include "../../include/simx.h"
 
 typedef unsigned short bf16_t;   // raw bf16 bits
@@ -374,6 +376,54 @@ bool simx_x3_tn_ok(int M, int N, int K, const float* A, int lda, const float* B,
 size_t simx_x3_tn_workspace_bytes(int M, int N, int K);
 int simx_x3_gemm_tn(hipStream_t s, int fmt, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     int accumulate, void* ws, size_t ws_bytes, float* dbias);
+// csrc/gemm_p5.hip, csrc/gemm_tn5.hip: eligibility + launch; SIMX_ERR_UNSUPPORTED (without an error text) when the shape is outside
+// the kernel's rules, so that the caller falls through to gemm_nt_p3_kernel / gemm_tn2_kernel
+int simx_launch_nt_p5(hipStream_t s, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
+                      const float* bias, int hm_c_rows, int ncu);
+int simx_launch_tn5(hipStream_t s, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* slabs,
+                    int splits, int kps, float* dbias, int a_hm_rows, const float* gs);
+
+static inline bool simx_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// ---- per-device launch state (gemm.hip; include/simx.h: initialised once per device under std::call_once) -----------------
+// CUs of the current device in whole XCD rows (xcd_remap assumes block b -> XCD b % 8); 0 when the device cannot be queried
+int simx_device_cus();
+// Dynamic LDS above 64 KB is a per-device kernel attribute.  Kernel templates cannot be named across translation units, so each
+// unit lists its own kernels and keeps one SimxLdsAttrs; simx_set_lds_attrs sets the list once per device (false: it failed).
+struct SimxLdsAttr { const void* kernel; int bytes; };
+template <typename... Args> SimxLdsAttr simx_lds(void (*kernel)(Args...), int bytes) { return {reinterpret_cast<const void*>(kernel), bytes}; }
+struct SimxLdsAttrs { std::once_flag once[SIMX_MAX_DEVICES]; bool ok[SIMX_MAX_DEVICES] = {}; };
+bool simx_set_lds_attrs(SimxLdsAttrs& st, const SimxLdsAttr* list, int n);
+
+// ---- split-K wgrad GEMMs (gemm.hip, gemm_xp.hip, gemm_x3.hip) ---------------------------------------------------------------
+// Plan: `tiles` output tiles, K tokens, `round` workgroups per round of the chip, k in multiples of `kstep`.  round / tiles splits,
+// capped at cdiv(K, 512) (at least 8 k-tiles each) and at least 1; k per split rounded up to kstep, then the splits recomputed.
+struct SimxSplitK { int splits, kps; };
+SimxSplitK simx_splitk_plan(int tiles, int K, int round, int kstep);
+// one round of the 256x256 wgrad kernels: one workgroup per CU the launch may fill; SIMX_TN_ROUNDS=2 (read per call: the full-size
+// tests cover both rules in one process) two rounds, the rule of rounds 2-4
+int simx_tn_round();
+// Where the kernel writes: with one split C itself (it may accumulate); with more, f32 slabs of M x N in ws that
+// simx_slab_reduce adds into C in slice order, x 1/S of gs (gs_inv(NULL) == 1: bit-identical sums without a gradient scale).
+struct SimxTnOut { float* out; long slab_stride; int ld, accumulate; };
+static inline SimxTnOut simx_tn_out(int splits, void* ws, float* C, int M, int N, int ldc, int accumulate) {
+  return splits > 1 ? SimxTnOut{(float*)ws, (long)M * N, N, 0} : SimxTnOut{C, 0L, ldc, accumulate};
+}
+int simx_slab_reduce(hipStream_t s, const float* slabs, int splits, int M, int N, float* C, int ldc, int accumulate, const float* gs);
+// Bias gradient of a wgrad kernel.  SIMX_DETERMINISTIC=1: the kernel writes `nparts` partial rows of M floats (simx_det_ws) instead
+// of atomics into dbias, and finish() adds them into dbias in order.  Otherwise `rows` is dbias itself and finish() does nothing.
+struct SimxDetBias {
+  float* dbias;
+  float* rows;
+  int nparts, M;
+  SimxDetBias(hipStream_t s, float* dbias_, int nparts_, int M_)
+      : dbias(dbias_), rows(dbias_ && simx_det() ? simx_det_ws(s, (size_t)nparts_ * M_ * sizeof(float)) : dbias_), nparts(nparts_), M(M_) {}
+  bool ok() const { return rows || !dbias; }
+  int parts() const { return rows != dbias; }       // the kernels' dbias_parts flag
+  int finish(hipStream_t s, const float* gs) const {
+    return parts() ? simx_det_reduce(s, rows, (long)M, nparts, M, dbias, nullptr, nullptr, gs) : SIMX_OK;
+  }
+};
 // run STMT with TT bound to the element type of `dtype` (the three activation types of the engine)
 #define SIMX_DISPATCH3(DTYPE, TT, ...)                                   \
   do {                                                                   \

@@ -30,16 +30,18 @@ extern "C" int simx_version(void) { return 100; }
 // of the tile list; the wgrad plans fill exactly one round of the chip.  When another kernel holds k CUs for the whole launch -- an
 // RCCL ring during the overlapped backward -- k of those workgroups only start when a resident one has finished its WHOLE share:
 // the launch takes up to twice as long (tools/cu_steal_bench, profiles/r06_cu_steal.json).  With a budget of ncu - k the launches
-// fit beside the communication kernel and lose k / ncu instead.  0 = every CU (default; SIMX_COMPUTE_CUS overrides at first use).
-static int g_compute_cus = -1;
+// fit beside the communication kernel and lose k / ncu instead.  0 = every CU (default; SIMX_COMPUTE_CUS until the first explicit set).
+static std::atomic<int> g_compute_cus{-1};      // -1: no explicit set yet, the environment's value holds
 extern "C" int simx_set_compute_cus(int n) {
   SIMX_REQUIRE(n >= 0, SIMX_ERR_BAD_SHAPE, "simx_set_compute_cus: %d", n);
-  g_compute_cus = n;
+  g_compute_cus.store(n, std::memory_order_relaxed);
   return SIMX_OK;
 }
 int simx_compute_cus(int device_cus) {
-  if (g_compute_cus < 0) { const char* e = getenv("SIMX_COMPUTE_CUS"); g_compute_cus = e ? atoi(e) : 0; if (g_compute_cus < 0) g_compute_cus = 0; }
-  int n = g_compute_cus > 0 && g_compute_cus < device_cus ? g_compute_cus : device_cus;
+  static const int env_cus = [] { const char* e = getenv("SIMX_COMPUTE_CUS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
+  const int set = g_compute_cus.load(std::memory_order_relaxed);
+  const int budget = set < 0 ? env_cus : set;
+  int n = budget > 0 && budget < device_cus ? budget : device_cus;
   n -= n % 8;                                   // whole XCD rows: xcd_remap assumes block b -> XCD b % 8
   return n < 8 ? 8 : n;
 }

@@ -16,7 +16,6 @@
 //   * blockIdx -> tile map is XCD-aware: the 8 XCDs (private L2s) each walk a contiguous
 //     range of tiles so that the N-tiles sharing an A panel hit the same L2.
 // f32 path ("parity mode") and odd shapes: a plain LDS-tiled FMA kernel, k-ordered f32 accumulate.
-#include <mutex>
 #include <type_traits>
 #include "common.h"
 #include "prof.h"
@@ -1375,51 +1374,61 @@ __global__ __launch_bounds__(256) void cast_weight_kernel(const float* __restric
 // host entry points
 // ------------------------------------------------------------------------------------------
 // Per-device launch state (simx.h: "per-device caches are initialised once per device, thread-safely"): the CU count that
-// sizes the persistent grids and the dynamic-LDS limits of the kernels that need more than 64 KB.  hipFuncSetAttribute is
+// sizes the persistent grids, and the dynamic-LDS limits of the kernels that need more than 64 KB.  hipFuncSetAttribute is
 // a per-device setting, so every device the process touches gets its own std::call_once.
-struct GemmDevice { std::once_flag once; int ncu = 0; bool ok = false; };
-static GemmDevice g_gemm_dev[SIMX_MAX_DEVICES];
-static const GemmDevice* gemm_device() {
+int simx_device_cus() {
+  static std::once_flag once[SIMX_MAX_DEVICES];
+  static int ncu[SIMX_MAX_DEVICES];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SIMX_MAX_DEVICES) return nullptr;
-  GemmDevice& g = g_gemm_dev[dev];
-  std::call_once(g.once, [&g, dev] {
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SIMX_MAX_DEVICES) return 0;
+  std::call_once(once[dev], [dev] {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return;
-    g.ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    g.ncu -= g.ncu % 8;                           // whole XCD rows: xcd_remap assumes block b -> XCD b % 8
-    bool ok = true;
-#define SIMX_LDS_ATTR(KERNEL, BYTES) \
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)) == hipSuccess
-#define SIMX_LDS_ATTRS16(F)                                                           \
-    SIMX_LDS_ATTR((gemm_nt_h16_kernel<F, SIMX_EPI_NONE>), 2 * NT_STAGE_BYTES);           \
-    SIMX_LDS_ATTR((gemm_nt_h16_kernel<F, SIMX_EPI_GELU>), 2 * NT_STAGE_BYTES);           \
-    SIMX_LDS_ATTR((gemm_nt_h16_kernel<F, SIMX_EPI_DGELU>), 2 * NT_STAGE_BYTES);          \
-    SIMX_LDS_ATTR(gemm_tn_h16_kernel<F>, 2 * NT_STAGE_BYTES);                            \
-    SIMX_LDS_ATTR((gemm_nt_h16_v5_kernel<F, SIMX_EPI_NONE>), V5_LDS);                    \
-    SIMX_LDS_ATTR((gemm_nt_h16_v5_kernel<F, SIMX_EPI_GELU>), V5_LDS);                    \
-    SIMX_LDS_ATTR((gemm_nt_h16_v5_kernel<F, SIMX_EPI_DGELU>), V5_LDS);                   \
-    SIMX_LDS_ATTR((gemm_nt_p3_kernel<F, SIMX_EPI_NONE, false>), P_LDS);                  \
-    SIMX_LDS_ATTR((gemm_nt_p3_kernel<F, SIMX_EPI_NONE, true>), P_LDS);                   \
-    SIMX_LDS_ATTR((gemm_nt_p3_kernel<F, SIMX_EPI_GELU, false>), P_LDS);                  \
-    SIMX_LDS_ATTR((gemm_nt_p3_kernel<F, SIMX_EPI_DGELU, true>), P_LDS);                  \
-    SIMX_LDS_ATTR((gemm_nt_p3_kernel<F, SIMX_EPI_NONE, false, 2>), P_LDS);               \
-    SIMX_LDS_ATTR((gemm_nt_p3_kernel<F, SIMX_EPI_NONE, true, 1>), P_LDS);                \
-    SIMX_LDS_ATTR(gemm_tn2_kernel<F>, TN2_LDS)
-    SIMX_LDS_ATTRS16(bf16_t);
-    SIMX_LDS_ATTRS16(f16_t);
-#undef SIMX_LDS_ATTRS16
-#undef SIMX_LDS_ATTR
-    g.ok = ok;
+    const int n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    ncu[dev] = n - n % 8;
   });
-  return g.ok ? &g : nullptr;
+  return ncu[dev];
+}
+bool simx_set_lds_attrs(SimxLdsAttrs& st, const SimxLdsAttr* list, int n) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SIMX_MAX_DEVICES) return false;
+  std::call_once(st.once[dev], [&st, dev, list, n] {
+    bool ok = true;
+    for (int i = 0; i < n; ++i)
+      ok = ok && hipFuncSetAttribute(list[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, list[i].bytes) == hipSuccess;
+    st.ok[dev] = ok;
+  });
+  return st.ok[dev];
+}
+// this unit's CU count with its dynamic-LDS limits set; 0: the current device cannot be queried / configured
+static int gemm_device() {
+  static SimxLdsAttrs st;
+#define GEMM_LDS16(F)                                                                                                           \
+  simx_lds(gemm_nt_h16_kernel<F, SIMX_EPI_NONE>, 2 * NT_STAGE_BYTES), simx_lds(gemm_nt_h16_kernel<F, SIMX_EPI_GELU>, 2 * NT_STAGE_BYTES), \
+  simx_lds(gemm_nt_h16_kernel<F, SIMX_EPI_DGELU>, 2 * NT_STAGE_BYTES), simx_lds(gemm_tn_h16_kernel<F>, 2 * NT_STAGE_BYTES),            \
+  simx_lds(gemm_nt_h16_v5_kernel<F, SIMX_EPI_NONE>, V5_LDS), simx_lds(gemm_nt_h16_v5_kernel<F, SIMX_EPI_GELU>, V5_LDS),                 \
+  simx_lds(gemm_nt_h16_v5_kernel<F, SIMX_EPI_DGELU>, V5_LDS), simx_lds(gemm_nt_p3_kernel<F, SIMX_EPI_NONE, false>, P_LDS),              \
+  simx_lds(gemm_nt_p3_kernel<F, SIMX_EPI_NONE, true>, P_LDS), simx_lds(gemm_nt_p3_kernel<F, SIMX_EPI_GELU, false>, P_LDS),              \
+  simx_lds(gemm_nt_p3_kernel<F, SIMX_EPI_DGELU, true>, P_LDS), simx_lds(gemm_nt_p3_kernel<F, SIMX_EPI_NONE, false, 2>, P_LDS),          \
+  simx_lds(gemm_nt_p3_kernel<F, SIMX_EPI_NONE, true, 1>, P_LDS), simx_lds(gemm_tn2_kernel<F>, TN2_LDS)
+  static const SimxLdsAttr lds[] = {GEMM_LDS16(bf16_t), GEMM_LDS16(f16_t)};
+#undef GEMM_LDS16
+  const int ncu = simx_device_cus();
+  return ncu > 0 && simx_set_lds_attrs(st, lds, sizeof(lds) / sizeof(lds[0])) ? ncu : 0;
+}
+
+int simx_slab_reduce(hipStream_t s, const float* slabs, int splits, int M, int N, float* C, int ldc, int accumulate, const float* gs) {
+  long blocks = ((long)M * N / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((int)blocks), dim3(256), 0, s, slabs, (long)M * N, splits, M, N, C, ldc, accumulate, gs);
+  SIMX_CHECK_LAUNCH("slab_reduce");
+  return SIMX_OK;
 }
 
 static int operand_mode(const float* p, long stride_mn, long stride_k) {
   // 1: k contiguous, 2: m/n contiguous (16-B loads need a 16-B aligned base and leading dimension), 0: scalar
-  const bool al16 = (((uintptr_t)p) & 15) == 0;
-  if (stride_k == 1 && al16 && stride_mn % 4 == 0) return 1;
-  if (stride_mn == 1 && al16 && stride_k % 4 == 0) return 2;
+  if (stride_k == 1 && simx_al16(p) && stride_mn % 4 == 0) return 1;
+  if (stride_mn == 1 && simx_al16(p) && stride_k % 4 == 0) return 2;
   return 0;
 }
 // Split-K plan of the f32 MFMA kernel for problems whose 128x128 tile grid leaves most of the chip idle while K is long
@@ -1443,8 +1452,7 @@ static int launch_f32_mfma(hipStream_t s, int epi, int M, int N, int K, const fl
                            size_t ws_bytes = 0) {
   dim3 grid(cdiv(N, 128), cdiv(M, 128));
   const int am = operand_mode(A, a_rs, a_cs), bm = operand_mode(B, b_ns, b_ks);
-  if (epi == SIMX_EPI_NONE && !bias && !res && !drop.thr && ws && (((uintptr_t)ws) & 15) == 0 && ldc % 4 == 0 &&
-      (((uintptr_t)C) & 15) == 0) {
+  if (epi == SIMX_EPI_NONE && !bias && !res && !drop.thr && ws && simx_al16(ws) && ldc % 4 == 0 && simx_al16(C)) {
     const int sp = f32_splits(M, N, K, ws_bytes);
     if (sp > 1) {
       const int kps = cdiv(cdiv(K, sp), 16) * 16;
@@ -1452,13 +1460,7 @@ static int launch_f32_mfma(hipStream_t s, int epi, int M, int N, int K, const fl
       hipLaunchKernelGGL((gemm_f32_mfma_kernel<SIMX_EPI_NONE>), dim3(grid.x, grid.y, nsp), dim3(256), 0, s, M, N, K, A, a_rs, a_cs, B, b_ks,
                          b_ns, (float*)ws, N, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, 0, drop, am, bm, kps, (long)M * N);
       SIMX_CHECK_LAUNCH("gemm_f32_mfma(split)");
-      const long tot4 = (long)M * N / 4;
-      int rb = (int)((tot4 + 255) / 256);
-      if (rb > 2048) rb = 2048;
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(rb), dim3(256), 0, s, (const float*)ws, (long)M * N, nsp, M, N, C, ldc, accumulate,
-                         (const float*)nullptr);
-      SIMX_CHECK_LAUNCH("slab_reduce");
-      return SIMX_OK;
+      return simx_slab_reduce(s, (const float*)ws, nsp, M, N, C, ldc, accumulate, nullptr);
     }
   }
 #define LF(E) hipLaunchKernelGGL((gemm_f32_mfma_kernel<E>), grid, dim3(256), 0, s, M, N, K, A, a_rs, a_cs, B, b_ks, b_ns, C, ldc, bias, \
@@ -1476,12 +1478,9 @@ static int launch_simple(hipStream_t s, int epi, int M, int N, int K, const TI* 
                          const TI* B, long b_ks, long b_ns, TO* C, int ldc, const float* bias, const TI* res, int ldr,
                          const TI* aux, int ldaux, TO* C2, int ldc2, int accumulate, DropCtx drop = DropCtx{0u, 1.f, 0u, 0u},
                          void* ws = nullptr, size_t ws_bytes = 0, const float* gs = nullptr) {
-  if constexpr (std::is_same<TI, float>::value && std::is_same<TO, float>::value) {
-    static const char* pin = getenv("SIMX_GEMM_F32");           // SIMX_GEMM_F32=fma pins the VALU kernel (A/B measurements)
-    if (!(pin && pin[0] == 'f'))
-      return launch_f32_mfma(s, epi, M, N, K, A, a_rs, a_cs, B, b_ks, b_ns, C, ldc, bias, res, ldr, aux, ldaux, C2, ldc2, accumulate, drop,
-                             ws, ws_bytes);
-  }
+  if constexpr (std::is_same<TI, float>::value && std::is_same<TO, float>::value)
+    return launch_f32_mfma(s, epi, M, N, K, A, a_rs, a_cs, B, b_ks, b_ns, C, ldc, bias, res, ldr, aux, ldaux, C2, ldc2, accumulate, drop,
+                           ws, ws_bytes);
   dim3 grid(cdiv(N, 64), cdiv(M, 64));
 #define L(E) hipLaunchKernelGGL((gemm_simple_kernel<TI, TO, E>), grid, dim3(256), 0, s, M, N, K, A, a_rs, a_cs, B, b_ks, \
                                 b_ns, C, ldc, bias, res, ldr, aux, ldaux, C2, ldc2, accumulate, drop, gs)
@@ -1493,16 +1492,12 @@ static int launch_simple(hipStream_t s, int epi, int M, int N, int K, const TI* 
   return SIMX_OK;
 }
 
-static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 extern "C" int simx_gemm_nt_ex(simx_stream_t stream, int dtype, int M, int N, int K, const void* A, int lda,
                                const void* B, int ldb, void* C, int ldc, const float* bias, const void* residual,
                                int ldr, int epilogue, const void* aux, int ldaux, void* C2, int ldc2,
                                const simx_dropout* dropd);
 // csrc/gemm_p5.hip: the persistent kernel whose epilogue runs under the next tile's main loop (plain bias epilogue only so far).
 // SIMX_P5=0 keeps every launch on gemm_nt_p3_kernel (A/B measurements, tests/test_kernels_gpu.py compares the two bit for bit).
-int simx_launch_nt_p5(hipStream_t s, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
-                      const float* bias, int hm_c_rows, int ncu);
 // Default: the shapes where it measures faster -- K >= 1536 (FFN-out geometry: 0.877 vs 0.914 ms at M = 262144, N = 768, K = 3072;
 // at K = 768 the two tie, profiles/r06_experiments/01_p5.md).  SIMX_P5=1: every eligible launch, SIMX_P5=0: none.
 static bool p5_enabled(int K) {
@@ -1544,9 +1539,9 @@ extern "C" int simx_gemm_nt_ex(simx_stream_t stream, int dtype, int M, int N, in
   }
   SIMX_REQUIRE(simx_is16(dtype), SIMX_ERR_BAD_DTYPE, "gemm_nt: dtype %d", dtype);
   const bool fast = (K % 64 == 0) && (N % 4 == 0) && (lda % 8 == 0) && (ldb % 8 == 0) && (ldc % 4 == 0) &&
-                    aligned16(A) && aligned16(B) && aligned16(C) && (!bias || aligned16(bias)) &&
-                    (!residual || (ldr % 4 == 0 && aligned16(residual))) && (!aux || (ldaux % 4 == 0 && aligned16(aux))) &&
-                    (!C2 || (ldc2 % 4 == 0 && aligned16(C2)));
+                    simx_al16(A) && simx_al16(B) && simx_al16(C) && (!bias || simx_al16(bias)) &&
+                    (!residual || (ldr % 4 == 0 && simx_al16(residual))) && (!aux || (ldaux % 4 == 0 && simx_al16(aux))) &&
+                    (!C2 || (ldc2 % 4 == 0 && simx_al16(C2)));
   if (!fast) {
     int rcs = SIMX_OK;
     SIMX_DISPATCH16(dtype, TT, rcs = (launch_simple<TT, TT>(s, epilogue, M, N, K, (const TT*)A, lda, 1, (const TT*)B, 1, ldb, (TT*)C, ldc, bias,
@@ -1555,27 +1550,23 @@ extern "C" int simx_gemm_nt_ex(simx_stream_t stream, int dtype, int M, int N, in
   }
   const int tiles_m = cdiv(M, NT_BM), tiles_n = cdiv(N, NT_BN), nwg = tiles_m * tiles_n;
   const size_t lds = 2 * NT_STAGE_BYTES;
-  const GemmDevice* gd = gemm_device();
-  SIMX_REQUIRE(gd != nullptr, SIMX_ERR_HIP, "gemm_nt: cannot query the current device");
-  {
-    // SIMX_GEMM pins a kernel for A/B measurements: v1 = the 128x128 kernel, v5 = the per-tile 256x256 kernel
-    static const char* pin = getenv("SIMX_GEMM");
-    const bool force_v1 = pin && pin[1] == '1', force_v5 = pin && pin[1] == '5';
-    const int t3m = cdiv(M, 256), t3n = cdiv(N, 256), nwg3 = t3m * t3n;
-    // full 256x256 tiles, K >= 256: the persistent kernel, one workgroup per CU
-    if (!force_v1 && !force_v5 && nwg3 >= 192 && M % 256 == 0 && N % 256 == 0 && K >= 256 && ldc % 8 == 0 &&
-        (!residual || ldr % 8 == 0) && (!aux || ldaux % 8 == 0) && (!C2 || ldc2 % 8 == 0) &&
-        !(epilogue == SIMX_EPI_DGELU && residual) && !(epilogue == SIMX_EPI_GELU && residual)) {
-      const int ncu = simx_compute_cus(gd->ncu);
-      const int grid = nwg3 < ncu ? nwg3 : ncu;
-      if (epilogue == SIMX_EPI_NONE && !residual && !drop.thr && p5_enabled(K) &&
-          simx_launch_nt_p5(s, dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, 0, ncu) == SIMX_OK) {
-        simx_prof_retag(SIMX_K_GEMM_NT_P3);
-        return SIMX_OK;
-      }
+  const int ncu_dev = gemm_device();
+  SIMX_REQUIRE(ncu_dev > 0, SIMX_ERR_HIP, "gemm_nt: cannot query the current device");
+  const int t3m = cdiv(M, 256), t3n = cdiv(N, 256), nwg3 = t3m * t3n;
+  // full 256x256 tiles, K >= 256: the persistent kernel, one workgroup per CU
+  if (nwg3 >= 192 && M % 256 == 0 && N % 256 == 0 && K >= 256 && ldc % 8 == 0 &&
+      (!residual || ldr % 8 == 0) && (!aux || ldaux % 8 == 0) && (!C2 || ldc2 % 8 == 0) &&
+      !(epilogue == SIMX_EPI_DGELU && residual) && !(epilogue == SIMX_EPI_GELU && residual)) {
+    const int ncu = simx_compute_cus(ncu_dev);
+    const int grid = nwg3 < ncu ? nwg3 : ncu;
+    if (epilogue == SIMX_EPI_NONE && !residual && !drop.thr && p5_enabled(K) &&
+        simx_launch_nt_p5(s, dtype, M, N, K, A, lda, B, ldb, C, ldc, bias, 0, ncu) == SIMX_OK) {
+      simx_prof_retag(SIMX_K_GEMM_NT_P3);
+      return SIMX_OK;
+    }
 #ifdef SIMX_MEASUREMENT_HOOKS                   /* tools/build_variant.sh builds only: SIMX_NOEPI=1 times the main loop alone */
-      static const bool noepi_p = getenv("SIMX_NOEPI") != nullptr;
-      if (noepi_p) C = nullptr;
+    static const bool noepi_p = getenv("SIMX_NOEPI") != nullptr;
+    if (noepi_p) C = nullptr;
 #endif
 #define LP3(E, HI, INP, LDI) hipLaunchKernelGGL((gemm_nt_p3_kernel<FF, E, HI>), dim3(grid), dim3(512), P_LDS, s, M, N, K, (const bf16_t*)A, lda, \
                                  (const bf16_t*)B, ldb, (bf16_t*)C, ldc, bias, (const bf16_t*)(INP), LDI, (bf16_t*)C2, ldc2, t3n, nwg3, drop)
@@ -1585,30 +1576,29 @@ extern "C" int simx_gemm_nt_ex(simx_stream_t stream, int dtype, int M, int N, in
     else if (epilogue == SIMX_EPI_GELU) LP3(SIMX_EPI_GELU, false, nullptr, gelu_infer ? 1 : 0);                                 \
     else LP3(SIMX_EPI_DGELU, true, aux, ldaux);                                                                                 \
   } while (0)
-      SIMX_DISPATCH16(dtype, FF, LP3_ALL());
+    SIMX_DISPATCH16(dtype, FF, LP3_ALL());
 #undef LP3_ALL
 #undef LP3
-      simx_prof_retag(SIMX_K_GEMM_NT_P3);
-      SIMX_CHECK_LAUNCH("gemm_nt_p3");
-      return SIMX_OK;
-    }
-    // large ragged problems: the per-tile 256x256x64 two-stage kernel
-    if (!force_v1 && nwg3 >= 192 && N % 8 == 0 && ldc % 8 == 0 && (!residual || ldr % 8 == 0) &&
-        (!aux || ldaux % 8 == 0) && (!C2 || ldc2 % 8 == 0)) {
+    simx_prof_retag(SIMX_K_GEMM_NT_P3);
+    SIMX_CHECK_LAUNCH("gemm_nt_p3");
+    return SIMX_OK;
+  }
+  // large ragged problems: the per-tile 256x256x64 two-stage kernel
+  if (nwg3 >= 192 && N % 8 == 0 && ldc % 8 == 0 && (!residual || ldr % 8 == 0) &&
+      (!aux || ldaux % 8 == 0) && (!C2 || ldc2 % 8 == 0)) {
 #ifdef SIMX_MEASUREMENT_HOOKS
-      static const bool noepi = getenv("SIMX_NOEPI") != nullptr;
-      if (noepi) C = nullptr;
+    static const bool noepi = getenv("SIMX_NOEPI") != nullptr;
+    if (noepi) C = nullptr;
 #endif
 #define L5(E) hipLaunchKernelGGL((gemm_nt_h16_v5_kernel<FF, E>), dim3(nwg3), dim3(512), V5_LDS, s, M, N, K, (const bf16_t*)A, lda, \
                                  (const bf16_t*)B, ldb, (bf16_t*)C, ldc, bias, (const bf16_t*)residual, ldr,                  \
                                  (const bf16_t*)aux, ldaux, (bf16_t*)C2, ldc2, t3n, nwg3, drop)
 #define L5_ALL() do { if (epilogue == SIMX_EPI_NONE) L5(SIMX_EPI_NONE); else if (epilogue == SIMX_EPI_GELU) L5(SIMX_EPI_GELU); else L5(SIMX_EPI_DGELU); } while (0)
-      SIMX_DISPATCH16(dtype, FF, L5_ALL());
+    SIMX_DISPATCH16(dtype, FF, L5_ALL());
 #undef L5_ALL
 #undef L5
-      SIMX_CHECK_LAUNCH("gemm_nt_h16_v5");
-      return SIMX_OK;
-    }
+    SIMX_CHECK_LAUNCH("gemm_nt_h16_v5");
+    return SIMX_OK;
   }
 #define L(E) hipLaunchKernelGGL((gemm_nt_h16_kernel<FF, E>), dim3(nwg), dim3(256), lds, s, M, N, K, (const bf16_t*)A, lda, \
                                 (const bf16_t*)B, ldb, (bf16_t*)C, ldc, bias, (const bf16_t*)residual, ldr,               \
@@ -1626,8 +1616,7 @@ extern "C" int simx_gemm_nt_ex(simx_stream_t stream, int dtype, int M, int N, in
 //   a_hm_rows = R > 0: A is [K/64][R][64] (dq/dk/dv as the dgrad operand; `residual` required: it is the other gradient branch).
 // simx_gemm_hm_ok tells a caller whether both forms (and the wgrad form, simx_gemm_tn_hm) run for its shapes.
 extern "C" int simx_gemm_hm_ok(int rows, int H, int tokens) {
-  const GemmDevice* gd = gemm_device();
-  if (!gd || rows <= 0 || H <= 0) return 0;
+  if (gemm_device() == 0 || rows <= 0 || H <= 0) return 0;
   const bool shapes = rows % 256 == 0 && H % 256 == 0 && H >= 256;
   const long dgrad_tiles = (long)(rows / 256) * (H / 256);            // the narrowest of the three GEMMs (N = H)
   return shapes && dgrad_tiles >= 192 && tokens >= 2048 ? 1 : 0;
@@ -1650,17 +1639,17 @@ extern "C" int simx_gemm_nt_pb(simx_stream_t stream, int dtype, int M, int N, in
   if (infer) epilogue = SIMX_EPI_GELU;
   const bool combo = epilogue == SIMX_EPI_NONE && ((flags == 1 && in) || (flags == 2 && !in));
   SIMX_REQUIRE(combo, SIMX_ERR_UNSUPPORTED, "gemm_nt_pb: epilogue %d with plane flags %d is not built", epilogue, flags);
-  const GemmDevice* gd = gemm_device();
-  SIMX_REQUIRE(gd != nullptr, SIMX_ERR_HIP, "gemm_nt_pb: cannot query the current device");
+  const int ncu_dev = gemm_device();
+  SIMX_REQUIRE(ncu_dev > 0, SIMX_ERR_HIP, "gemm_nt_pb: cannot query the current device");
   const int t3n = N / 256, nwg3 = (M / 256) * t3n;
   const bool pa = flags & 1, pc = flags & 2, pi = flags & 4;
   const bool ok = M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K >= 256 && nwg3 >= 192 && rows >= M && ldb % 8 == 0 && ldb >= K &&
-                  aligned16(A) && aligned16(B) && aligned16(C) && (!C2 || aligned16(C2)) && (!bias || aligned16(bias)) &&
-                  (!in || aligned16(in)) && (pa || (lda % 8 == 0 && lda >= K)) && (pc || (ldc % 8 == 0 && ldc >= N)) &&
+                  simx_al16(A) && simx_al16(B) && simx_al16(C) && (!C2 || simx_al16(C2)) && (!bias || simx_al16(bias)) &&
+                  (!in || simx_al16(in)) && (pa || (lda % 8 == 0 && lda >= K)) && (pc || (ldc % 8 == 0 && ldc >= N)) &&
                   (!in || pi || (ldin % 8 == 0 && ldin >= N)) && (!C2 || pc || (ldc2 % 8 == 0 && ldc2 >= N));
   SIMX_REQUIRE(ok, SIMX_ERR_UNSUPPORTED, "gemm_nt_pb: shape %d x %d x %d (planes of %d rows) is outside the persistent kernel's rules", M, N, K, rows);
   const DropCtx drop = make_drop(epilogue == SIMX_EPI_NONE ? dropd : nullptr);
-  const int ncu = simx_compute_cus(gd->ncu);
+  const int ncu = simx_compute_cus(ncu_dev);
   const int grid = nwg3 < ncu ? nwg3 : ncu;
   if (flags == 2 && !drop.thr && p5_enabled(K) && simx_launch_nt_p5(s, dtype, M, N, K, A, lda, B, ldb, C, 64, bias, rows, ncu) == SIMX_OK) {
     simx_prof_retag(SIMX_K_GEMM_NT_P3);
@@ -1684,42 +1673,40 @@ extern "C" int simx_gemm_nt_hm(simx_stream_t stream, int dtype, int M, int N, in
                          a_hm_rows > 0 ? 1 : 2, a_hm_rows > 0 ? a_hm_rows : c_hm_rows);
 }
 
-static bool tn_use_v2(int M, int N, int K) {
-  static const char* pin = getenv("SIMX_GEMM_TN");
-  if (pin && pin[1] == '1') return false;
-  return M >= 256 && N >= 256 && K >= 2048;
-}
-static void tn_plan(int M, int N, int K, int* splits, int* k_per_split) {
-  const bool v2 = tn_use_v2(M, N, K);
-  const int tiles = v2 ? cdiv(M, 256) * cdiv(N, 256) : cdiv(M, 128) * cdiv(N, 128);
-  // whole rounds of the chip: v2 runs one workgroup per CU (256 per round), v1 two.  Rounding the split count UP
-  // (513 workgroups for wqkv/wo, 540 for w1/w2) left a third, almost empty round; rounds 2-4 filled exactly TWO rounds; ONE
-  // round (half the splits: each workgroup pays its prologue, its 256 KB slab epilogue and its share of the slab pass once
-  // for twice the tokens) measures better at every size -- 262144 tokens 3.54 -> 3.37 ms over the four wgrad shapes, 32768
-  // tokens 0.61 -> 0.52, 16384 tokens 0.41 -> 0.32 (tools/kbench, profiles/r05_experiments/09).  SIMX_TN_ROUNDS=2: the old rule.
-  const char* rounds_env = getenv("SIMX_TN_ROUNDS");       // (read per call: tests/test_fullsize_gpu.py covers both rules in one process)
-  const int round = simx_compute_cus(256);      // one workgroup per CU the launch may fill (256 unless a compute-CU budget is set)
-  int s = (v2 ? (rounds_env && rounds_env[0] == '2' ? 2 * round : round) : 1024) / tiles;
+static bool tn_use_v2(int M, int N, int K) { return M >= 256 && N >= 256 && K >= 2048; }
+SimxSplitK simx_splitk_plan(int tiles, int K, int round, int kstep) {
+  int s = round / tiles;
   const int max_s = cdiv(K, 512);          // at least 8 k-tiles per split
   if (s > max_s) s = max_s;
   if (s < 1) s = 1;
-  int kps = cdiv(cdiv(K, s), 64) * 64;
-  s = cdiv(K, kps);
-  *splits = s;
-  *k_per_split = kps;
+  const int kps = cdiv(cdiv(K, s), kstep) * kstep;
+  return {cdiv(K, kps), kps};
+}
+// Whole rounds of the chip: the 256x256 kernels run one workgroup per CU.  Rounding the split count UP (513 workgroups for
+// wqkv/wo, 540 for w1/w2) left a third, almost empty round; rounds 2-4 filled exactly TWO rounds; ONE round (half the splits:
+// each workgroup pays its prologue, its 256 KB slab epilogue and its share of the slab pass once for twice the tokens) measures
+// better at every size -- 262144 tokens 3.54 -> 3.37 ms over the four wgrad shapes, 32768 tokens 0.61 -> 0.52, 16384 tokens
+// 0.41 -> 0.32 (tools/kbench, profiles/r05_experiments/09).  SIMX_TN_ROUNDS=2: the old rule.
+int simx_tn_round() {
+  const char* rounds = getenv("SIMX_TN_ROUNDS");
+  const int ncu = simx_device_cus();             // (a workspace query without a device plans for the MI355X's 256)
+  const int round = simx_compute_cus(ncu > 0 ? ncu : 256);
+  return rounds && rounds[0] == '2' ? 2 * round : round;
+}
+// the 128x128 kernel runs two workgroups per CU: 1024 (~4 per CU) keeps its tail short
+static SimxSplitK tn_plan(int M, int N, int K) {
+  if (tn_use_v2(M, N, K)) return simx_splitk_plan(cdiv(M, 256) * cdiv(N, 256), K, simx_tn_round(), 64);
+  return simx_splitk_plan(cdiv(M, 128) * cdiv(N, 128), K, 1024, 64);
 }
 
 extern "C" size_t simx_gemm_tn_workspace_bytes(int M, int N, int K) {
-  int s, kps;
-  tn_plan(M, N, K, &s, &kps);
+  const int s = tn_plan(M, N, K).splits;
   const size_t bf = s > 1 ? (size_t)s * M * N * sizeof(float) : 0, f32 = simx_gemm_f32_workspace_bytes(M, N, K);
   const size_t x3 = simx_x3_tn_workspace_bytes(M, N, K);
   const size_t m2 = bf > f32 ? bf : f32;
   return m2 > x3 ? m2 : x3;                     // (the dtype is not an argument: enough for any of them)
 }
 
-int simx_launch_tn5(hipStream_t s, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* slabs,
-                    int splits, int kps, float* dbias, int a_hm_rows, const float* gs);
 static int gemm_tn_impl(simx_stream_t stream, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* C,
                         int ldc, int accumulate, void* ws, size_t ws_bytes, float* dbias, int a_hm_rows, const float* gs);
 extern "C" int simx_gemm_tn(simx_stream_t stream, int dtype, int M, int N, int K, const void* A, int lda,
@@ -1764,8 +1751,8 @@ static int gemm_tn_impl(simx_stream_t stream, int dtype, int M, int N, int K, co
                                        ldc, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, accumulate, DropCtx{0u, 1.f, 0u, 0u}, ws, ws_bytes);
   }
   SIMX_REQUIRE(simx_is16(dtype), SIMX_ERR_BAD_DTYPE, "gemm_tn: dtype %d", dtype);
-  const bool fast = (M % 8 == 0) && (N % 8 == 0) && (lda % 8 == 0) && (ldb % 8 == 0) && (ldc % 4 == 0) && aligned16(A) &&
-                    aligned16(B) && aligned16(C);
+  const bool fast = (M % 8 == 0) && (N % 8 == 0) && (lda % 8 == 0) && (ldb % 8 == 0) && (ldc % 4 == 0) && simx_al16(A) &&
+                    simx_al16(B) && simx_al16(C);
   SIMX_REQUIRE(a_hm_rows == 0 || fast, SIMX_ERR_UNSUPPORTED, "gemm_tn_hm: operands not 16-B aligned");
   if (!fast) {
     if (dbias) { int rcb = simx_colsum_gs(stream, dtype, K, M, A, lda, dbias, 1, gs); if (rcb) return rcb; }
@@ -1777,80 +1764,45 @@ static int gemm_tn_impl(simx_stream_t stream, int dtype, int M, int N, int K, co
     SIMX_CHECK_LAUNCH("gemm_simple(tn)");
     return SIMX_OK;
   }
-  int splits, kps;
-  tn_plan(M, N, K, &splits, &kps);
-  SIMX_REQUIRE(a_hm_rows == 0 || tn_use_v2(M, N, K), SIMX_ERR_UNSUPPORTED, "gemm_tn_hm: shape outside the 256x256 kernel's rules");
-  if (tn_use_v2(M, N, K)) {
-    SIMX_REQUIRE(gemm_device() != nullptr, SIMX_ERR_HIP, "gemm_tn: cannot query the current device");
+  const SimxSplitK plan = tn_plan(M, N, K);
+  const int splits = plan.splits, kps = plan.kps;
+  const bool v2 = tn_use_v2(M, N, K);
+  SIMX_REQUIRE(a_hm_rows == 0 || v2, SIMX_ERR_UNSUPPORTED, "gemm_tn_hm: shape outside the 256x256 kernel's rules");
+  if (splits > 1) {
+    const size_t need = (size_t)splits * M * N * sizeof(float);
+    SIMX_REQUIRE(ws && ws_bytes >= need, SIMX_ERR_WORKSPACE, "gemm_tn: workspace %zu < %zu", ws_bytes, need);
+    SIMX_REQUIRE(simx_al16(ws), SIMX_ERR_WORKSPACE, "gemm_tn: workspace not 16-B aligned");
+  }
+  const SimxTnOut o = simx_tn_out(splits, ws, C, M, N, ldc, accumulate);
+  if (v2) {
+    SIMX_REQUIRE(gemm_device() > 0, SIMX_ERR_HIP, "gemm_tn: cannot query the current device");
     const int t_m = cdiv(M, 256), t_n = cdiv(N, 256), t_mn = t_m * t_n;
     simx_prof_retag(SIMX_K_GEMM_TN2);              // the large-shape wgrad kernel (with its slab pass) apart from the small launches
-    float* dbias_out = dbias;
-    const int nbp = splits * t_n * 4;
-    if (dbias && simx_det()) {                    // ordered bias gradient: one partial row per contributing wave column
-      dbias = simx_det_ws(s, (size_t)nbp * M * sizeof(float));
-      if (!dbias) return SIMX_ERR_WORKSPACE;
-    }
-    const int dparts = dbias != dbias_out;
-    if (splits == 1) {
-      SIMX_DISPATCH16(dtype, FF, hipLaunchKernelGGL(gemm_tn2_kernel<FF>, dim3(t_mn), dim3(512), TN2_LDS, s, M, N, K, (const bf16_t*)A, lda,
-                                                    (const bf16_t*)B, ldb, C, 0L, ldc, t_n, t_mn, kps, accumulate, dbias, a_hm_rows, gs, 1, dparts));
-      SIMX_CHECK_LAUNCH("gemm_tn2");
-      if (dparts) return simx_det_reduce(s, dbias, (long)M, nbp, M, dbias_out, nullptr, nullptr, gs);
-      return SIMX_OK;
-    }
-    const size_t need2 = (size_t)splits * M * N * sizeof(float);
-    SIMX_REQUIRE(ws && ws_bytes >= need2, SIMX_ERR_WORKSPACE, "gemm_tn: workspace %zu < %zu", ws_bytes, need2);
-    SIMX_REQUIRE(aligned16(ws), SIMX_ERR_WORKSPACE, "gemm_tn: workspace not 16-B aligned");
+    const SimxDetBias db(s, dbias, splits * t_n * 4, M);     // ordered mode: one partial row per contributing wave column
+    if (!db.ok()) return SIMX_ERR_WORKSPACE;
     // csrc/gemm_tn5.hip: one wave per SIMD, AGPR accumulators, 96 KB in flight -- full tiles, whole stages, not the ordered mode.
     // SIMX_TN5=0 keeps gemm_tn2_kernel (A/B measurements; read per call: the kernel test compares the two in one process).
-    {
-      const char* e5 = getenv("SIMX_TN5");
-      if (!(e5 && e5[0] == '0') && !dparts &&
-          simx_launch_tn5(s, dtype, M, N, K, A, lda, B, ldb, (float*)ws, splits, kps, dbias, a_hm_rows, gs) == SIMX_OK) {
-        const long tot4 = (long)M * N / 4;
-        int rb = (int)((tot4 + 255) / 256);
-        if (rb > 2048) rb = 2048;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(rb), dim3(256), 0, s, (const float*)ws, (long)M * N, splits, M, N, C, ldc, accumulate, gs);
-        SIMX_CHECK_LAUNCH("slab_reduce");
-        return SIMX_OK;
-      }
-    }
+    const char* e5 = getenv("SIMX_TN5");
+    if (splits > 1 && !(e5 && e5[0] == '0') && !db.parts() &&
+        simx_launch_tn5(s, dtype, M, N, K, A, lda, B, ldb, (float*)ws, splits, kps, dbias, a_hm_rows, gs) == SIMX_OK)
+      return simx_slab_reduce(s, (const float*)ws, splits, M, N, C, ldc, accumulate, gs);
     SIMX_DISPATCH16(dtype, FF, hipLaunchKernelGGL(gemm_tn2_kernel<FF>, dim3(t_mn * splits), dim3(512), TN2_LDS, s, M, N, K, (const bf16_t*)A, lda,
-                                                  (const bf16_t*)B, ldb, (float*)ws, (long)M * N, N, t_n, t_mn, kps, 0, dbias, a_hm_rows, gs, 0, dparts));
+                                                  (const bf16_t*)B, ldb, o.out, o.slab_stride, o.ld, t_n, t_mn, kps, o.accumulate, db.rows,
+                                                  a_hm_rows, gs, splits == 1, db.parts()));
     SIMX_CHECK_LAUNCH("gemm_tn2");
-    if (dparts) { int rcd = simx_det_reduce(s, dbias, (long)M, nbp, M, dbias_out, nullptr, nullptr, gs); if (rcd) return rcd; }
-    const long tot4 = (long)M * N / 4;
-    int rb = (int)((tot4 + 255) / 256);
-    if (rb > 2048) rb = 2048;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(rb), dim3(256), 0, s, (const float*)ws, (long)M * N, splits, M, N, C, ldc, accumulate, gs);
-    SIMX_CHECK_LAUNCH("slab_reduce");
-    return SIMX_OK;
-  }
-  if (dbias) {                                   // small problems: separate column-sum pass
-    int rcb = simx_colsum_gs(stream, dtype, K, M, A, lda, dbias, 1, gs);
-    if (rcb) return rcb;
-  }
-  const int tiles_m = cdiv(M, 128), tiles_n = cdiv(N, 128), tiles_mn = tiles_m * tiles_n;
-  const size_t lds = 2 * NT_STAGE_BYTES;
-  if (splits == 1) {
-    SIMX_DISPATCH16(dtype, FF, hipLaunchKernelGGL(gemm_tn_h16_kernel<FF>, dim3(tiles_mn), dim3(256), lds, s, M, N, K, (const bf16_t*)A, lda,
-                                                  (const bf16_t*)B, ldb, C, 0L, ldc, tiles_n, tiles_mn, kps, accumulate, gs));
+    if (int rc = db.finish(s, gs)) return rc;
+  } else {
+    if (dbias) {                                   // small problems: separate column-sum pass
+      int rcb = simx_colsum_gs(stream, dtype, K, M, A, lda, dbias, 1, gs);
+      if (rcb) return rcb;
+    }
+    const int tiles_m = cdiv(M, 128), tiles_n = cdiv(N, 128), tiles_mn = tiles_m * tiles_n;
+    SIMX_DISPATCH16(dtype, FF, hipLaunchKernelGGL(gemm_tn_h16_kernel<FF>, dim3(tiles_mn * splits), dim3(256), 2 * NT_STAGE_BYTES, s, M, N, K,
+                                                  (const bf16_t*)A, lda, (const bf16_t*)B, ldb, o.out, o.slab_stride, o.ld, tiles_n, tiles_mn,
+                                                  kps, o.accumulate, splits == 1 ? gs : nullptr));
     SIMX_CHECK_LAUNCH("gemm_tn_h16");
-    return SIMX_OK;
   }
-  const size_t need = (size_t)splits * M * N * sizeof(float);
-  SIMX_REQUIRE(ws && ws_bytes >= need, SIMX_ERR_WORKSPACE, "gemm_tn: workspace %zu < %zu", ws_bytes, need);
-  SIMX_REQUIRE(aligned16(ws), SIMX_ERR_WORKSPACE, "gemm_tn: workspace not 16-B aligned");
-  SIMX_DISPATCH16(dtype, FF, hipLaunchKernelGGL(gemm_tn_h16_kernel<FF>, dim3(tiles_mn * splits), dim3(256), lds, s, M, N, K, (const bf16_t*)A, lda,
-                                                (const bf16_t*)B, ldb, (float*)ws, (long)M * N, N, tiles_n, tiles_mn, kps, 0, (const float*)nullptr));
-  SIMX_CHECK_LAUNCH("gemm_tn_h16");
-  const long total4 = (long)M * N / 4;
-  int blocks = (int)((total4 + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)ws, (long)M * N, splits, M, N, C,
-                     ldc, accumulate, gs);
-  SIMX_CHECK_LAUNCH("slab_reduce");
-  return SIMX_OK;
+  return splits > 1 ? simx_slab_reduce(s, (const float*)ws, splits, M, N, C, ldc, accumulate, gs) : SIMX_OK;
 }
 
 extern "C" int simx_colsum(simx_stream_t stream, int dtype, int T, int N, const void* x, int ldx, float* out,
@@ -1975,7 +1927,7 @@ int simx_transpose_cast_group(hipStream_t s, int out_dtype, const SimxCastGroup*
   for (int i = 0; i < gg.n; ++i) {
     const SimxCastJob& jb = gg.job[i];
     SIMX_REQUIRE(jb.rows > 0 && jb.cols > 0 && jb.w, SIMX_ERR_BAD_SHAPE, "transpose_cast_group: bad job %d", i);
-    wide = wide && jb.rows % 64 == 0 && jb.cols % 64 == 0 && aligned16(jb.w) && aligned16(jb.out) && aligned16(jb.outT);
+    wide = wide && jb.rows % 64 == 0 && jb.cols % 64 == 0 && simx_al16(jb.w) && simx_al16(jb.out) && simx_al16(jb.outT);
   }
   const int ts = wide ? 64 : 32;
   for (int i = 0; i < gg.n; ++i) {

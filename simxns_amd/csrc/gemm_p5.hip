@@ -434,23 +434,15 @@ __global__ __launch_bounds__(256) void gemm_nt_p5_kernel(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-static bool p5_attr_done[SIMX_MAX_DEVICES];
 // Eligibility + launch; returns SIMX_ERR_UNSUPPORTED (without an error text) when the shape is outside this kernel's rules, so that
 // the caller falls through to gemm_nt_p3_kernel.
 int simx_launch_nt_p5(hipStream_t s, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
                       const float* bias, int hm_c_rows, int ncu) {
   if (!(M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K >= 576 && lda % 8 == 0 && lda == ldb && simx_is16(dtype))) return SIMX_ERR_UNSUPPORTED;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SIMX_MAX_DEVICES) return SIMX_ERR_UNSUPPORTED;
-  if (!p5_attr_done[dev]) {
-    bool ok = true;
-#define P5_ATTR(KRN) ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(KRN), hipFuncAttributeMaxDynamicSharedMemorySize, P5_LDS) == hipSuccess
-    P5_ATTR((gemm_nt_p5_kernel<f16_t, false>)); P5_ATTR((gemm_nt_p5_kernel<f16_t, true>));
-    P5_ATTR((gemm_nt_p5_kernel<bf16_t, false>)); P5_ATTR((gemm_nt_p5_kernel<bf16_t, true>));
-#undef P5_ATTR
-    if (!ok) return SIMX_ERR_UNSUPPORTED;
-    p5_attr_done[dev] = true;
-  }
+  static SimxLdsAttrs st;
+  static const SimxLdsAttr lds[] = {simx_lds(gemm_nt_p5_kernel<f16_t, false>, P5_LDS), simx_lds(gemm_nt_p5_kernel<f16_t, true>, P5_LDS),
+                                    simx_lds(gemm_nt_p5_kernel<bf16_t, false>, P5_LDS), simx_lds(gemm_nt_p5_kernel<bf16_t, true>, P5_LDS)};
+  if (!simx_set_lds_attrs(st, lds, sizeof(lds) / sizeof(lds[0]))) return SIMX_ERR_UNSUPPORTED;
   const int t_n = N / 256, ntiles = (M / 256) * t_n;
   const int grid = ntiles < ncu ? ntiles : ncu;
 #define LP5(FF, HM) hipLaunchKernelGGL((gemm_nt_p5_kernel<FF, HM>), dim3(grid), dim3(256), P5_LDS, s, M, N, K, (const bf16_t*)A, lda, \

@@ -310,7 +310,6 @@ __global__ __launch_bounds__(256) void gemm_tn5_kernel(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-static bool t5_attr_done[SIMX_MAX_DEVICES];
 // Eligibility + launch of the slab kernel (the caller runs slab_reduce_kernel behind it); SIMX_ERR_UNSUPPORTED (no error text)
 // when the shape is outside the rules above, so that the caller falls through to gemm_tn2_kernel.
 int simx_launch_tn5(hipStream_t s, int dtype, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* slabs,
@@ -318,14 +317,9 @@ int simx_launch_tn5(hipStream_t s, int dtype, int M, int N, int K, const void* A
   if (!(simx_is16(dtype) && M % 256 == 0 && N % 256 == 0 && kps % 64 == 0 && splits >= 2 && kps >= 256 &&
         K - (splits - 1) * (long)kps >= 256))
     return SIMX_ERR_UNSUPPORTED;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SIMX_MAX_DEVICES) return SIMX_ERR_UNSUPPORTED;
-  if (!t5_attr_done[dev]) {
-    bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn5_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T5_LDS) == hipSuccess;
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn5_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T5_LDS) == hipSuccess;
-    if (!ok) return SIMX_ERR_UNSUPPORTED;
-    t5_attr_done[dev] = true;
-  }
+  static SimxLdsAttrs st;
+  static const SimxLdsAttr lds[] = {simx_lds(gemm_tn5_kernel<f16_t>, T5_LDS), simx_lds(gemm_tn5_kernel<bf16_t>, T5_LDS)};
+  if (!simx_set_lds_attrs(st, lds, sizeof(lds) / sizeof(lds[0]))) return SIMX_ERR_UNSUPPORTED;
   const int t_n = N / 256, t_mn = (M / 256) * t_n;
   if (dtype == SIMX_F16)
     hipLaunchKernelGGL(gemm_tn5_kernel<f16_t>, dim3(t_mn * splits), dim3(256), T5_LDS, s, M, N, K, (const bf16_t*)A, lda, (const bf16_t*)B, ldb,

@@ -40,24 +40,6 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t&
 #define X3_PLANE (128 * 64)                 // one 128 x 32 16-bit plane
 #define X3_STAGE (4 * X3_PLANE)             // Ahi | Alo | Bhi | Blo
 
-// slabs added in slice order (deterministic), as slab_reduce_kernel of csrc/gemm.hip (kernels do not link across translation units)
-__global__ __launch_bounds__(256) void x3_slab_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int splits, int M, int N,
-                                                             float* __restrict__ C, int ldc, int accumulate) {
-  const long total4 = (long)M * N / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
-    const long e = i * 4;
-    const int m = (int)(e / N), n = (int)(e % N);
-    float4 s = make_float4(0, 0, 0, 0);
-    for (int k = 0; k < splits; ++k) {
-      const float4 v = *reinterpret_cast<const float4*>(slabs + (long)k * slab_stride + e);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    float4* dst = reinterpret_cast<float4*>(C + (long)m * ldc + n);
-    if (accumulate) { const float4 c = *dst; s.x += c.x; s.y += c.y; s.z += c.z; s.w += c.w; }
-    *dst = s;
-  }
-}
-
 template <typename F, int EPI>
 __global__ __launch_bounds__(256, 3) void gemm_x3_nt_kernel(
     int M, int N, int K, const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ C, int ldc,
@@ -338,13 +320,11 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_tn_kernel(
 }
 
 // ------------------------------------------------------------------------------------------ host
-static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // can the split kernels take this NT problem?  (whole float4s everywhere; anything else stays on the exact kernel)
 bool simx_x3_nt_ok(int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C, int ldc, const float* bias,
                    const float* res, int ldr, const float* aux, int ldaux, const float* C2, int ldc2) {
-  return K % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && al16(A) && al16(B) && al16(C) && (!bias || al16(bias)) &&
-         (!res || (ldr % 4 == 0 && al16(res))) && (!aux || (ldaux % 4 == 0 && al16(aux))) && (!C2 || (ldc2 % 4 == 0 && al16(C2))) &&
+  return K % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && simx_al16(A) && simx_al16(B) && simx_al16(C) && (!bias || simx_al16(bias)) &&
+         (!res || (ldr % 4 == 0 && simx_al16(res))) && (!aux || (ldaux % 4 == 0 && simx_al16(aux))) && (!C2 || (ldc2 % 4 == 0 && simx_al16(C2))) &&
          (long)M * N >= 64 * 1024 && K >= 64;
 }
 
@@ -363,51 +343,27 @@ int simx_x3_gemm_nt(hipStream_t s, int fmt, int epi, int M, int N, int K, const 
 }
 
 bool simx_x3_tn_ok(int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C, int ldc) {
-  return M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && al16(A) && al16(B) && al16(C) && (long)M * N >= 16 * 1024 &&
+  return M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && simx_al16(A) && simx_al16(B) && simx_al16(C) && (long)M * N >= 16 * 1024 &&
          K >= 256;
 }
-static void x3_tn_plan(int M, int N, int K, int* splits, int* kps) {
-  const int tiles = cdiv(M, X3_BM) * cdiv(N, X3_BN);
-  int sp = 1024 / tiles;                            // two workgroups per CU: ~4 per CU keeps the tail short
-  const int max_s = cdiv(K, 512);
-  if (sp > max_s) sp = max_s;
-  if (sp < 1) sp = 1;
-  int k = cdiv(cdiv(K, sp), X3_BK) * X3_BK;
-  *splits = cdiv(K, k);
-  *kps = k;
-}
+// 128x128 tiles, two workgroups per CU: ~4 per CU (1024 per round) keeps the tail short
+static SimxSplitK x3_tn_plan(int M, int N, int K) { return simx_splitk_plan(cdiv(M, X3_BM) * cdiv(N, X3_BN), K, 1024, X3_BK); }
 size_t simx_x3_tn_workspace_bytes(int M, int N, int K) {
-  int sp, kps;
-  x3_tn_plan(M, N, K, &sp, &kps);
+  const int sp = x3_tn_plan(M, N, K).splits;
   return sp > 1 ? (size_t)sp * M * N * sizeof(float) : 0;
 }
 int simx_x3_gemm_tn(hipStream_t s, int fmt, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     int accumulate, void* ws, size_t ws_bytes, float* dbias) {
-  int sp, kps;
-  x3_tn_plan(M, N, K, &sp, &kps);
+  SimxSplitK plan = x3_tn_plan(M, N, K);
   const int t_n = cdiv(N, X3_BN), t_mn = cdiv(M, X3_BM) * t_n;
-  if (sp > 1 && (!ws || ws_bytes < (size_t)sp * M * N * sizeof(float) || !al16(ws))) { sp = 1; kps = cdiv(K, X3_BK) * X3_BK; }
-  float* dbias_out = dbias;
-  if (dbias && simx_det()) {                      // ordered bias gradient: one partial row per split
-    dbias = simx_det_ws(s, (size_t)sp * M * sizeof(float));
-    if (!dbias) return SIMX_ERR_WORKSPACE;
-  }
-  const int dparts = dbias != dbias_out;
-  if (sp == 1) {
-    SIMX_DISPATCH16(fmt, FF, hipLaunchKernelGGL(gemm_x3_tn_kernel<FF>, dim3(t_mn), dim3(256), 0, s, M, N, K, A, lda, B, ldb, C, 0L, ldc, t_n, t_mn,
-                                                kps, accumulate, dbias, dparts));
-    SIMX_CHECK_LAUNCH("gemm_x3_tn");
-    if (dparts) return simx_det_reduce(s, dbias, (long)M, sp, M, dbias_out, nullptr, nullptr, nullptr);
-    return SIMX_OK;
-  }
-  SIMX_DISPATCH16(fmt, FF, hipLaunchKernelGGL(gemm_x3_tn_kernel<FF>, dim3(t_mn * sp), dim3(256), 0, s, M, N, K, A, lda, B, ldb, (float*)ws,
-                                              (long)M * N, N, t_n, t_mn, kps, 0, dbias, dparts));
+  if (plan.splits > 1 && (!ws || ws_bytes < (size_t)plan.splits * M * N * sizeof(float) || !simx_al16(ws))) plan = {1, cdiv(K, X3_BK) * X3_BK};
+  const int sp = plan.splits;
+  const SimxDetBias db(s, dbias, sp, M);           // ordered mode: one partial row per split
+  if (!db.ok()) return SIMX_ERR_WORKSPACE;
+  const SimxTnOut o = simx_tn_out(sp, ws, C, M, N, ldc, accumulate);
+  SIMX_DISPATCH16(fmt, FF, hipLaunchKernelGGL(gemm_x3_tn_kernel<FF>, dim3(t_mn * sp), dim3(256), 0, s, M, N, K, A, lda, B, ldb, o.out,
+                                              o.slab_stride, o.ld, t_n, t_mn, plan.kps, o.accumulate, db.rows, db.parts()));
   SIMX_CHECK_LAUNCH("gemm_x3_tn");
-  if (dparts) { int rcd = simx_det_reduce(s, dbias, (long)M, sp, M, dbias_out, nullptr, nullptr, nullptr); if (rcd) return rcd; }
-  const long tot4 = (long)M * N / 4;
-  int rb = (int)((tot4 + 255) / 256);
-  if (rb > 2048) rb = 2048;
-  hipLaunchKernelGGL(x3_slab_reduce_kernel, dim3(rb), dim3(256), 0, s, (const float*)ws, (long)M * N, sp, M, N, C, ldc, accumulate);
-  SIMX_CHECK_LAUNCH("slab_reduce");
-  return SIMX_OK;
+  if (int rc = db.finish(s, nullptr)) return rc;
+  return sp > 1 ? simx_slab_reduce(s, (const float*)ws, sp, M, N, C, ldc, accumulate, nullptr) : SIMX_OK;
 }

@@ -17,7 +17,6 @@
 //   SIMX_EPI_GELU  : C = gelu'(u) f32 (skipped when C == NULL), Cp = planes of gelu(u), u = acc + bias
 //   SIMX_EPI_DGELU : Cp = planes of acc * in                              (in = the stored derivative, f32)
 // Reference op: the nn.Linear's of LEAD/modeling_bert.py:285-310, 385, 450, 463 in fp32 (SimANS/train_MS_Pas_AR2.sh:8-26).
-#include <mutex>
 #include <type_traits>
 #include "common.h"
 #include "prof.h"
@@ -844,23 +843,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_xq_kernel(
 #undef XQ_ADDR_HI
 }
 
-__global__ __launch_bounds__(256) void xp_slab_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int splits, int M, int N,
-                                                             float* __restrict__ C, int ldc, int accumulate) {
-  const long total4 = (long)M * N / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
-    const long e = i * 4;
-    const int m = (int)(e / N), n = (int)(e % N);
-    float4 s = make_float4(0, 0, 0, 0);
-    for (int k = 0; k < splits; ++k) {
-      const float4 v = *reinterpret_cast<const float4*>(slabs + (long)k * slab_stride + e);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    float4* dst = reinterpret_cast<float4*>(C + (long)m * ldc + n);
-    if (accumulate) { const float4 c = *dst; s.x += c.x; s.y += c.y; s.z += c.z; s.w += c.w; }
-    *dst = s;
-  }
-}
-
 // ------------------------------------------------------------------------------------------ plane producers of last resort
 // f32 [rows, cols] -> plane pair (SRC = float), or plane pair in format SRC -> plane pair in format DST (the wgrad GEMM needs
 // the bf16 planes of an activation the forward wrote as fp16 planes).  8 elements per thread: whole 16-B accesses on every
@@ -1018,36 +1000,19 @@ __global__ __launch_bounds__(256) void split_weight_group64_kernel(SimxSplitGrou
 }
 
 // ------------------------------------------------------------------------------------------ host
-struct XpDevice { std::once_flag once; int ncu = 0; bool ok = false; };
-static XpDevice g_xp_dev[SIMX_MAX_DEVICES];
-static const XpDevice* xp_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SIMX_MAX_DEVICES) return nullptr;
-  XpDevice& g = g_xp_dev[dev];
-  std::call_once(g.once, [&g, dev] {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return;
-    g.ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    g.ncu -= g.ncu % 8;
-    bool ok = true;
-#define XP_ATTR(KERNEL, BYTES) \
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)) == hipSuccess
-    XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE, false, false, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE, false, false, true>), P_LDS);
-    XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE, true, false, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE, true, false, true>), P_LDS);
-    XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE, true, true, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE, true, true, true>), P_LDS);
-    XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE_PLANES, false, false, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_NONE_PLANES, false, false, true>), P_LDS);
-    XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_GELU, false, false, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<f16_t, SIMX_EPI_GELU, false, false, true>), P_LDS);
-    XP_ATTR((gemm_nt_xp_kernel<bf16_t, SIMX_EPI_NONE, false, false, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<bf16_t, SIMX_EPI_NONE, false, false, true>), P_LDS);
-    XP_ATTR((gemm_nt_xp_kernel<bf16_t, SIMX_EPI_NONE, true, false, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<bf16_t, SIMX_EPI_NONE, true, false, true>), P_LDS);
-    XP_ATTR((gemm_nt_xp_kernel<bf16_t, SIMX_EPI_DGELU, true, false, false>), P_LDS); XP_ATTR((gemm_nt_xp_kernel<bf16_t, SIMX_EPI_DGELU, true, false, true>), P_LDS);
-    XP_ATTR(gemm_tn_xp_kernel<bf16_t>, TN2_LDS);
-    XP_ATTR(gemm_tn_xq_kernel<bf16_t>, TN2_LDS);
-#undef XP_ATTR
-    g.ok = ok;
-  });
-  return g.ok ? &g : nullptr;
+// this unit's CU count with its dynamic-LDS limits set; 0: the current device cannot be queried / configured
+static int xp_device() {
+  static SimxLdsAttrs st;
+#define XP_LDS(FF, E, HI, DR) simx_lds(gemm_nt_xp_kernel<FF, E, HI, DR, false>, P_LDS), simx_lds(gemm_nt_xp_kernel<FF, E, HI, DR, true>, P_LDS)
+  static const SimxLdsAttr lds[] = {
+      XP_LDS(f16_t, SIMX_EPI_NONE, false, false), XP_LDS(f16_t, SIMX_EPI_NONE, true, false), XP_LDS(f16_t, SIMX_EPI_NONE, true, true),
+      XP_LDS(f16_t, SIMX_EPI_NONE_PLANES, false, false), XP_LDS(f16_t, SIMX_EPI_GELU, false, false),
+      XP_LDS(bf16_t, SIMX_EPI_NONE, false, false), XP_LDS(bf16_t, SIMX_EPI_NONE, true, false), XP_LDS(bf16_t, SIMX_EPI_DGELU, true, false),
+      simx_lds(gemm_tn_xp_kernel<bf16_t>, TN2_LDS), simx_lds(gemm_tn_xq_kernel<bf16_t>, TN2_LDS)};
+#undef XP_LDS
+  const int ncu = simx_device_cus();
+  return ncu > 0 && simx_set_lds_attrs(st, lds, sizeof(lds) / sizeof(lds[0])) ? ncu : 0;
 }
-static bool xal16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 extern "C" int simx_gemm_nt_planes_ok(int M, int N, int K) {
   return M > 0 && N > 0 && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K >= 128 && K <= 8192 ? 1 : 0;
@@ -1069,22 +1034,20 @@ extern "C" int simx_gemm_nt_planes_cs(simx_stream_t stream, int fmt, int epilogu
   SIMX_PROF(SIMX_K_GEMM_NT_XP, s, 2.0 * M * N * K);
   SIMX_REQUIRE(fmt == SIMX_F16 || fmt == SIMX_BF16, SIMX_ERR_BAD_DTYPE, "gemm_nt_planes: fmt %d (the format of the operand planes)", fmt);
   SIMX_REQUIRE(simx_gemm_nt_planes_ok(M, N, K), SIMX_ERR_UNSUPPORTED, "gemm_nt_planes: shape %d x %d x %d (needs M, N %% 256 == 0, K %% 64 == 0, K >= 128)", M, N, K);
-  SIMX_REQUIRE(A && B && lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && a_ps % 8 == 0 && b_ps % 8 == 0 && xal16(A) && xal16(B),
+  SIMX_REQUIRE(A && B && lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && a_ps % 8 == 0 && b_ps % 8 == 0 && simx_al16(A) && simx_al16(B),
                SIMX_ERR_BAD_SHAPE, "gemm_nt_planes: operand planes must be 16-B aligned with leading dimensions %% 8 == 0");
-  SIMX_REQUIRE(!bias || xal16(bias), SIMX_ERR_BAD_SHAPE, "gemm_nt_planes: bias not 16-B aligned");
-  SIMX_REQUIRE(!in || (ldin >= N && ldin % 4 == 0 && xal16(in)), SIMX_ERR_BAD_SHAPE, "gemm_nt_planes: bad `in`");
+  SIMX_REQUIRE(!bias || simx_al16(bias), SIMX_ERR_BAD_SHAPE, "gemm_nt_planes: bias not 16-B aligned");
+  SIMX_REQUIRE(!in || (ldin >= N && ldin % 4 == 0 && simx_al16(in)), SIMX_ERR_BAD_SHAPE, "gemm_nt_planes: bad `in`");
   SIMX_REQUIRE(!dropd || (dropd->p >= 0.f && dropd->p < 1.f), SIMX_ERR_BAD_SHAPE, "gemm_nt_planes: dropout p must be in [0,1)");
-  const bool c_ok = C && ldc >= N && ldc % 4 == 0 && xal16(C);
-  const bool p_ok = Cp && ldcp >= N && ldcp % 8 == 0 && cp_ps % 8 == 0 && xal16(Cp);
-  const XpDevice* gd = xp_device();
-  SIMX_REQUIRE(gd != nullptr, SIMX_ERR_HIP, "gemm_nt_planes: cannot query / configure the current device");
+  const bool c_ok = C && ldc >= N && ldc % 4 == 0 && simx_al16(C);
+  const bool p_ok = Cp && ldcp >= N && ldcp % 8 == 0 && cp_ps % 8 == 0 && simx_al16(Cp);
+  const int ncu_dev = xp_device();
+  SIMX_REQUIRE(ncu_dev > 0, SIMX_ERR_HIP, "gemm_nt_planes: cannot query / configure the current device");
   const int tn = N / 256, nt = (M / 256) * tn;
-  const int ncu_c = simx_compute_cus(gd->ncu);
+  const int ncu_c = simx_compute_cus(ncu_dev);
   const int grid = nt < ncu_c ? nt : ncu_c;
   const DropCtx drop = make_drop(epilogue == SIMX_EPI_NONE ? dropd : nullptr);
-  // SIMX_NT_XP=k3 pins the tripled-K stream (six tile loads per k block; A/B measurements); the ring form needs lda == ldb
-  static const bool k3 = [] { const char* e = getenv("SIMX_NT_XP"); return e && e[0] == 'k'; }();
-  const bool ring = !k3 && lda == ldb;
+  const bool ring = lda == ldb;                  // the ring form needs lda == ldb; else the tripled-K stream (six tile loads per k block)
 #define LXP(FF, E, HI, DR) do { if (ring) hipLaunchKernelGGL((gemm_nt_xp_kernel<FF, E, HI, DR, true>), dim3(grid), dim3(512), P_LDS, s, M, N, K, (const bf16_t*)A, lda, a_ps, \
                                               (const bf16_t*)B, ldb, b_ps, C, ldc, bias, in, ldin, (bf16_t*)Cp, ldcp, cp_ps, tn, nt, drop, colsum, m_valid);    \
                                 else hipLaunchKernelGGL((gemm_nt_xp_kernel<FF, E, HI, DR, false>), dim3(grid), dim3(512), P_LDS, s, M, N, K, (const bf16_t*)A, lda, a_ps, \
@@ -1120,21 +1083,10 @@ extern "C" int simx_gemm_nt_planes_cs(simx_stream_t stream, int fmt, int epilogu
   return SIMX_OK;
 }
 
-static void xp_tn_plan(int M, int N, int K, int* splits, int* kps) {
-  const int tiles = cdiv(M, 256) * cdiv(N, 256);
-  const char* rounds_env = getenv("SIMX_TN_ROUNDS");       // (read per call, as tn_plan)
-  const int round = simx_compute_cus(256);
-  int sp = (rounds_env && rounds_env[0] == '2' ? 2 * round : round) / tiles;      // ONE whole round of the chip (one workgroup per CU), as tn_plan (csrc/gemm.hip): 32768 tokens 1.60 -> 1.48 ms
-  const int max_s = cdiv(K, 512);
-  if (sp > max_s) sp = max_s;
-  if (sp < 1) sp = 1;
-  const int k = cdiv(cdiv(K, sp), 64) * 64;
-  *splits = cdiv(K, k);
-  *kps = k;
-}
+// ONE whole round of the chip (one workgroup per CU), as tn_plan (csrc/gemm.hip): 32768 tokens 1.60 -> 1.48 ms
+static SimxSplitK xp_tn_plan(int M, int N, int K) { return simx_splitk_plan(cdiv(M, 256) * cdiv(N, 256), K, simx_tn_round(), 64); }
 extern "C" size_t simx_gemm_tn_planes_workspace_bytes(int M, int N, int K) {
-  int sp, kps;
-  xp_tn_plan(M, N, K, &sp, &kps);
+  const int sp = xp_tn_plan(M, N, K).splits;
   return sp > 1 ? (size_t)sp * M * N * sizeof(float) : 0;
 }
 extern "C" int simx_gemm_tn_planes(simx_stream_t stream, int M, int N, int K, const void* A, int lda, long a_ps, const void* B, int ldb,
@@ -1143,42 +1095,26 @@ extern "C" int simx_gemm_tn_planes(simx_stream_t stream, int M, int N, int K, co
   SIMX_PROF(SIMX_K_GEMM_TN_XP, s, 2.0 * M * N * K);
   SIMX_REQUIRE(M >= 8 && N >= 8 && K > 0 && A && B && C, SIMX_ERR_BAD_SHAPE, "gemm_tn_planes: bad shape %d %d %d", M, N, K);
   SIMX_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda >= M && ldb >= N && lda % 8 == 0 && ldb % 8 == 0 && a_ps % 8 == 0 && b_ps % 8 == 0 && ldc >= N &&
-                   ldc % 4 == 0 && xal16(A) && xal16(B) && xal16(C),
+                   ldc % 4 == 0 && simx_al16(A) && simx_al16(B) && simx_al16(C),
                SIMX_ERR_BAD_SHAPE, "gemm_tn_planes: operands must be 16-B aligned with dimensions %% 8 == 0");
-  const XpDevice* gd = xp_device();
-  SIMX_REQUIRE(gd != nullptr, SIMX_ERR_HIP, "gemm_tn_planes: cannot query / configure the current device");
-  int sp, kps;
-  xp_tn_plan(M, N, K, &sp, &kps);
+  SIMX_REQUIRE(xp_device() > 0, SIMX_ERR_HIP, "gemm_tn_planes: cannot query / configure the current device");
+  const SimxSplitK plan = xp_tn_plan(M, N, K);
+  const int sp = plan.splits;
   const int t_n = cdiv(N, 256), t_mn = cdiv(M, 256) * t_n;
-  float* dbias_out = dbias;
-  const int nbp = sp * t_n * 4;
-  if (dbias && simx_det()) {
-    dbias = simx_det_ws(s, (size_t)nbp * M * sizeof(float));
-    if (!dbias) return SIMX_ERR_WORKSPACE;
-  }
-  const int dparts = dbias != dbias_out;
-  // SIMX_TN_XP=k3 pins the tripled-K kernel (A/B measurements); default: four-plane stages
-  static const bool k3 = [] { const char* e = getenv("SIMX_TN_XP"); return e && e[0] == 'k'; }();
-  auto kern = (k3 || dbias) ? gemm_tn_xp_kernel<bf16_t> : gemm_tn_xq_kernel<bf16_t>;
-  if (sp == 1) {
-    hipLaunchKernelGGL(kern, dim3(t_mn), dim3(512), TN2_LDS, s, M, N, K, (const bf16_t*)A, lda, a_ps, (const bf16_t*)B, ldb, b_ps,
-                       C, 0L, ldc, t_n, t_mn, kps, accumulate, dbias, dparts);
-    SIMX_CHECK_LAUNCH("gemm_tn_xp");
-    if (dparts) return simx_det_reduce(s, dbias, (long)M, nbp, M, dbias_out, nullptr, nullptr, nullptr);
-    return SIMX_OK;
-  }
+  const SimxDetBias db(s, dbias, sp * t_n * 4, M);
+  if (!db.ok()) return SIMX_ERR_WORKSPACE;
   const size_t need = (size_t)sp * M * N * sizeof(float);
-  SIMX_REQUIRE(ws && ws_bytes >= need && xal16(ws), SIMX_ERR_WORKSPACE, "gemm_tn_planes: workspace %zu < %zu (or not 16-B aligned)", ws_bytes, need);
-  hipLaunchKernelGGL(kern, dim3(t_mn * sp), dim3(512), TN2_LDS, s, M, N, K, (const bf16_t*)A, lda, a_ps, (const bf16_t*)B, ldb, b_ps,
-                     (float*)ws, (long)M * N, N, t_n, t_mn, kps, 0, dbias, dparts);
+  SIMX_REQUIRE(sp == 1 || (ws && ws_bytes >= need && simx_al16(ws)), SIMX_ERR_WORKSPACE, "gemm_tn_planes: workspace %zu < %zu (or not 16-B aligned)",
+               ws_bytes, need);
+  const SimxTnOut o = simx_tn_out(sp, ws, C, M, N, ldc, accumulate);
+  // the fused bias gradient runs on the tripled-K kernel; without it, four-plane stages
+  auto kern = dbias ? gemm_tn_xp_kernel<bf16_t> : gemm_tn_xq_kernel<bf16_t>;
+  hipLaunchKernelGGL(kern, dim3(t_mn * sp), dim3(512), TN2_LDS, s, M, N, K,
+                     (const bf16_t*)A, lda, a_ps, (const bf16_t*)B, ldb, b_ps, o.out, o.slab_stride, o.ld, t_n, t_mn, plan.kps, o.accumulate,
+                     db.rows, db.parts());
   SIMX_CHECK_LAUNCH("gemm_tn_xp");
-  if (dparts) { int rcd = simx_det_reduce(s, dbias, (long)M, nbp, M, dbias_out, nullptr, nullptr, nullptr); if (rcd) return rcd; }
-  const long tot4 = (long)M * N / 4;
-  int rb = (int)((tot4 + 255) / 256);
-  if (rb > 2048) rb = 2048;
-  hipLaunchKernelGGL(xp_slab_reduce_kernel, dim3(rb), dim3(256), 0, s, (const float*)ws, (long)M * N, sp, M, N, C, ldc, accumulate);
-  SIMX_CHECK_LAUNCH("slab_reduce");
-  return SIMX_OK;
+  if (int rc = db.finish(s, nullptr)) return rc;
+  return sp > 1 ? simx_slab_reduce(s, (const float*)ws, sp, M, N, C, ldc, accumulate, nullptr) : SIMX_OK;
 }
 
 // planes of a [rows, cols] tensor.  src_fmt: SIMX_F32 (src = f32 matrix, src_ps ignored) or the format of a source plane pair
@@ -1193,7 +1129,7 @@ extern "C" int simx_planes_from(simx_stream_t stream, int src_fmt, int dst_fmt, 
                                 void* dst, int ldd, long dst_ps) {
   hipStream_t s = (hipStream_t)stream;
   SIMX_PROF(SIMX_K_CAST, s, (double)rows * cols * 8);
-  SIMX_REQUIRE(rows > 0 && cols > 0 && cols % 8 == 0 && src && dst && lds_ >= cols && ldd >= cols && ldd % 8 == 0 && dst_ps % 8 == 0 && xal16(dst) && xal16(src) &&
+  SIMX_REQUIRE(rows > 0 && cols > 0 && cols % 8 == 0 && src && dst && lds_ >= cols && ldd >= cols && ldd % 8 == 0 && dst_ps % 8 == 0 && simx_al16(dst) && simx_al16(src) &&
                    (src_fmt == SIMX_F32 ? lds_ % 4 == 0 : (lds_ % 8 == 0 && src_ps % 8 == 0)),
                SIMX_ERR_BAD_SHAPE, "planes_from: bad shape / alignment");
   SIMX_REQUIRE(dst_fmt == SIMX_F16 || dst_fmt == SIMX_BF16, SIMX_ERR_BAD_DTYPE, "planes_from: dst_fmt %d", dst_fmt);
@@ -1213,7 +1149,7 @@ extern "C" int simx_planes_join(simx_stream_t stream, int src_fmt, int rows, int
   hipStream_t s = (hipStream_t)stream;
   SIMX_PROF(SIMX_K_CAST, s, (double)rows * cols * 8);
   SIMX_REQUIRE(rows > 0 && cols > 0 && cols % 8 == 0 && src && dst && lds_ >= cols && lds_ % 8 == 0 && src_ps % 8 == 0 && ldd >= cols && ldd % 4 == 0 &&
-                   xal16(src) && xal16(dst), SIMX_ERR_BAD_SHAPE, "planes_join: bad shape / alignment");
+                   simx_al16(src) && simx_al16(dst), SIMX_ERR_BAD_SHAPE, "planes_join: bad shape / alignment");
   const long total = (long)rows * (cols / 8);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 8192) blocks = 8192;
@@ -1233,7 +1169,7 @@ int simx_split_weight_group(hipStream_t s, const SimxSplitGroup* g) {
   for (int i = 0; i < gg.n; ++i) {
     const SimxSplitJob& jb = gg.job[i];
     SIMX_REQUIRE(jb.rows > 0 && jb.cols > 0 && jb.w, SIMX_ERR_BAD_SHAPE, "split_weight_group: bad job %d", i);
-    wide = wide && jb.rows % 64 == 0 && jb.cols % 64 == 0 && xal16(jb.w) && xal16(jb.planes_h) && xal16(jb.planesT_b) && xal16(jb.wT);
+    wide = wide && jb.rows % 64 == 0 && jb.cols % 64 == 0 && simx_al16(jb.w) && simx_al16(jb.planes_h) && simx_al16(jb.planesT_b) && simx_al16(jb.wT);
   }
   const int ts = wide ? 64 : 32;
   for (int i = 0; i < gg.n; ++i) {

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 extern "C" int simx_sqnorm_accum(simx_stream_t stream, const float* g, size_t n, float* sqnorm) {
   SIMX_PROF(SIMX_K_ADAMW, stream, 4.0 * n);
   SIMX_REQUIRE(g && sqnorm && n > 0, SIMX_ERR_BAD_SHAPE, "sqnorm_accum: bad arguments");
-  SIMX_REQUIRE((((uintptr_t)g) & 15) == 0, SIMX_ERR_BAD_SHAPE, "sqnorm_accum: g not 16-B aligned");
+  SIMX_REQUIRE(simx_al16(g), SIMX_ERR_BAD_SHAPE, "sqnorm_accum: g not 16-B aligned");
   size_t blocks = (n / 4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
@@ -143,7 +143,7 @@ extern "C" int simx_sqnorm_accum(simx_stream_t stream, const float* g, size_t n,
 extern "C" int simx_sqnorm_accum_det(simx_stream_t stream, const float* g, size_t n, float* sqnorm, float* ws) {
   SIMX_PROF(SIMX_K_ADAMW, stream, 4.0 * n);
   SIMX_REQUIRE(g && sqnorm && ws && n > 0, SIMX_ERR_BAD_SHAPE, "sqnorm_accum_det: bad arguments");
-  SIMX_REQUIRE((((uintptr_t)g) & 15) == 0, SIMX_ERR_BAD_SHAPE, "sqnorm_accum_det: g not 16-B aligned");
+  SIMX_REQUIRE(simx_al16(g), SIMX_ERR_BAD_SHAPE, "sqnorm_accum_det: g not 16-B aligned");
   size_t blocks = (n / 4 + 255) / 256;
   if (blocks > SIMX_SQNORM_WS_FLOATS) blocks = SIMX_SQNORM_WS_FLOATS;
   if (blocks < 1) blocks = 1;
@@ -178,8 +178,7 @@ extern "C" int simx_adamw_step_sc(simx_stream_t stream, float* p, float* g, floa
                                   float grad_scale, int zero_grad, const float* scaler) {
   SIMX_PROF(SIMX_K_ADAMW, stream, 32.0 * n);
   SIMX_REQUIRE(p && g && m && v && n > 0 && step >= 1, SIMX_ERR_BAD_SHAPE, "adamw_step: bad arguments");
-  SIMX_REQUIRE(((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0, SIMX_ERR_BAD_SHAPE,
-               "adamw_step: buffers not 16-B aligned");
+  SIMX_REQUIRE(simx_al16(p) && simx_al16(g) && simx_al16(m) && simx_al16(v), SIMX_ERR_BAD_SHAPE, "adamw_step: buffers not 16-B aligned");
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr * sqrt(bc2) / bc1);
   size_t blocks = (n / 4 + 255) / 256;

@@ -14,8 +14,6 @@
 #include "common.h"
 #include "prof.h"
 
-static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 #define IP_BM 128
 #define IP_BN 128
 #define IP_BK 16
@@ -158,7 +156,7 @@ extern "C" int simx_ip_scores(simx_stream_t stream, int nq, int nc, int H, const
   hipStream_t s = (hipStream_t)stream;
   SIMX_PROF(SIMX_K_TOPK, s, 2.0 * nq * nc * H);
   SIMX_REQUIRE(nq > 0 && nc > 0 && H > 0 && H % 4 == 0 && ld >= nc, SIMX_ERR_BAD_SHAPE, "ip_scores: bad shape nq=%d nc=%d H=%d ld=%ld", nq, nc, H, ld);
-  SIMX_REQUIRE(aligned16(q) && aligned16(c) && aligned16(scores), SIMX_ERR_BAD_SHAPE, "ip_scores: pointers must be 16-byte aligned");
+  SIMX_REQUIRE(simx_al16(q) && simx_al16(c) && simx_al16(scores), SIMX_ERR_BAD_SHAPE, "ip_scores: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(ip_scores_kernel, dim3(cdiv(nc, IP_BN), cdiv(nq, IP_BM)), dim3(256), 0, s, nq, nc, H, q, c, scores, ld);
   SIMX_CHECK_LAUNCH("ip_scores");
   return SIMX_OK;

@@ -689,3 +689,41 @@ def test_compute_cu_budget_changes_the_partition_not_the_result(dev):
     assert torch.equal(outs[0][0], outs[240][0]) and torch.equal(outs[0][1], outs[240][1])
     d = float((outs[0][2] - outs[240][2]).abs().max())
     assert d <= 1e-5 * math.sqrt(M) * float(outs[0][2].abs().max()) / 100 + 1e-2, d
+
+
+# Workspace bytes of the wgrad split plans on a 256-CU chip without a compute-CU budget: {rule: {K: {(M, N): (tn, planes)}}}.
+# SIMX_TN_ROUNDS=2 is the rule of rounds 2-4.  The values are those of the three per-unit planners the shared one replaced.
+WGRAD_PLAN_BYTES = {
+    None: {
+        262144: {(2304, 768): (63700992, 63700992), (768, 768): (66060288, 66060288), (3072, 768): (66060288, 66060288), (768, 3072): (66060288, 66060288)},
+        32768: {(2304, 768): (63700992, 63700992), (768, 768): (66060288, 63700992), (3072, 768): (66060288, 66060288), (768, 3072): (66060288, 66060288)},
+        4096: {(2304, 768): (56623104, 56623104), (768, 768): (33030144, 18874368), (3072, 768): (66060288, 66060288), (768, 3072): (66060288, 66060288)},
+    },
+    "2": {
+        262144: {(2304, 768): (127401984, 127401984), (768, 768): (132120576, 132120576), (3072, 768): (132120576, 132120576), (768, 3072): (132120576, 132120576)},
+        32768: {(2304, 768): (127401984, 127401984), (768, 768): (122683392, 122683392), (3072, 768): (132120576, 132120576), (768, 3072): (132120576, 132120576)},
+        4096: {(2304, 768): (56623104, 56623104), (768, 768): (33030144, 18874368), (3072, 768): (75497472, 75497472), (768, 3072): (75497472, 75497472)},
+    },
+}
+
+
+def test_wgrad_split_plans_are_pinned(dev):
+    """The split-K plans of the wgrad GEMMs (splits, tokens per split) decide workspace sizes and summation order; no result test
+    notices when they drift.  Pinned through the two workspace queries for the four wgrad shapes of BERT-base under both rules."""
+    import os
+    if torch.cuda.get_device_properties(dev).multi_processor_count != 256 or int(os.environ.get("SIMX_COMPUTE_CUS") or 0) > 0:
+        pytest.skip("the pinned plans are those of a 256-CU device without a compute-CU budget")
+    lib = L().load()
+    old = os.environ.pop("SIMX_TN_ROUNDS", None)
+    got = {}
+    try:
+        for rule, table in WGRAD_PLAN_BYTES.items():
+            if rule is not None:
+                os.environ["SIMX_TN_ROUNDS"] = rule
+            got[rule] = {K: {(M, N): (int(lib.simx_gemm_tn_workspace_bytes(M, N, K)), int(lib.simx_gemm_tn_planes_workspace_bytes(M, N, K)))
+                             for (M, N) in shapes} for K, shapes in table.items()}
+    finally:
+        os.environ.pop("SIMX_TN_ROUNDS", None)
+        if old is not None:
+            os.environ["SIMX_TN_ROUNDS"] = old
+    assert got == WGRAD_PLAN_BYTES
