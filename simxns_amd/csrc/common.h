@@ -17,9 +17,9 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 #define WAVE 64
 #define SIMX_MAX_DEVICES 64   // per-device launch state tables (one process per GPU is the deployment; this is the bound)
 
-// ---- error plumbing (api.cpp) ---------------------------------------------------------
+// ---- error plumbing (runtime.hip) -----------------------------------------------------
 void simx_set_error(const char* fmt, ...);
-int simx_compute_cus(int device_cus);      // CUs the persistent kernels may fill (simx_set_compute_cus / SIMX_COMPUTE_CUS; encoder.hip)
+int simx_compute_cus(int device_cus);      // CUs the persistent kernels may fill (simx_set_compute_cus / SIMX_COMPUTE_CUS; runtime.hip)
 // SIMX_DETERMINISTIC=1 (det.hip): ordered reductions instead of f32 atomics
 bool simx_det();
 float* simx_det_ws(hipStream_t st, size_t bytes);                       // per-stream scratch, NULL (+ error text) on failure

@@ -1,52 +1,15 @@
-// Native runtime: the whole-encoder forward / backward driver and library plumbing.
+// The whole-encoder forward / backward driver.
 // Sequences the gfx950 kernels for HFBertEncoder.forward (SimANS/model/models.py:77-82 -> HF
 // BertModel.forward, spec LEAD/modeling_bert.py:916-1038) and its backward on the packed token
 // layout.  No allocation, no synchronisation: every buffer is carved from caller-provided memory.
 //
-// HBM layout (all 256-B aligned):
+// HBM layout (all 256-B aligned; each buffer is described once, by its walk_* function below):
 //   params / grads : one f32 buffer each, canonical order (simx_bert_param_offset)
 //   wcache         : per layer  Wqkv, Wqkv^T, Wo, Wo^T, W1, W1^T, W2, W2^T   (bf16 / fp16; f32 mode keeps only
-//                    the transposes, in f32) -- rebuilt once per optimiser step
-//   act            : x0 | per layer { qkv[T,3H] ctx[T,H] lse[heads,T](f32) z1[T,H] x1[T,H] u[T,F] h[T,F]
-//                    z2[T,H] xout[T,H] }   -- everything backward needs is KEPT (288 GB HBM: no recompute)
-//   bwd scratch    : bufA[T,H] bufB[T,H] du[T,F] dqkv[T,3H] | split-K slabs of the wgrad GEMMs
-#include <stdarg.h>
-#include <string.h>
+//                    the transposes, in f32) -- rebuilt once per optimiser step                       (walk_wlayer)
+//   act            : x0 | layer slots | the [CLS]-only last layer's compact tensors                   (walk_act)
+//   bwd scratch    : bufA[T,H] bufB[T,H] bufC[T,H] du[T,F] dqkv[T,3H] | split-K slabs of the wgrad GEMMs | ...   (walk_scratch)
 #include "common.h"
-
-// ------------------------------------------------------------------------------------------ errors
-static thread_local char g_err[512] = "";
-void simx_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* simx_last_error(void) { return g_err; }
-extern "C" int simx_version(void) { return 100; }
-
-// ---- compute-CU budget of the persistent kernels (include/simx.h simx_set_compute_cus) --------------------------------
-// The persistent GEMMs launch one workgroup per CU (each needs a whole CU's 160 KB of LDS) and give every workgroup a STATIC share
-// of the tile list; the wgrad plans fill exactly one round of the chip.  When another kernel holds k CUs for the whole launch -- an
-// RCCL ring during the overlapped backward -- k of those workgroups only start when a resident one has finished its WHOLE share:
-// the launch takes up to twice as long (tools/cu_steal_bench, profiles/r06_cu_steal.json).  With a budget of ncu - k the launches
-// fit beside the communication kernel and lose k / ncu instead.  0 = every CU (default; SIMX_COMPUTE_CUS until the first explicit set).
-static std::atomic<int> g_compute_cus{-1};      // -1: no explicit set yet, the environment's value holds
-extern "C" int simx_set_compute_cus(int n) {
-  SIMX_REQUIRE(n >= 0, SIMX_ERR_BAD_SHAPE, "simx_set_compute_cus: %d", n);
-  g_compute_cus.store(n, std::memory_order_relaxed);
-  return SIMX_OK;
-}
-int simx_compute_cus(int device_cus) {
-  static const int env_cus = [] { const char* e = getenv("SIMX_COMPUTE_CUS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
-  const int set = g_compute_cus.load(std::memory_order_relaxed);
-  const int budget = set < 0 ? env_cus : set;
-  int n = budget > 0 && budget < device_cus ? budget : device_cus;
-  n -= n % 8;                                   // whole XCD rows: xcd_remap assumes block b -> XCD b % 8
-  return n < 8 ? 8 : n;
-}
-
-extern "C" int simx_transpose_cast(simx_stream_t stream, int out_dtype, const float* w, int rows, int cols, void* out, void* outT);
 
 // ------------------------------------------------------------------------------------------ layouts
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -116,49 +79,55 @@ static bool pl_layout(const simx_bert_cfg* c, size_t Tp) {
 }
 static bool pl_run(const simx_bert_cfg* c, size_t Tp, int max_len) { return pl_layout(c, Tp) && simx_mha_planes_ok(c->hidden / c->heads, max_len); }
 
+// Bump carver.  Every caller-provided buffer is described ONCE, by the walk_* function that carves it with one of these and
+// fills a struct of pointers.  A walk from a NULL base yields no pointers and leaves the buffer's size in `off`: the
+// simx_bert_*_bytes entry points and the drivers run the same walk, so a size and a pointer chain cannot drift apart.
+struct Carver {
+  char* base;
+  size_t off;
+  char* at(size_t o) const { return base ? base + o : nullptr; }
+  char* take(size_t bytes) { char* p = at(off); off += al(bytes); return p; }
+  // the element walked since offset `first` is the first of n equal ones: skips the others, returns the stride
+  size_t repeat(size_t first, size_t n) { const size_t stride = off - first; off = first + n * stride; return stride; }
+};
+
 // wqkvP .. w2P: fp16 plane pairs of W [out, in] (forward operand); wqkvTP .. w2TP: bf16 plane pairs of W^T [in, out] (dgrad)
 struct WLayer { const char *wqkv, *wqkvT, *wo, *woT, *w1, *w1T, *w2, *w2T, *wqkvP, *woP, *w1P, *w2P, *wqkvTP, *woTP, *w1TP, *w2TP; };
-static size_t wcache_layer_bytes(const simx_bert_cfg* c) {
+static WLayer walk_wlayer(const simx_bert_cfg* c, Carver& k) {
   const size_t H = c->hidden, F = c->inter, e = esz(c->dtype);
-  const size_t one = al(3 * H * H * e) + al(H * H * e) + 2 * al(F * H * e);
-  if (pl_weights(c)) return 3 * one;              // f32 transposes | fp16 planes of W | bf16 planes of W^T (4 B per element each)
-  return c->dtype == SIMX_F32 ? one : 2 * one;
+  const size_t qkv = 3 * H * H * e, o = H * H * e, f = F * H * e;
+  WLayer w = {};
+  if (c->dtype == SIMX_F32) {                     // W itself is read from params (wlayer): the f32 transposes ...
+    w.wqkvT = k.take(qkv); w.woT = k.take(o); w.w1T = k.take(f); w.w2T = k.take(f);
+    if (pl_weights(c)) {                          // ... | fp16 planes of W | bf16 planes of W^T (4 B per element each)
+      w.wqkvP = k.take(qkv); w.woP = k.take(o); w.w1P = k.take(f); w.w2P = k.take(f);
+      w.wqkvTP = k.take(qkv); w.woTP = k.take(o); w.w1TP = k.take(f); w.w2TP = k.take(f);
+    }
+  } else {
+    w.wqkv = k.take(qkv); w.wqkvT = k.take(qkv);
+    w.wo = k.take(o); w.woT = k.take(o);
+    w.w1 = k.take(f); w.w1T = k.take(f);
+    w.w2 = k.take(f); w.w2T = k.take(f);
+  }
+  return w;
 }
 extern "C" size_t simx_bert_wcache_bytes(const simx_bert_cfg* c) {
-  return cfg_ok(c) ? (size_t)c->layers * wcache_layer_bytes(c) : 0;
+  if (!cfg_ok(c)) return 0;
+  Carver k{nullptr, 0};
+  walk_wlayer(c, k);
+  k.repeat(0, (size_t)c->layers);
+  return k.off;
 }
 static WLayer wlayer(const simx_bert_cfg* c, const float* params, const void* wcache, int l) {
-  const size_t H = c->hidden, F = c->inter, e = esz(c->dtype);
-  const char* b = (const char*)wcache + (size_t)l * wcache_layer_bytes(c);
-  WLayer w = {};
+  Carver k{nullptr, 0};
+  walk_wlayer(c, k);
+  k = Carver{(char*)const_cast<void*>(wcache), (size_t)l * k.off};
+  WLayer w = walk_wlayer(c, k);
   if (c->dtype == SIMX_F32) {
     w.wqkv = (const char*)(params + simx_bert_param_offset(c, l, SIMX_P_WQKV));
     w.wo = (const char*)(params + simx_bert_param_offset(c, l, SIMX_P_WO));
     w.w1 = (const char*)(params + simx_bert_param_offset(c, l, SIMX_P_W1));
     w.w2 = (const char*)(params + simx_bert_param_offset(c, l, SIMX_P_W2));
-    w.wqkvT = b; b += al(3 * H * H * e);
-    w.woT = b; b += al(H * H * e);
-    w.w1T = b; b += al(F * H * e);
-    w.w2T = b; b += al(F * H * e);
-    if (pl_weights(c)) {
-      w.wqkvP = b; b += al(3 * H * H * e);
-      w.woP = b; b += al(H * H * e);
-      w.w1P = b; b += al(F * H * e);
-      w.w2P = b; b += al(F * H * e);
-      w.wqkvTP = b; b += al(3 * H * H * e);
-      w.woTP = b; b += al(H * H * e);
-      w.w1TP = b; b += al(F * H * e);
-      w.w2TP = b;
-    }
-  } else {
-    w.wqkv = b; b += al(3 * H * H * e);
-    w.wqkvT = b; b += al(3 * H * H * e);
-    w.wo = b; b += al(H * H * e);
-    w.woT = b; b += al(H * H * e);
-    w.w1 = b; b += al(F * H * e);
-    w.w1T = b; b += al(F * H * e);
-    w.w2 = b; b += al(F * H * e);
-    w.w2T = b;
   }
   return w;
 }
@@ -172,96 +141,112 @@ static inline int rows_cap(int T) { return (T + 255) & ~255; }
 // per element (x1l / xoutl, NULL otherwise); z1 / z2 then hold the dense outputs without the residual, which the LayerNorm
 // kernels add
 static inline bool stream_lo(const simx_bert_cfg* c) { return c->stream_lo != 0 && simx_is16(c->dtype); }
+// a [Tp,H] tensor of the residual stream: the values, followed by the corrections (ONE BYTE per element: common.h lo8) when
+// stream_lo, or by the fp16 plane pair of the f32 values with pl_layout (the two never coincide: 16-bit vs f32 towers)
+struct XS { char *hi, *lo, *planes; };
+static XS walk_xs(const simx_bert_cfg* c, Carver& k, size_t Tp) {
+  XS x;
+  x.hi = k.take(Tp * c->hidden * esz(c->dtype));
+  x.lo = stream_lo(c) ? k.take(Tp * c->hidden) : nullptr;
+  x.planes = pl_layout(c, Tp) ? k.take(Tp * c->hidden * 4) : nullptr;
+  return x;
+}
 // x1p / xoutp (operand planes, pl_layout): the fp16 plane pairs of x1 / xout beside their f32 forms; in a layer that RUNS on planes
 // the ctx and h slots hold plane pairs instead of f32 (same bytes: two 16-bit planes)
 struct ALayer { char *qkv, *ctx, *z1, *x1, *u, *h, *z2, *xout, *x1l, *xoutl, *x1p, *xoutp; float* lse; };
-static size_t act_layer_bytes(const simx_bert_cfg* c, size_t T) {
+static ALayer walk_alayer(const simx_bert_cfg* c, Carver& k, size_t T) {
   const size_t H = c->hidden, F = c->inter, e = esz(c->dtype);
-  return al(T * 3 * H * e) + 5 * al(T * H * e) + (stream_lo(c) ? 2 * al(T * H) : 0) + (pl_layout(c, T) ? 2 * al(T * H * 4) : 0) + 2 * al(T * F * e) +
-         al((size_t)c->heads * T * 4);
+  ALayer a;
+  a.qkv = k.take(T * 3 * H * e);
+  a.ctx = k.take(T * H * e);
+  a.z1 = k.take(T * H * e);
+  a.x1 = k.take(T * H * e);
+  a.z2 = k.take(T * H * e);
+  a.xout = k.take(T * H * e);
+  a.x1l = a.xoutl = a.x1p = a.xoutp = nullptr;
+  if (stream_lo(c)) { a.x1l = k.take(T * H); a.xoutl = k.take(T * H); }
+  if (pl_layout(c, T)) { a.x1p = k.take(T * H * 4); a.xoutp = k.take(T * H * 4); }
+  a.u = k.take(T * F * e);                     // gelu'(u) of the FFN pre-activation (SIMX_EPI_GELU writes it; only DGELU reads it)
+  a.h = k.take(T * F * e);
+  a.lse = (float*)k.take((size_t)c->heads * T * 4);
+  return a;
 }
-// a [Tp,H] tensor of the residual stream: the 16-bit values, followed by the corrections (ONE BYTE per element: common.h
-// lo8) when stream_lo
-static size_t xs_bytes(const simx_bert_cfg* c, size_t Tp) {
-  return al(Tp * c->hidden * esz(c->dtype)) + (stream_lo(c) ? al(Tp * c->hidden) : 0) + (pl_layout(c, Tp) ? al(Tp * c->hidden * 4) : 0);
+// The [CLS]-only last layer's compact [n,H] tensors: q and the attention context of the [CLS] rows (kept for backward), a
+// temporary, and -- stream_lo -- the gathered residual rows of the layer input with their correction bytes (kept for backward)
+struct ClsExtra { char *qc, *ctxc, *ytmp, *xg, *xgl; };
+static ClsExtra walk_cls_extra(const simx_bert_cfg* c, Carver& k, size_t n) {
+  const size_t b = n * c->hidden * esz(c->dtype);
+  ClsExtra x;
+  x.qc = k.take(b);
+  x.ctxc = k.take(b);
+  x.ytmp = k.take(b);
+  x.xg = k.take(b);
+  x.xgl = k.take(b);
+  return x;
 }
-static const char* xs_lo(const simx_bert_cfg* c, const char* hi, size_t Tp) { return stream_lo(c) ? hi + al(Tp * c->hidden * esz(c->dtype)) : nullptr; }
-// the plane pair that follows an f32 [Tp,H] tensor of the residual stream (NULL without pl_layout)
-static const char* xs_pl(const simx_bert_cfg* c, const char* x, size_t Tp) { return pl_layout(c, Tp) ? x + al(Tp * c->hidden * 4) : nullptr; }
 // Activation memory, three modes:
 //   save = 0                      : x0 | 2 layer slots used as a ring                                  (inference)
 //   save = 1, grad_checkpoint = 0 : x0 | L layer slots -- everything backward needs is kept            (default)
 //   save = 1, grad_checkpoint = 1 : x0 | L layer OUTPUTS [Tp,H] | 2 layer slots (ring) -- only every layer's input is kept
 //                                   (torch.utils.checkpoint per BertLayer, SimANS/model/models.py:73-74); backward re-runs
 //                                   a layer's forward into ring slot 0 (same stateless dropout masks) before its backward
-// followed by three [nseq,H] tensors of the [CLS]-only last layer (q, attention context, a temporary).
-static inline bool ckpt_mode(const simx_bert_cfg* c, int save) { return save && c->grad_checkpoint != 0; }
-static size_t act_slots_bytes(const simx_bert_cfg* c, size_t Tp, int save) {
-  if (ckpt_mode(c, save)) return (size_t)c->layers * xs_bytes(c, Tp) + 2 * act_layer_bytes(c, Tp);
-  return (size_t)(save ? c->layers : 2) * act_layer_bytes(c, Tp);
+// followed by the [CLS]-only last layer's compact tensors.
+struct Act {
+  char* base;
+  size_t Tp;
+  bool ckpt, ring;              // ring: two slots, layer l in slot l & 1
+  XS x0;
+  size_t kept, kept_stride;     // checkpoint mode: the layer outputs (offset of the first, stride)
+  size_t slots, slot_stride;
+  ClsExtra extra;
+  size_t bytes;
+};
+static Act walk_act(const simx_bert_cfg* c, void* act, int T, int nseq, int save) {
+  Act A = {};
+  A.base = (char*)act;
+  A.Tp = (size_t)rows_cap(T);
+  A.ckpt = save && c->grad_checkpoint != 0;
+  A.ring = !save || A.ckpt;
+  Carver k{A.base, 0};
+  A.x0 = walk_xs(c, k, A.Tp);
+  if (A.ckpt) {
+    A.kept = k.off;
+    walk_xs(c, k, A.Tp);
+    A.kept_stride = k.repeat(A.kept, (size_t)c->layers);
+  }
+  A.slots = k.off;
+  walk_alayer(c, k, A.Tp);
+  A.slot_stride = k.repeat(A.slots, A.ring ? 2 : (size_t)c->layers);
+  A.extra = walk_cls_extra(c, k, nseq > 0 ? (size_t)nseq : A.Tp);
+  A.bytes = k.off;
+  return A;
 }
 extern "C" size_t simx_bert_act_bytes(const simx_bert_cfg* c, int T, int nseq, int save_for_bwd) {
-  if (!cfg_ok(c) || T <= 0) return 0;
-  const size_t Tp = (size_t)rows_cap(T);
-  const size_t x0 = xs_bytes(c, Tp);
-  const size_t n = nseq > 0 ? (size_t)nseq : Tp;
-  // (+ the [CLS]-only last layer's compact tensors: q, attention context, a temporary, and -- stream_lo -- the gathered
-  // residual rows with their correction bytes)
-  return x0 + act_slots_bytes(c, Tp, save_for_bwd) + 5 * al(n * c->hidden * esz(c->dtype));
+  return cfg_ok(c) && T > 0 ? walk_act(c, nullptr, T, nseq, save_for_bwd).bytes : 0;
 }
-static char* act_extra(const simx_bert_cfg* c, void* act, size_t Tp, int save) {
-  return (char*)act + xs_bytes(c, Tp) + act_slots_bytes(c, Tp, save);
+static ALayer act_slot(const simx_bert_cfg* c, const Act& A, int i) {
+  Carver k{A.base, A.slots + (size_t)i * A.slot_stride};
+  return walk_alayer(c, k, A.Tp);
 }
-static char* act_x0(void* act) { return (char*)act; }
-static ALayer carve_layer(const simx_bert_cfg* c, char* b, size_t T) {
-  const size_t H = c->hidden, F = c->inter, e = esz(c->dtype);
-  ALayer a;
-  a.qkv = b; b += al(T * 3 * H * e);
-  a.ctx = b; b += al(T * H * e);
-  a.z1 = b; b += al(T * H * e);
-  a.x1 = b; b += al(T * H * e);
-  a.z2 = b; b += al(T * H * e);
-  a.xout = b; b += al(T * H * e);
-  a.x1l = a.xoutl = a.x1p = a.xoutp = nullptr;
-  if (stream_lo(c)) { a.x1l = b; b += al(T * H); a.xoutl = b; b += al(T * H); }
-  if (pl_layout(c, T)) { a.x1p = b; b += al(T * H * 4); a.xoutp = b; b += al(T * H * 4); }
-  a.u = b; b += al(T * F * e);                 // gelu'(u) of the FFN pre-activation (SIMX_EPI_GELU writes it; only DGELU reads it)
-  a.h = b; b += al(T * F * e);
-  a.lse = (float*)b;
+// the slot layer l's FORWARD writes (checkpoint mode: ring slot l & 1, its output redirected to the kept array)
+static ALayer alayer(const simx_bert_cfg* c, const Act& A, int l) {
+  ALayer a = act_slot(c, A, A.ring ? l & 1 : l);
+  if (A.ckpt) {
+    Carver k{A.base, A.kept + (size_t)l * A.kept_stride};
+    const XS out = walk_xs(c, k, A.Tp);
+    a.xout = out.hi;
+    a.xoutl = out.lo;
+    a.xoutp = out.planes;
+  }
   return a;
 }
-// the slot layer l's FORWARD writes (checkpoint mode: ring slot l&1, its output redirected to the kept array)
-static ALayer alayer(const simx_bert_cfg* c, void* act, size_t T, int l, int save) {
-  const size_t xb = xs_bytes(c, T);
-  char* base = (char*)act + xb;
-  if (ckpt_mode(c, save)) {
-    ALayer a = carve_layer(c, base + (size_t)c->layers * xb + (size_t)(l & 1) * act_layer_bytes(c, T), T);
-    a.xout = base + (size_t)l * xb;
-    a.xoutl = const_cast<char*>(xs_lo(c, a.xout, T));
-    a.xoutp = const_cast<char*>(xs_pl(c, a.xout, T));
-    return a;
-  }
-  return carve_layer(c, base + (size_t)(save ? l : (l & 1)) * act_layer_bytes(c, T), T);
-}
-// checkpoint mode, backward: the slot layer l is RE-COMPUTED into (ring slot 0, its own xout)
-static ALayer alayer_recompute(const simx_bert_cfg* c, void* act, size_t T) {
-  const size_t xb = xs_bytes(c, T);
-  return carve_layer(c, (char*)act + xb + (size_t)c->layers * xb, T);
-}
+// the slot layer l's BACKWARD reads (checkpoint mode: the layer is RE-COMPUTED into ring slot 0, its own xout)
+static ALayer alayer_bwd(const simx_bert_cfg* c, const Act& A, int l) { return A.ckpt ? act_slot(c, A, 0) : alayer(c, A, l); }
 // input of layer l (= output of layer l-1, or the embedding output)
-static const char* layer_input(const simx_bert_cfg* c, const void* act, size_t T, int l) {
-  if (l == 0) return act_x0(const_cast<void*>(act));
-  return alayer(c, const_cast<void*>(act), T, l - 1, 1).xout;
-}
-// its fp16 plane pair (NULL without pl_layout)
-static const char* layer_input_pl(const simx_bert_cfg* c, const void* act, size_t T, int l) {
-  if (l == 0) return xs_pl(c, act_x0(const_cast<void*>(act)), T);
-  return alayer(c, const_cast<void*>(act), T, l - 1, 1).xoutp;
-}
-// its stream correction (NULL without stream_lo)
-static const char* layer_input_lo(const simx_bert_cfg* c, const void* act, size_t T, int l) {
-  if (l == 0) return xs_lo(c, act_x0(const_cast<void*>(act)), T);
-  return alayer(c, const_cast<void*>(act), T, l - 1, 1).xoutl;
+static XS layer_input(const simx_bert_cfg* c, const Act& A, int l) {
+  if (l == 0) return A.x0;
+  const ALayer p = alayer(c, A, l - 1);
+  return XS{p.xout, p.xoutl, p.xoutp};
 }
 
 static size_t tn_ws_max(const simx_bert_cfg* c, int T) {
@@ -275,15 +260,34 @@ static size_t tn_ws_max(const simx_bert_cfg* c, int T) {
     v = simx_gemm_tn_planes_workspace_bytes(F, H, T); if (v > m) m = v;
     v = simx_gemm_tn_planes_workspace_bytes(H, F, T); if (v > m) m = v;
   }
-  return al(m);
+  return m;
+}
+// Backward scratch.  bufB carries the gradient w.r.t. the current layer's OUTPUT from one layer to the next -- and from one
+// simx_bert_bwd_range call to the next (the caller keeps `scratch` alive and untouched between the parts); bufA is the gradient
+// of the residual branch; bufC the dropout-masked copy of dz (only with hidden dropout; always, as bf16 planes, in a plane tower)
+struct Scratch { char *bufA, *bufB, *bufC, *du, *dqkv, *tnws, *e0, *e1, *e2, *xconv; size_t tnws_bytes, bytes; };
+static Scratch walk_scratch(const simx_bert_cfg* c, void* scratch, int T, int nseq) {
+  const size_t H = c->hidden, F = c->inter, e = esz(c->dtype);
+  const size_t Tp = (size_t)rows_cap(T), n = nseq > 0 ? (size_t)nseq : Tp;
+  Carver k{(char*)scratch, 0};
+  Scratch s;
+  s.bufA = k.take(Tp * H * e);
+  s.bufB = k.take(Tp * H * e);
+  s.bufC = k.take(Tp * H * e);
+  s.du = k.take(Tp * F * e);
+  s.dqkv = k.take(Tp * 3 * H * e);
+  s.tnws_bytes = al(tn_ws_max(c, T));           // split-K slabs of the wgrad GEMMs
+  s.tnws = k.take(s.tnws_bytes);
+  s.e0 = k.take(n * H * e);                     // three [nseq,H] temporaries of the [CLS]-only last layer
+  s.e1 = k.take(n * H * e);
+  s.e2 = k.take(n * H * e);
+  // operand planes: the bf16 plane pair of the activation a wgrad GEMM contracts against, converted per use
+  s.xconv = pl_layout(c, Tp) ? k.take(Tp * F * 4) : nullptr;
+  s.bytes = k.off;
+  return s;
 }
 extern "C" size_t simx_bert_bwd_scratch_bytes(const simx_bert_cfg* c, int T, int nseq) {
-  if (!cfg_ok(c) || T <= 0) return 0;
-  const size_t H = c->hidden, F = c->inter, e = esz(c->dtype);
-  const size_t Tp = (size_t)rows_cap(T);
-  const size_t n = nseq > 0 ? (size_t)nseq : Tp;
-  // (+ operand planes: the bf16 plane pair of the activation a wgrad GEMM contracts against, converted per use)
-  return 3 * al(Tp * H * e) + al(Tp * F * e) + al(Tp * 3 * H * e) + tn_ws_max(c, T) + 3 * al(n * H * e) + (pl_layout(c, Tp) ? al(Tp * F * 4) : 0);
+  return cfg_ok(c) && T > 0 ? walk_scratch(c, nullptr, T, nseq).bytes : 0;
 }
 
 // ------------------------------------------------------------------------------------------ driver
@@ -364,114 +368,154 @@ static int hm_rows_for(const simx_bert_cfg* c, int T, int Tp, int max_len) {
   return simx_gemm_hm_ok(Tp, c->hidden, T) ? Tp : 0;
 }
 
-// One encoder layer's forward: x_in [Tp,H] -> a.xout (a = the slot it writes).  `keep`: backward will read this slot
-// (the pre-activation u is stored); the [CLS]-only form of the last layer writes [nseq, .] tensors into the slot's usual
-// buffers and q / attention context of the [CLS] rows into `extra` (kept for backward).
-static int layer_fwd(hipStream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache, int l, const char* x,
-                     const char* xl, const char* xp, const ALayer& a, char* extra, const int32_t* cu, int nseq, int T, int Tp, int max_len, int keep,
-                     bool cls_form, float* cls_out) {
-  const int H = c->hidden, F = c->inter, dt = c->dtype, d = H / c->heads;
-  auto off = [&](int ll, int w) { return params + simx_bert_param_offset(c, ll, w); };
-  const WLayer w = wlayer(c, params, wcache, l);
+// Hidden dropout is live <=> the LayerNorm backward writes the dropout-masked copy of dz (ln_bwd_kernel stores it under the
+// REALISED threshold: make_drop runs 0 < p < 1/512 as no dropout).  The one predicate behind both the kernel's dz_masked
+// argument and the buffer the dgrad / wgrad GEMMs read.
+static bool hidden_drop_live(const simx_bert_cfg* c) {
+  const simx_dropout d = drop_of(c, 0, 1);
+  return make_drop(&d).thr != 0;
+}
+
+// What one forward / backward call hands to every layer
+struct Ctx {
+  hipStream_t stream;
+  const simx_bert_cfg* c;
+  const float* params;
+  float* grads;
+  const void* wcache;
+  const int32_t* cu;
+  int nseq, T, Tp, max_len;
+  int hm;               // rows of the head-major q / k / v tensor (hm_rows_for), 0 = token-major
+  const float* gs;      // fp16 engine: activation gradients travel multiplied by the loss scale S (gs = {S, 1/S} on the device); the
+                        // kernels that accumulate into `grads` multiply by 1/S, so `grads` holds true gradients (simx.h "gradient scale")
+  int gdt;              // fp32 engine: the dense GEMMs run on the 16-bit matrix cores from fp16 hi + lo splits of their f32 operands unless
+                        // the config asks for exact f32 products (simx.h SIMX_F32_SPLIT_H; every other kernel of the layer is plain f32)
+  int gdb;              // ... and the dgrad / wgrad GEMMs from bf16 splits (gradients need f32's exponent range; simx.h SIMX_F32_SPLIT_B)
+  Act A;
+  const float* p(int l, int w) const { return params + simx_bert_param_offset(c, l, w); }
+  float* g(int l, int w) const { return grads + simx_bert_param_offset(c, l, w); }
+};
+static Ctx make_ctx(simx_stream_t stream, const simx_bert_cfg* c, const float* params, float* grads, const void* wcache, const int32_t* cu,
+                    int nseq, int T, int max_len, void* act, int save) {
+  Ctx cx;
+  cx.stream = (hipStream_t)stream; cx.c = c; cx.params = params; cx.grads = grads; cx.wcache = wcache; cx.cu = cu;
+  cx.nseq = nseq; cx.T = T; cx.Tp = rows_cap(T); cx.max_len = max_len;
+  cx.hm = hm_rows_for(c, T, cx.Tp, max_len);
+  cx.gs = c->dtype == SIMX_F16 ? c->grad_scale : nullptr;
+  const bool split = c->dtype == SIMX_F32 && c->f32_gemm == 0;
+  cx.gdt = split ? SIMX_F32_SPLIT_H : c->dtype;
+  cx.gdb = split ? SIMX_F32_SPLIT_B : c->dtype;
+  cx.A = walk_act(c, act, T, nseq, save);
+  return cx;
+}
+
+// ---- forward: one encoder layer, x [Tp,H] -> a.xout (a = the slot it writes), in one of three forms.  `keep`: backward will read
+// this slot (the pre-activation u is stored).
+
+// Last layer, [CLS] rows only: row s of every [nseq, .] buffer below is the sequence's token 0 (row cu[s] of the
+// full tensors).  Only K and V are projected for every token; Q, the attention core and everything after it run
+// for the one query per sequence that is read.  Same arithmetic as the full path -- dropout masks stay keyed by
+// the ORIGINAL row index.  z1, x1, u, h, z2, xout of this layer hold [nseq, .] tensors in their usual slots; q and the
+// attention context of the [CLS] rows go to the compact tensors behind the slots.
+static int layer_fwd_cls(const Ctx& cx, int l, const XS& x, const ALayer& a, float* cls_out) {
+  const simx_bert_cfg* c = cx.c;
+  const int H = c->hidden, F = c->inter, dt = c->dtype, d = H / c->heads, nseq = cx.nseq, gdt = cx.gdt;
+  const size_t e = esz(dt);
+  const WLayer w = wlayer(c, cx.params, cx.wcache, l);
   const simx_dropout d1 = drop_of(c, l, 1), d2 = drop_of(c, l, 2), d3 = drop_of(c, l, 3);
-  const int hm = hm_rows_for(c, T, Tp, max_len);
-  // fp32 engine: the dense GEMMs run on the 16-bit matrix cores from fp16 hi + lo splits of their f32 operands unless the
-  // config asks for exact f32 products (simx.h SIMX_F32_SPLIT_H; every other kernel of the layer is plain f32)
-  const int gdt = (dt == SIMX_F32 && c->f32_gemm == 0) ? SIMX_F32_SPLIT_H : dt;
-  if (cls_form) {
-    // Last layer, [CLS] rows only: row s of every [nseq, .] buffer below is the sequence's token 0 (row cu[s] of the
-    // full tensors).  Only K and V are projected for every token; Q, the attention core and everything after it run
-    // for the one query per sequence that is read.  Same arithmetic as the full path -- dropout masks stay keyed by
-    // the ORIGINAL row index.  z1, x1, u, h, z2, xout of this layer hold [nseq, .] tensors in their usual slots.
-    const size_t e = esz(dt);
-    char* qc = extra;                                            // kept for backward
-    char* ctxc = qc + al((size_t)nseq * H * e);                  // kept for backward
-    char* ytmp = ctxc + al((size_t)nseq * H * e);
-    if (hm)      // K, V planes [heads, 3*heads) of the head-major tensor
-      RUN(simx_gemm_nt_hm(stream, dt, Tp, 2 * H, H, x, H, w.wqkv + (size_t)H * H * e, H, a.qkv + (size_t)c->heads * hm * 64 * e, 64,
-                          off(l, SIMX_P_BQKV) + H, nullptr, 0, nullptr, 0, hm));
-    else
-      RUN(simx_gemm_nt(stream, gdt, Tp, 2 * H, H, x, H, w.wqkv + (size_t)H * H * e, H, a.qkv + (size_t)H * e, 3 * H,
-                       off(l, SIMX_P_BQKV) + H, nullptr, 0, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
-    RUN(simx_rows_copy(stream, dt, dt, nseq, H, cu, nullptr, x, ytmp));
-    RUN(simx_gemm_nt(stream, gdt, nseq, H, H, ytmp, H, w.wqkv, H, qc, H, off(l, SIMX_P_BQKV), nullptr, 0, SIMX_EPI_NONE, nullptr, 0,
-                     nullptr, 0));
-    RUN(simx_mha_cls_fwd_hm(stream, dt, nseq, c->heads, d, cu, max_len, T, qc, a.qkv, ctxc, &d3, hm));
-    RUN(simx_gemm_nt(stream, gdt, nseq, H, H, ctxc, H, w.wo, H, ytmp, H, off(l, SIMX_P_BO), nullptr, 0, SIMX_EPI_NONE, nullptr, 0,
-                     nullptr, 0));
-    if (stream_lo(c)) {
-      // residual stream with corrections: the [CLS] rows of the layer input (16-bit values + correction bytes) are gathered
-      // behind the compact q / context / temporary tensors (kept for backward), the LayerNorm kernels add them in f32, and the embeddings
-      // leave as f32(hi + correction) -- never rounded to 16 bits
-      char* xg = ytmp + al((size_t)nseq * H * e);
-      char* xgl = xg + al((size_t)nseq * H * e);
-      RUN(simx_stream_rows(stream, dt, nseq, H, cu, x, xl, xg, xgl, nullptr));
-      RUN(simx_drop_residual_rows(stream, dt, nseq, H, ytmp, nullptr, nullptr, cu, &d1, a.z1));
-      RUN(simx_ln_fwd_res(stream, dt, nseq, H, a.z1, xg, xgl, off(l, SIMX_P_LN1_G), off(l, SIMX_P_LN1_B), c->eps, a.x1, a.x1l));
-      RUN(simx_gemm_nt(stream, gdt, nseq, F, H, a.x1, H, w.w1, H, a.u, F, off(l, SIMX_P_B1), nullptr, 0, SIMX_EPI_GELU, nullptr, 0, a.h, F));
-      RUN(simx_gemm_nt(stream, gdt, nseq, H, F, a.h, F, w.w2, F, ytmp, H, off(l, SIMX_P_B2), nullptr, 0, SIMX_EPI_NONE, nullptr, 0,
-                       nullptr, 0));
-      RUN(simx_drop_residual_rows(stream, dt, nseq, H, ytmp, nullptr, nullptr, cu, &d2, a.z2));
-      RUN(simx_ln_fwd_res(stream, dt, nseq, H, a.z2, a.x1, a.x1l, off(l, SIMX_P_LN2_G), off(l, SIMX_P_LN2_B), c->eps, a.xout, a.xoutl));
-      if (cls_out) RUN(simx_stream_rows(stream, dt, nseq, H, nullptr, a.xout, a.xoutl, nullptr, nullptr, cls_out));
-      return SIMX_OK;
-    }
-    RUN(simx_drop_residual_rows(stream, dt, nseq, H, ytmp, x, cu, cu, &d1, a.z1));
-    RUN(simx_ln_fwd(stream, dt, nseq, H, a.z1, off(l, SIMX_P_LN1_G), off(l, SIMX_P_LN1_B), c->eps, a.x1));
-    RUN(simx_gemm_nt(stream, gdt, nseq, F, H, a.x1, H, w.w1, H, a.u, F, off(l, SIMX_P_B1), nullptr, 0, SIMX_EPI_GELU, nullptr, 0, a.h, F));
-    RUN(simx_gemm_nt(stream, gdt, nseq, H, F, a.h, F, w.w2, F, ytmp, H, off(l, SIMX_P_B2), nullptr, 0, SIMX_EPI_NONE, nullptr, 0,
-                     nullptr, 0));
-    RUN(simx_drop_residual_rows(stream, dt, nseq, H, ytmp, a.x1, nullptr, cu, &d2, a.z2));
-    RUN(simx_ln_fwd(stream, dt, nseq, H, a.z2, off(l, SIMX_P_LN2_G), off(l, SIMX_P_LN2_B), c->eps, a.xout));
-    if (cls_out) RUN(simx_rows_copy(stream, dt, SIMX_F32, nseq, H, nullptr, nullptr, a.xout, cls_out));
-    return SIMX_OK;
-  }
-  if (pl_run(c, Tp, max_len)) {
-    // fp32 engine on operand planes: every GEMM operand is a 16-bit plane pair written by its producer -- xp by the previous
-    // LayerNorm, ctx by the attention kernel, x1p by LayerNorm, h by the FFN-in epilogue; f32 forms exist where an
-    // elementwise consumer needs them (residuals x / x1, q/k/v, the pre-LayerNorm sums, gelu')
-    const long psH = (long)Tp * H, psF = (long)Tp * F;
-    if (simx_mha_x3_ok(d, max_len)) {
-      // q / k / v leave the projection as an fp16 plane pair (no f32 form) and the attention products run on the 16-bit
-      // matrix cores from pairs (csrc/attention_x3.hip); longer sequences keep f32 q / k / v and the chunked f32 MFMA kernels
-      RUN(simx_gemm_nt_planes(stream, SIMX_F16, SIMX_EPI_NONE_PLANES, Tp, 3 * H, H, xp, H, psH, w.wqkvP, H, 3L * H * H, nullptr, 3 * H,
-                              off(l, SIMX_P_BQKV), nullptr, 0, a.qkv, 3 * H, (long)Tp * 3 * H, nullptr));
-      RUN(simx_mha_fwd_x3(stream, nseq, c->heads, d, cu, max_len, T, a.qkv, (long)Tp * 3 * H, a.ctx, psH, a.lse, &d3));
-    } else {
-      RUN(simx_gemm_nt_planes(stream, SIMX_F16, SIMX_EPI_NONE, Tp, 3 * H, H, xp, H, psH, w.wqkvP, H, 3L * H * H, (float*)a.qkv, 3 * H,
-                              off(l, SIMX_P_BQKV), nullptr, 0, nullptr, 0, 0, nullptr));
-      RUN(simx_mha_fwd_planes(stream, nseq, c->heads, d, cu, max_len, T, (const float*)a.qkv, a.ctx, psH, a.lse, &d3));
-    }
-    RUN(simx_gemm_nt_planes(stream, SIMX_F16, SIMX_EPI_NONE, Tp, H, H, a.ctx, H, psH, w.woP, H, (long)H * H, (float*)a.z1, H, off(l, SIMX_P_BO),
-                            (const float*)x, H, nullptr, 0, 0, &d1));
-    RUN(simx_ln_fwd_planes(stream, T, H, (const float*)a.z1, off(l, SIMX_P_LN1_G), off(l, SIMX_P_LN1_B), c->eps, (float*)a.x1, a.x1p, psH));
-    RUN(simx_gemm_nt_planes(stream, SIMX_F16, keep ? SIMX_EPI_GELU : SIMX_EPI_GELU_INFER, Tp, F, H, a.x1p, H, psH, w.w1P, H, (long)F * H,
-                            (float*)a.u, F, off(l, SIMX_P_B1), nullptr, 0, a.h, F, psF, nullptr));
-    RUN(simx_gemm_nt_planes(stream, SIMX_F16, SIMX_EPI_NONE, Tp, H, F, a.h, F, psF, w.w2P, F, (long)H * F, (float*)a.z2, H, off(l, SIMX_P_B2),
-                            (const float*)a.x1, H, nullptr, 0, 0, &d2));
-    RUN(simx_ln_fwd_planes(stream, T, H, (const float*)a.z2, off(l, SIMX_P_LN2_G), off(l, SIMX_P_LN2_B), c->eps, (float*)a.xout, a.xoutp, psH));
-    return SIMX_OK;
-  }
-  if (hm)
-    RUN(simx_gemm_nt_hm(stream, dt, Tp, 3 * H, H, x, H, w.wqkv, H, a.qkv, 64, off(l, SIMX_P_BQKV), nullptr, 0, nullptr, 0, hm));
+  const ClsExtra& ex = cx.A.extra;
+  if (cx.hm)      // K, V planes [heads, 3*heads) of the head-major tensor
+    RUN(simx_gemm_nt_hm(cx.stream, dt, cx.Tp, 2 * H, H, x.hi, H, w.wqkv + (size_t)H * H * e, H, a.qkv + (size_t)c->heads * cx.hm * 64 * e, 64,
+                        cx.p(l, SIMX_P_BQKV) + H, nullptr, 0, nullptr, 0, cx.hm));
   else
-    RUN(simx_gemm_nt(stream, gdt, Tp, 3 * H, H, x, H, w.wqkv, H, a.qkv, 3 * H, off(l, SIMX_P_BQKV), nullptr, 0, SIMX_EPI_NONE,
+    RUN(simx_gemm_nt(cx.stream, gdt, cx.Tp, 2 * H, H, x.hi, H, w.wqkv + (size_t)H * H * e, H, a.qkv + (size_t)H * e, 3 * H,
+                     cx.p(l, SIMX_P_BQKV) + H, nullptr, 0, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
+  RUN(simx_rows_copy(cx.stream, dt, dt, nseq, H, cx.cu, nullptr, x.hi, ex.ytmp));
+  RUN(simx_gemm_nt(cx.stream, gdt, nseq, H, H, ex.ytmp, H, w.wqkv, H, ex.qc, H, cx.p(l, SIMX_P_BQKV), nullptr, 0, SIMX_EPI_NONE, nullptr, 0,
+                   nullptr, 0));
+  RUN(simx_mha_cls_fwd_hm(cx.stream, dt, nseq, c->heads, d, cx.cu, cx.max_len, cx.T, ex.qc, a.qkv, ex.ctxc, &d3, cx.hm));
+  RUN(simx_gemm_nt(cx.stream, gdt, nseq, H, H, ex.ctxc, H, w.wo, H, ex.ytmp, H, cx.p(l, SIMX_P_BO), nullptr, 0, SIMX_EPI_NONE, nullptr, 0,
+                   nullptr, 0));
+  // stream_lo: the [CLS] rows of the layer input (16-bit values + correction bytes) are gathered into xg / xgl, the dense outputs
+  // are dropped WITHOUT their residual, the LayerNorm kernels add the residual in f32, and the embeddings leave as
+  // f32(hi + correction) -- never rounded to 16 bits.  Otherwise the residual rides in simx_drop_residual_rows.
+  const bool sl = stream_lo(c);
+  if (sl) RUN(simx_stream_rows(cx.stream, dt, nseq, H, cx.cu, x.hi, x.lo, ex.xg, ex.xgl, nullptr));
+  RUN(simx_drop_residual_rows(cx.stream, dt, nseq, H, ex.ytmp, sl ? nullptr : x.hi, sl ? nullptr : cx.cu, cx.cu, &d1, a.z1));
+  RUN(simx_ln_fwd_res(cx.stream, dt, nseq, H, a.z1, sl ? ex.xg : nullptr, sl ? ex.xgl : nullptr, cx.p(l, SIMX_P_LN1_G), cx.p(l, SIMX_P_LN1_B), c->eps,
+                      a.x1, a.x1l));
+  RUN(simx_gemm_nt(cx.stream, gdt, nseq, F, H, a.x1, H, w.w1, H, a.u, F, cx.p(l, SIMX_P_B1), nullptr, 0, SIMX_EPI_GELU, nullptr, 0, a.h, F));
+  RUN(simx_gemm_nt(cx.stream, gdt, nseq, H, F, a.h, F, w.w2, F, ex.ytmp, H, cx.p(l, SIMX_P_B2), nullptr, 0, SIMX_EPI_NONE, nullptr, 0,
+                   nullptr, 0));
+  RUN(simx_drop_residual_rows(cx.stream, dt, nseq, H, ex.ytmp, sl ? nullptr : a.x1, nullptr, cx.cu, &d2, a.z2));
+  RUN(simx_ln_fwd_res(cx.stream, dt, nseq, H, a.z2, sl ? a.x1 : nullptr, sl ? a.x1l : nullptr, cx.p(l, SIMX_P_LN2_G), cx.p(l, SIMX_P_LN2_B), c->eps,
+                      a.xout, a.xoutl));
+  if (!cls_out) return SIMX_OK;
+  if (sl) return simx_stream_rows(cx.stream, dt, nseq, H, nullptr, a.xout, a.xoutl, nullptr, nullptr, cls_out);
+  return simx_rows_copy(cx.stream, dt, SIMX_F32, nseq, H, nullptr, nullptr, a.xout, cls_out);
+}
+
+// fp32 engine on operand planes: every GEMM operand is a 16-bit plane pair written by its producer -- x.planes by the previous
+// LayerNorm, ctx by the attention kernel, x1p by LayerNorm, h by the FFN-in epilogue; f32 forms exist where an
+// elementwise consumer needs them (residuals x / x1, q/k/v, the pre-LayerNorm sums, gelu')
+static int layer_fwd_planes(const Ctx& cx, int l, const XS& x, const ALayer& a, int keep) {
+  const simx_bert_cfg* c = cx.c;
+  const int H = c->hidden, F = c->inter, d = H / c->heads, T = cx.T, Tp = cx.Tp;
+  const WLayer w = wlayer(c, cx.params, cx.wcache, l);
+  const simx_dropout d1 = drop_of(c, l, 1), d2 = drop_of(c, l, 2), d3 = drop_of(c, l, 3);
+  const long psH = (long)Tp * H, psF = (long)Tp * F;
+  if (simx_mha_x3_ok(d, cx.max_len)) {
+    // q / k / v leave the projection as an fp16 plane pair (no f32 form) and the attention products run on the 16-bit
+    // matrix cores from pairs (csrc/attention_x3.hip); longer sequences keep f32 q / k / v and the chunked f32 MFMA kernels
+    RUN(simx_gemm_nt_planes(cx.stream, SIMX_F16, SIMX_EPI_NONE_PLANES, Tp, 3 * H, H, x.planes, H, psH, w.wqkvP, H, 3L * H * H, nullptr, 3 * H,
+                            cx.p(l, SIMX_P_BQKV), nullptr, 0, a.qkv, 3 * H, (long)Tp * 3 * H, nullptr));
+    RUN(simx_mha_fwd_x3(cx.stream, cx.nseq, c->heads, d, cx.cu, cx.max_len, T, a.qkv, (long)Tp * 3 * H, a.ctx, psH, a.lse, &d3));
+  } else {
+    RUN(simx_gemm_nt_planes(cx.stream, SIMX_F16, SIMX_EPI_NONE, Tp, 3 * H, H, x.planes, H, psH, w.wqkvP, H, 3L * H * H, (float*)a.qkv, 3 * H,
+                            cx.p(l, SIMX_P_BQKV), nullptr, 0, nullptr, 0, 0, nullptr));
+    RUN(simx_mha_fwd_planes(cx.stream, cx.nseq, c->heads, d, cx.cu, cx.max_len, T, (const float*)a.qkv, a.ctx, psH, a.lse, &d3));
+  }
+  RUN(simx_gemm_nt_planes(cx.stream, SIMX_F16, SIMX_EPI_NONE, Tp, H, H, a.ctx, H, psH, w.woP, H, (long)H * H, (float*)a.z1, H, cx.p(l, SIMX_P_BO),
+                          (const float*)x.hi, H, nullptr, 0, 0, &d1));
+  RUN(simx_ln_fwd_planes(cx.stream, T, H, (const float*)a.z1, cx.p(l, SIMX_P_LN1_G), cx.p(l, SIMX_P_LN1_B), c->eps, (float*)a.x1, a.x1p, psH));
+  RUN(simx_gemm_nt_planes(cx.stream, SIMX_F16, keep ? SIMX_EPI_GELU : SIMX_EPI_GELU_INFER, Tp, F, H, a.x1p, H, psH, w.w1P, H, (long)F * H,
+                          (float*)a.u, F, cx.p(l, SIMX_P_B1), nullptr, 0, a.h, F, psF, nullptr));
+  RUN(simx_gemm_nt_planes(cx.stream, SIMX_F16, SIMX_EPI_NONE, Tp, H, F, a.h, F, psF, w.w2P, F, (long)H * F, (float*)a.z2, H, cx.p(l, SIMX_P_B2),
+                          (const float*)a.x1, H, nullptr, 0, 0, &d2));
+  return simx_ln_fwd_planes(cx.stream, T, H, (const float*)a.z2, cx.p(l, SIMX_P_LN2_G), cx.p(l, SIMX_P_LN2_B), c->eps, (float*)a.xout, a.xoutp, psH);
+}
+
+// the 16-bit engines and the fp32 engine on register-split (or exact f32) GEMMs
+static int layer_fwd_dense(const Ctx& cx, int l, const XS& x, const ALayer& a, int keep) {
+  const simx_bert_cfg* c = cx.c;
+  const int H = c->hidden, F = c->inter, dt = c->dtype, d = H / c->heads, T = cx.T, Tp = cx.Tp, gdt = cx.gdt;
+  const WLayer w = wlayer(c, cx.params, cx.wcache, l);
+  const simx_dropout d1 = drop_of(c, l, 1), d2 = drop_of(c, l, 2), d3 = drop_of(c, l, 3);
+  if (cx.hm)
+    RUN(simx_gemm_nt_hm(cx.stream, dt, Tp, 3 * H, H, x.hi, H, w.wqkv, H, a.qkv, 64, cx.p(l, SIMX_P_BQKV), nullptr, 0, nullptr, 0, cx.hm));
+  else
+    RUN(simx_gemm_nt(cx.stream, gdt, Tp, 3 * H, H, x.hi, H, w.wqkv, H, a.qkv, 3 * H, cx.p(l, SIMX_P_BQKV), nullptr, 0, SIMX_EPI_NONE,
                      nullptr, 0, nullptr, 0));
-  RUN(simx_mha_fwd_hm(stream, dt, nseq, c->heads, d, cu, max_len, T, a.qkv, a.ctx, a.lse, &d3, hm));
+  RUN(simx_mha_fwd_hm(cx.stream, dt, cx.nseq, c->heads, d, cx.cu, cx.max_len, T, a.qkv, a.ctx, a.lse, &d3, cx.hm));
   // stream_lo: the dense output leaves without the residual (a plain bias + dropout epilogue) and the LayerNorm kernel sums
   // dense + x_hi + x_lo in f32; otherwise the residual rides in the GEMM epilogue and z1 is the LayerNorm input itself
   const bool sl = stream_lo(c);
-  RUN(simx_gemm_nt_ex(stream, gdt, Tp, H, H, a.ctx, H, w.wo, H, a.z1, H, off(l, SIMX_P_BO), sl ? nullptr : x, H, SIMX_EPI_NONE, nullptr, 0,
+  RUN(simx_gemm_nt_ex(cx.stream, gdt, Tp, H, H, a.ctx, H, w.wo, H, a.z1, H, cx.p(l, SIMX_P_BO), sl ? nullptr : x.hi, H, SIMX_EPI_NONE, nullptr, 0,
                       nullptr, 0, &d1));
-  RUN(simx_ln_fwd_res(stream, dt, T, H, a.z1, sl ? x : nullptr, sl ? xl : nullptr, off(l, SIMX_P_LN1_G), off(l, SIMX_P_LN1_B), c->eps, a.x1,
+  RUN(simx_ln_fwd_res(cx.stream, dt, T, H, a.z1, sl ? x.hi : nullptr, sl ? x.lo : nullptr, cx.p(l, SIMX_P_LN1_G), cx.p(l, SIMX_P_LN1_B), c->eps, a.x1,
                       a.x1l));
-  RUN(simx_gemm_nt(stream, gdt, Tp, F, H, a.x1, H, w.w1, H, a.u, F, off(l, SIMX_P_B1), nullptr, 0,
+  RUN(simx_gemm_nt(cx.stream, gdt, Tp, F, H, a.x1, H, w.w1, H, a.u, F, cx.p(l, SIMX_P_B1), nullptr, 0,
                    keep ? SIMX_EPI_GELU : SIMX_EPI_GELU_INFER, nullptr, 0, a.h, F));   // no backward from this slot: u has no reader
-  RUN(simx_gemm_nt_ex(stream, gdt, Tp, H, F, a.h, F, w.w2, F, a.z2, H, off(l, SIMX_P_B2), sl ? nullptr : a.x1, H, SIMX_EPI_NONE, nullptr, 0,
+  RUN(simx_gemm_nt_ex(cx.stream, gdt, Tp, H, F, a.h, F, w.w2, F, a.z2, H, cx.p(l, SIMX_P_B2), sl ? nullptr : a.x1, H, SIMX_EPI_NONE, nullptr, 0,
                       nullptr, 0, &d2));
-  RUN(simx_ln_fwd_res(stream, dt, T, H, a.z2, sl ? a.x1 : nullptr, sl ? a.x1l : nullptr, off(l, SIMX_P_LN2_G), off(l, SIMX_P_LN2_B), c->eps,
-                      a.xout, a.xoutl));
-  return SIMX_OK;
+  return simx_ln_fwd_res(cx.stream, dt, T, H, a.z2, sl ? a.x1 : nullptr, sl ? a.x1l : nullptr, cx.p(l, SIMX_P_LN2_G), cx.p(l, SIMX_P_LN2_B), c->eps,
+                         a.xout, a.xoutl);
+}
+
+static int layer_fwd(const Ctx& cx, int l, const XS& x, const ALayer& a, int keep, bool cls_form, float* cls_out) {
+  if (cls_form) return layer_fwd_cls(cx, l, x, a, cls_out);
+  if (pl_run(cx.c, cx.Tp, cx.max_len)) return layer_fwd_planes(cx, l, x, a, keep);
+  return layer_fwd_dense(cx, l, x, a, keep);
 }
 
 extern "C" int simx_bert_fwd(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
@@ -479,51 +523,184 @@ extern "C" int simx_bert_fwd(simx_stream_t stream, const simx_bert_cfg* c, const
                              void* act, size_t act_bytes, int save, float* cls_out, void* hidden_out) {
   RUN(check_io(c, nseq, T, max_len, "bert_fwd"));
   SIMX_REQUIRE(params && wcache && ids && pos_ids && cu && act, SIMX_ERR_BAD_SHAPE, "bert_fwd: NULL buffer");
-  SIMX_REQUIRE(act_bytes >= simx_bert_act_bytes(c, T, nseq, save), SIMX_ERR_WORKSPACE, "bert_fwd: activation buffer %zu < %zu",
-               act_bytes, simx_bert_act_bytes(c, T, nseq, save));
+  const Ctx cx = make_ctx(stream, c, params, nullptr, wcache, cu, nseq, T, max_len, act, save);
+  SIMX_REQUIRE(act_bytes >= cx.A.bytes, SIMX_ERR_WORKSPACE, "bert_fwd: activation buffer %zu < %zu", act_bytes, cx.A.bytes);
   const int H = c->hidden, dt = c->dtype;
-  const int Tp = rows_cap(T);
-  auto off = [&](int l, int w) { return params + simx_bert_param_offset(c, l, w); };
-  const char* x = act_x0(act);
-  const char* xl = xs_lo(c, x, Tp);
-  const char* xp = xs_pl(c, x, Tp);
+  XS x = cx.A.x0;
   {
     const simx_dropout d0 = drop_of(c, -1, 0);
-    if (xp)
-      RUN(simx_embed_ln_fwd_planes(stream, T, H, ids, pos_ids, off(-1, SIMX_P_WORD), off(-1, SIMX_P_POS), off(-1, SIMX_P_TYPE),
-                                   off(-1, SIMX_P_EMB_LN_G), off(-1, SIMX_P_EMB_LN_B), c->eps, (float*)act_x0(act), const_cast<char*>(xp),
-                                   (long)Tp * H, &d0));
+    if (x.planes)
+      RUN(simx_embed_ln_fwd_planes(stream, T, H, ids, pos_ids, cx.p(-1, SIMX_P_WORD), cx.p(-1, SIMX_P_POS), cx.p(-1, SIMX_P_TYPE),
+                                   cx.p(-1, SIMX_P_EMB_LN_G), cx.p(-1, SIMX_P_EMB_LN_B), c->eps, (float*)x.hi, x.planes, (long)cx.Tp * H, &d0));
     else
-      RUN(simx_embed_ln_fwd_lo(stream, dt, T, H, ids, pos_ids, off(-1, SIMX_P_WORD), off(-1, SIMX_P_POS), off(-1, SIMX_P_TYPE),
-                               off(-1, SIMX_P_EMB_LN_G), off(-1, SIMX_P_EMB_LN_B), c->eps, act_x0(act), const_cast<char*>(xl), &d0));
+      RUN(simx_embed_ln_fwd_lo(stream, dt, T, H, ids, pos_ids, cx.p(-1, SIMX_P_WORD), cx.p(-1, SIMX_P_POS), cx.p(-1, SIMX_P_TYPE),
+                               cx.p(-1, SIMX_P_EMB_LN_G), cx.p(-1, SIMX_P_EMB_LN_B), c->eps, x.hi, x.lo, &d0));
   }
   const bool cls_only = c->cls_only_last_layer != 0;
-  const bool ckpt = ckpt_mode(c, save);
   SIMX_REQUIRE(!(cls_only && hidden_out), SIMX_ERR_BAD_SHAPE, "bert_fwd: cls_only_last_layer leaves no full hidden state to return");
   for (int l = 0; l < c->layers; ++l) {
-    const ALayer a = alayer(c, act, Tp, l, save);
+    const ALayer a = alayer(c, cx.A, l);
     const bool cls_form = cls_only && l == c->layers - 1;
     // (checkpoint mode: the slot is recomputed by backward, so the forward runs it in its inference form)
-    RUN(layer_fwd((hipStream_t)stream, c, params, wcache, l, x, xl, xp, a, act_extra(c, act, Tp, save), cu, nseq, T, Tp, max_len,
-                  save && !ckpt, cls_form, cls_out));
+    RUN(layer_fwd(cx, l, x, a, save && !cx.A.ckpt, cls_form, cls_out));
     if (cls_form) return SIMX_OK;
-    x = a.xout;
-    xl = a.xoutl;
-    xp = a.xoutp;
+    x = XS{a.xout, a.xoutl, a.xoutp};
   }
   if (cls_out) {
     // (a stream_lo tower: the embeddings are f32(hi + correction byte), as the [CLS]-only last layer returns them -- the same
     // precision whichever form the last layer ran in)
-    if (stream_lo(c) && xl) RUN(simx_stream_rows(stream, dt, nseq, H, cu, x, xl, nullptr, nullptr, cls_out));
-    else RUN(simx_cls_gather(stream, dt, nseq, H, cu, x, cls_out));
+    if (x.lo) RUN(simx_stream_rows(stream, dt, nseq, H, cu, x.hi, x.lo, nullptr, nullptr, cls_out));
+    else RUN(simx_cls_gather(stream, dt, nseq, H, cu, x.hi, cls_out));
   }
   if (hidden_out) {
-    if (hipMemcpyAsync(hidden_out, x, (size_t)T * H * esz(dt), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+    if (hipMemcpyAsync(hidden_out, x.hi, (size_t)T * H * esz(dt), hipMemcpyDeviceToDevice, cx.stream) != hipSuccess) {
       simx_set_error("bert_fwd: copy of last hidden state failed");
       return SIMX_ERR_HIP;
     }
   }
   return SIMX_OK;
+}
+
+// ---- backward: the three layer forms, mirroring the forwards.  On entry s.bufB holds the gradient w.r.t. the layer's output, on
+// exit the gradient w.r.t. its input (full [T,H] tensors, except on entry to the [CLS] form).
+
+// The post-attention half of a layer's backward -- output LayerNorm, FFN, attention-output LayerNorm, Wo -- on `n` rows
+// (`np`: the row count of the NT GEMMs).  ctx: the attention context the Wo wgrad contracts against; res: the layer's input
+// rows (read with stream_lo only: the residual of the attention-output LayerNorm); keys: the rows' dropout keys (NULL: the row
+// index); dctx: where the gradient of the attention context goes.  Leaves the gradient of the residual branch in s.bufA.
+struct PostRows { int n, np; const char* ctx; const char *res, *resl; const int32_t* keys; char* dctx; };
+static int layer_bwd_post(const Ctx& cx, const Scratch& s, int l, const WLayer& w, const ALayer& a, const PostRows& r) {
+  const simx_bert_cfg* c = cx.c;
+  const int H = c->hidden, F = c->inter, dt = c->dtype, gdb = cx.gdb;
+  const simx_dropout d1 = drop_of(c, l, 1), d2 = drop_of(c, l, 2);
+  const bool sl = stream_lo(c);
+  // gradient of the (dropped) dense output: the masked copy when hidden dropout is live, else dz itself
+  char* dz_masked = hidden_drop_live(c) ? s.bufC : nullptr;
+  const char* dzm = dz_masked ? dz_masked : s.bufA;
+  // output LayerNorm : dz2, dgamma2, dbeta2, db2
+  RUN(simx_ln_bwd_res(cx.stream, dt, r.n, H, a.z2, sl ? a.x1 : nullptr, sl ? a.x1l : nullptr, cx.p(l, SIMX_P_LN2_G), c->eps, s.bufB, s.bufA,
+                      dz_masked, cx.g(l, SIMX_P_LN2_G), cx.g(l, SIMX_P_LN2_B), cx.g(l, SIMX_P_B2), &d2, r.keys, cx.gs));
+  // du = (dz2m . W2) * gelu'(u)
+  RUN(simx_gemm_nt(cx.stream, gdb, r.np, F, H, dzm, H, w.w2T, H, s.du, F, nullptr, nullptr, 0, SIMX_EPI_DGELU, a.u, F, nullptr, 0));
+  RUN(simx_gemm_tn_gs(cx.stream, gdb, H, F, r.n, dzm, H, a.h, F, cx.g(l, SIMX_P_W2), F, 1, s.tnws, s.tnws_bytes, nullptr, 0, cx.gs));
+  // dx1 = du . W1 + dz2
+  RUN(simx_gemm_nt(cx.stream, gdb, r.np, H, F, s.du, F, w.w1T, F, s.bufB, H, nullptr, s.bufA, H, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
+  RUN(simx_gemm_tn_gs(cx.stream, gdb, F, H, r.n, s.du, F, a.x1, H, cx.g(l, SIMX_P_W1), H, 1, s.tnws, s.tnws_bytes, cx.g(l, SIMX_P_B1), 0, cx.gs));
+  // attention-output LayerNorm : dz1, dgamma1, dbeta1, dbo
+  RUN(simx_ln_bwd_res(cx.stream, dt, r.n, H, a.z1, sl ? r.res : nullptr, sl ? r.resl : nullptr, cx.p(l, SIMX_P_LN1_G), c->eps, s.bufB, s.bufA,
+                      dz_masked, cx.g(l, SIMX_P_LN1_G), cx.g(l, SIMX_P_LN1_B), cx.g(l, SIMX_P_BO), &d1, r.keys, cx.gs));
+  // dctx = dz1m . Wo
+  RUN(simx_gemm_nt(cx.stream, gdb, r.np, H, H, dzm, H, w.woT, H, r.dctx, H, nullptr, nullptr, 0, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
+  return simx_gemm_tn_gs(cx.stream, gdb, H, H, r.n, dzm, H, r.ctx, H, cx.g(l, SIMX_P_WO), H, 1, s.tnws, s.tnws_bytes, nullptr, 0, cx.gs);
+}
+
+// mirror of the forward's [CLS]-only last layer: everything up to the attention core runs on nseq rows
+static int layer_bwd_cls(const Ctx& cx, const Scratch& s, int l, const float* dcls) {
+  const simx_bert_cfg* c = cx.c;
+  const int H = c->hidden, dt = c->dtype, d = H / c->heads, nseq = cx.nseq, T = cx.T, Tp = cx.Tp, hm = cx.hm, gdb = cx.gdb;
+  const size_t e = esz(dt);
+  const WLayer w = wlayer(c, cx.params, cx.wcache, l);
+  const XS x = layer_input(c, cx.A, l);
+  const ALayer a = alayer_bwd(c, cx.A, l);
+  if (cx.A.ckpt) RUN(layer_fwd(cx, l, x, a, 1, true, nullptr));
+  const simx_dropout d3 = drop_of(c, l, 3);
+  const ClsExtra& ex = cx.A.extra;                    // qc, ctxc and (stream_lo) xg / xgl: saved by the forward
+  RUN(simx_rows_copy_gs(cx.stream, SIMX_F32, dt, nseq, H, nullptr, nullptr, dcls, s.bufB, cx.gs));
+  // e1 = dctx (gradient of the attention context, [CLS] rows), bufA[0:nseq] = gradient of the residual branch
+  RUN(layer_bwd_post(cx, s, l, w, a, PostRows{nseq, nseq, ex.ctxc, ex.xg, ex.xgl, cx.cu, s.e1}));
+  // attention core for the one query per sequence: e0 = dq [nseq,H]; dK, dV for every token -> dqkv[:, H:3H]
+  RUN(simx_mha_cls_bwd_hm(cx.stream, dt, nseq, c->heads, d, cx.cu, cx.max_len, T, ex.qc, a.qkv, s.e1, s.e0, s.dqkv, &d3, hm));
+  // Q projection ([CLS] rows): dWq, dbq, and dx = dq . Wq + (residual-branch gradient), still compact
+  RUN(simx_rows_copy(cx.stream, dt, dt, nseq, H, cx.cu, nullptr, x.hi, s.e2));
+  RUN(simx_gemm_tn_gs(cx.stream, gdb, H, H, nseq, s.e0, H, s.e2, H, cx.g(l, SIMX_P_WQKV), H, 1, s.tnws, s.tnws_bytes, cx.g(l, SIMX_P_BQKV), 0, cx.gs));
+  RUN(simx_gemm_nt(cx.stream, gdb, nseq, H, H, s.e0, H, w.wqkvT, 3 * H, s.e1, H, nullptr, s.bufA, H, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
+  // back to full tensors: that gradient is zero outside the [CLS] rows
+  if (hipMemsetAsync(s.bufA, 0, (size_t)T * H * e, cx.stream) != hipSuccess) {
+    simx_set_error("bert_bwd: memset failed");
+    return SIMX_ERR_HIP;
+  }
+  RUN(simx_rows_copy(cx.stream, dt, dt, nseq, H, nullptr, cx.cu, s.e1, s.bufA));
+  // K, V projections (every token): dx += dkv . Wkv ; dWkv, dbkv
+  if (hm) {
+    const char* dkv = s.dqkv + (size_t)c->heads * hm * 64 * e;                  // planes [heads, 3*heads)
+    RUN(simx_gemm_nt_hm(cx.stream, dt, Tp, H, 2 * H, dkv, 64, w.wqkvT + (size_t)H * e, 3 * H, s.bufB, H, nullptr, s.bufA, H, nullptr, hm, 0));
+    return simx_gemm_tn_gs(cx.stream, gdb, 2 * H, H, T, dkv, 0, x.hi, H, cx.g(l, SIMX_P_WQKV) + (size_t)H * H, H, 1, s.tnws, s.tnws_bytes,
+                           cx.g(l, SIMX_P_BQKV) + H, hm, cx.gs);
+  }
+  RUN(simx_gemm_nt(cx.stream, gdb, Tp, H, 2 * H, s.dqkv + (size_t)H * e, 3 * H, w.wqkvT + (size_t)H * e, 3 * H, s.bufB, H, nullptr, s.bufA, H,
+                   SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
+  return simx_gemm_tn_gs(cx.stream, gdb, 2 * H, H, T, s.dqkv + (size_t)H * e, 3 * H, x.hi, H, cx.g(l, SIMX_P_WQKV) + (size_t)H * H, H, 1, s.tnws,
+                         s.tnws_bytes, cx.g(l, SIMX_P_BQKV) + H, 0, cx.gs);
+}
+
+// fp32 engine on operand planes (see layer_fwd_planes): gradients that feed a GEMM leave their producer as bf16 plane pairs --
+// bufC = dz (x dropout mask) from the LayerNorm backward, du from the DGELU epilogue, dqkv from the attention backward;
+// the activation operand of each wgrad GEMM is converted to a bf16 pair into xconv right before its use
+static int layer_bwd_planes(const Ctx& cx, const Scratch& s, int l) {
+  const simx_bert_cfg* c = cx.c;
+  const int H = c->hidden, F = c->inter, d = H / c->heads, nseq = cx.nseq, T = cx.T, Tp = cx.Tp;
+  const WLayer w = wlayer(c, cx.params, cx.wcache, l);
+  const XS x = layer_input(c, cx.A, l);
+  const ALayer a = alayer_bwd(c, cx.A, l);
+  if (cx.A.ckpt) RUN(layer_fwd(cx, l, x, a, 1, false, nullptr));
+  const simx_dropout d1 = drop_of(c, l, 1), d2 = drop_of(c, l, 2), d3 = drop_of(c, l, 3);
+  const long psH = (long)Tp * H, psF = (long)Tp * F, ps3 = (long)Tp * 3 * H;
+  RUN(simx_ln_bwd_planes(cx.stream, T, H, (const float*)a.z2, cx.p(l, SIMX_P_LN2_G), c->eps, (const float*)s.bufB, (float*)s.bufA, s.bufC, psH,
+                         cx.g(l, SIMX_P_LN2_G), cx.g(l, SIMX_P_LN2_B), cx.g(l, SIMX_P_B2), &d2));
+  // (the bias gradient of B1 = column sums of du comes out of this epilogue, so the W1 wgrad runs on the four-plane-stage
+  // kernel, which carries no fused bias pass; the deterministic mode keeps the wgrad kernel's ordered pass)
+  const bool b1_here = !simx_det();
+  RUN(simx_gemm_nt_planes_cs(cx.stream, SIMX_BF16, SIMX_EPI_DGELU, Tp, F, H, s.bufC, H, psH, w.w2TP, H, (long)F * H, nullptr, F, nullptr,
+                             (const float*)a.u, F, s.du, F, psF, nullptr, b1_here ? cx.g(l, SIMX_P_B1) : nullptr, T));
+  RUN(simx_planes_from(cx.stream, SIMX_F16, SIMX_BF16, T, F, a.h, F, psF, s.xconv, F, psF));
+  RUN(simx_gemm_tn_planes(cx.stream, H, F, T, s.bufC, H, psH, s.xconv, F, psF, cx.g(l, SIMX_P_W2), F, 1, s.tnws, s.tnws_bytes, nullptr));
+  RUN(simx_gemm_nt_planes(cx.stream, SIMX_BF16, SIMX_EPI_NONE, Tp, H, F, s.du, F, psF, w.w1TP, F, (long)H * F, (float*)s.bufB, H, nullptr,
+                          (const float*)s.bufA, H, nullptr, 0, 0, nullptr));
+  RUN(simx_planes_from(cx.stream, SIMX_F32, SIMX_BF16, T, H, a.x1, H, 0, s.xconv, H, psH));
+  RUN(simx_gemm_tn_planes(cx.stream, F, H, T, s.du, F, psF, s.xconv, H, psH, cx.g(l, SIMX_P_W1), H, 1, s.tnws, s.tnws_bytes,
+                          b1_here ? nullptr : cx.g(l, SIMX_P_B1)));
+  RUN(simx_ln_bwd_planes(cx.stream, T, H, (const float*)a.z1, cx.p(l, SIMX_P_LN1_G), c->eps, (const float*)s.bufB, (float*)s.bufA, s.bufC, psH,
+                         cx.g(l, SIMX_P_LN1_G), cx.g(l, SIMX_P_LN1_B), cx.g(l, SIMX_P_BO), &d1));
+  RUN(simx_gemm_nt_planes(cx.stream, SIMX_BF16, SIMX_EPI_NONE, Tp, H, H, s.bufC, H, psH, w.woTP, H, (long)H * H, (float*)s.bufB, H, nullptr, nullptr, 0,
+                          nullptr, 0, 0, nullptr));
+  RUN(simx_planes_from(cx.stream, SIMX_F16, SIMX_BF16, T, H, a.ctx, H, psH, s.xconv, H, psH));
+  RUN(simx_gemm_tn_planes(cx.stream, H, H, T, s.bufC, H, psH, s.xconv, H, psH, cx.g(l, SIMX_P_WO), H, 1, s.tnws, s.tnws_bytes, nullptr));
+  // (x3 attention: the QKV bias gradient = column sums of dq | dk | dv comes out of the attention backward, so the Wqkv wgrad
+  // runs on the four-plane-stage kernel too; the deterministic mode keeps the wgrad kernel's ordered pass)
+  const bool bqkv_here = simx_mha_x3_ok(d, cx.max_len) && !simx_det();
+  if (simx_mha_x3_ok(d, cx.max_len))
+    RUN(simx_mha_bwd_x3_bias(cx.stream, nseq, c->heads, d, cx.cu, cx.max_len, T, a.qkv, ps3, a.ctx, psH, a.lse, (const float*)s.bufB, s.dqkv, ps3, &d3,
+                             bqkv_here ? cx.g(l, SIMX_P_BQKV) : nullptr));
+  else
+    RUN(simx_mha_bwd_planes(cx.stream, nseq, c->heads, d, cx.cu, cx.max_len, T, (const float*)a.qkv, a.ctx, psH, a.lse, (const float*)s.bufB, s.dqkv, ps3,
+                            &d3));
+  RUN(simx_gemm_nt_planes(cx.stream, SIMX_BF16, SIMX_EPI_NONE, Tp, H, 3 * H, s.dqkv, 3 * H, ps3, w.wqkvTP, 3 * H, 3L * H * H, (float*)s.bufB, H, nullptr,
+                          (const float*)s.bufA, H, nullptr, 0, 0, nullptr));
+  RUN(simx_planes_from(cx.stream, SIMX_F32, SIMX_BF16, T, H, x.hi, H, 0, s.xconv, H, psH));
+  return simx_gemm_tn_planes(cx.stream, 3 * H, H, T, s.dqkv, 3 * H, ps3, s.xconv, H, psH, cx.g(l, SIMX_P_WQKV), H, 1, s.tnws, s.tnws_bytes,
+                             bqkv_here ? nullptr : cx.g(l, SIMX_P_BQKV));
+}
+
+static int layer_bwd_dense(const Ctx& cx, const Scratch& s, int l) {
+  const simx_bert_cfg* c = cx.c;
+  const int H = c->hidden, dt = c->dtype, d = H / c->heads, T = cx.T, Tp = cx.Tp, hm = cx.hm, gdb = cx.gdb;
+  const WLayer w = wlayer(c, cx.params, cx.wcache, l);
+  const XS x = layer_input(c, cx.A, l);
+  const ALayer a = alayer_bwd(c, cx.A, l);
+  if (cx.A.ckpt) RUN(layer_fwd(cx, l, x, a, 1, false, nullptr));
+  const simx_dropout d3 = drop_of(c, l, 3);
+  RUN(layer_bwd_post(cx, s, l, w, a, PostRows{T, Tp, a.ctx, x.hi, x.lo, nullptr, s.bufB}));
+  RUN(simx_mha_bwd_hm(cx.stream, dt, cx.nseq, c->heads, d, cx.cu, cx.max_len, T, a.qkv, a.ctx, a.lse, s.bufB, s.dqkv, &d3, hm));
+  // dx = dqkv . Wqkv + dz1
+  if (hm) {
+    RUN(simx_gemm_nt_hm(cx.stream, dt, Tp, H, 3 * H, s.dqkv, 64, w.wqkvT, 3 * H, s.bufB, H, nullptr, s.bufA, H, nullptr, hm, 0));
+    return simx_gemm_tn_gs(cx.stream, gdb, 3 * H, H, T, s.dqkv, 0, x.hi, H, cx.g(l, SIMX_P_WQKV), H, 1, s.tnws, s.tnws_bytes, cx.g(l, SIMX_P_BQKV), hm,
+                           cx.gs);
+  }
+  RUN(simx_gemm_nt(cx.stream, gdb, Tp, H, 3 * H, s.dqkv, 3 * H, w.wqkvT, 3 * H, s.bufB, H, nullptr, s.bufA, H, SIMX_EPI_NONE, nullptr, 0,
+                   nullptr, 0));
+  return simx_gemm_tn_gs(cx.stream, gdb, 3 * H, H, T, s.dqkv, 3 * H, x.hi, H, cx.g(l, SIMX_P_WQKV), H, 1, s.tnws, s.tnws_bytes,
+                         cx.g(l, SIMX_P_BQKV), 0, cx.gs);
 }
 
 extern "C" int simx_bert_bwd(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
@@ -554,241 +731,29 @@ extern "C" int simx_bert_bwd_range(simx_stream_t stream, const simx_bert_cfg* c,
   SIMX_REQUIRE(!top || ((dcls != nullptr) != (dhidden != nullptr)), SIMX_ERR_BAD_SHAPE, "bert_bwd: pass exactly one of dcls / dhidden");
   SIMX_REQUIRE(!(dhidden && c->cls_only_last_layer), SIMX_ERR_BAD_SHAPE,
                "bert_bwd: a gradient for the whole hidden state needs the full last layer (cls_only_last_layer = 0)");
-  SIMX_REQUIRE(act_bytes >= simx_bert_act_bytes(c, T, nseq, 1), SIMX_ERR_WORKSPACE, "bert_bwd: activation buffer too small");
-  SIMX_REQUIRE(scratch_bytes >= simx_bert_bwd_scratch_bytes(c, T, nseq), SIMX_ERR_WORKSPACE, "bert_bwd: scratch %zu < %zu",
-               scratch_bytes, simx_bert_bwd_scratch_bytes(c, T, nseq));
-  const int H = c->hidden, F = c->inter, dt = c->dtype, d = H / c->heads;
-  const int Tp = rows_cap(T);
-  const size_t e = esz(dt);
-  const bool ckpt = c->grad_checkpoint != 0;
-  auto off = [&](int l, int w) { return params + simx_bert_param_offset(c, l, w); };
-  auto goff = [&](int l, int w) { return grads + simx_bert_param_offset(c, l, w); };
-  // scratch: bufB carries the gradient w.r.t. the current layer's OUTPUT from one layer to the next -- and from one
-  // simx_bert_bwd_range call to the next (the caller keeps `scratch` alive and untouched between the parts)
-  char* bufA = (char*)scratch;
-  char* bufB = bufA + al((size_t)Tp * H * e);
-  char* bufC = bufB + al((size_t)Tp * H * e);                    // dropout-masked copy of dz (only with hidden dropout)
-  char* du = bufC + al((size_t)Tp * H * e);
-  const bool hd = c->hidden_dropout > 0.f;
-  char* dqkv = du + al((size_t)Tp * F * e);
-  char* tnws = dqkv + al((size_t)Tp * 3 * H * e);
-  const size_t tnws_bytes = tn_ws_max(c, T);
-  char* xconv = tnws + tnws_bytes + 3 * al((size_t)(nseq > 0 ? nseq : Tp) * H * e);   // operand planes: bf16 pair of a wgrad's activation operand
-  const bool pl = pl_run(c, Tp, max_len);
-  const int hm = hm_rows_for(c, T, Tp, max_len);        // layout of qkv / dqkv (the forward's choice: same config copy, same inputs)
-  // fp16 engine: activation gradients travel multiplied by the loss scale S (gs = {S, 1/S} on the device); the kernels that
-  // accumulate into `grads` multiply by 1/S, so `grads` holds true gradients (simx.h "gradient scale")
-  const float* gs = dt == SIMX_F16 ? c->grad_scale : nullptr;
-  // fp32 engine: dgrad / wgrad GEMMs from bf16 hi + lo splits (gradients need f32's exponent range; simx.h SIMX_F32_SPLIT_B)
-  const int gdb = (dt == SIMX_F32 && c->f32_gemm == 0) ? SIMX_F32_SPLIT_B : dt;
+  const Ctx cx = make_ctx(stream, c, params, grads, wcache, cu, nseq, T, max_len, act, 1);
+  const Scratch s = walk_scratch(c, scratch, T, nseq);
+  SIMX_REQUIRE(act_bytes >= cx.A.bytes, SIMX_ERR_WORKSPACE, "bert_bwd: activation buffer too small");
+  SIMX_REQUIRE(scratch_bytes >= s.bytes, SIMX_ERR_WORKSPACE, "bert_bwd: scratch %zu < %zu", scratch_bytes, s.bytes);
+  const int H = c->hidden, dt = c->dtype;
+  const bool pl = pl_run(c, cx.Tp, max_len);
 
+  // the gradient w.r.t. the last hidden state -> bufB (the [CLS]-only last layer takes dcls itself)
   int l_top = layer_hi;
   if (top && c->cls_only_last_layer) {
-    // mirror of the forward's [CLS]-only last layer: everything up to the attention core runs on nseq rows
-    const int l = l_top;
-    const WLayer w = wlayer(c, params, wcache, l);
-    const char* xin = layer_input(c, act, Tp, l);
-    const ALayer a = ckpt ? alayer_recompute(c, act, Tp) : alayer(c, act, Tp, l, 1);
-    if (ckpt) RUN(layer_fwd((hipStream_t)stream, c, params, wcache, l, xin, layer_input_lo(c, act, Tp, l), layer_input_pl(c, act, Tp, l), a, act_extra(c, act, Tp, 1), cu, nseq, T, Tp, max_len, 1, true, nullptr));
-    const simx_dropout d1 = drop_of(c, l, 1), d2 = drop_of(c, l, 2), d3 = drop_of(c, l, 3);
-    char* dzm = hd ? bufC : bufA;
-    char* e0 = tnws + tnws_bytes;                        // three [nseq,H] temporaries
-    char* e1 = e0 + al((size_t)nseq * H * e);
-    char* e2 = e1 + al((size_t)nseq * H * e);
-    const char* qc = act_extra(c, act, Tp, 1);                                     // saved by the forward
-    const char* ctxc = qc + al((size_t)nseq * H * e);
-    RUN(simx_rows_copy_gs(stream, SIMX_F32, dt, nseq, H, nullptr, nullptr, dcls, bufB, gs));
-    const bool slc = stream_lo(c);                           // (the compact rows kept by the forward: see layer_fwd)
-    const char* xg = ctxc + 2 * al((size_t)nseq * H * e);
-    const char* xgl = xg + al((size_t)nseq * H * e);
-    RUN(simx_ln_bwd_res(stream, dt, nseq, H, a.z2, slc ? a.x1 : nullptr, slc ? a.x1l : nullptr, off(l, SIMX_P_LN2_G), c->eps, bufB, bufA,
-                        hd ? bufC : nullptr, goff(l, SIMX_P_LN2_G), goff(l, SIMX_P_LN2_B), goff(l, SIMX_P_B2), &d2, cu, gs));
-    RUN(simx_gemm_nt(stream, gdb, nseq, F, H, dzm, H, w.w2T, H, du, F, nullptr, nullptr, 0, SIMX_EPI_DGELU, a.u, F, nullptr, 0));
-    RUN(simx_gemm_tn_gs(stream, gdb, H, F, nseq, dzm, H, a.h, F, goff(l, SIMX_P_W2), F, 1, tnws, tnws_bytes, nullptr, 0, gs));
-    RUN(simx_gemm_nt(stream, gdb, nseq, H, F, du, F, w.w1T, F, bufB, H, nullptr, bufA, H, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
-    RUN(simx_gemm_tn_gs(stream, gdb, F, H, nseq, du, F, a.x1, H, goff(l, SIMX_P_W1), H, 1, tnws, tnws_bytes, goff(l, SIMX_P_B1), 0, gs));
-    RUN(simx_ln_bwd_res(stream, dt, nseq, H, a.z1, slc ? xg : nullptr, slc ? xgl : nullptr, off(l, SIMX_P_LN1_G), c->eps, bufB, bufA,
-                        hd ? bufC : nullptr, goff(l, SIMX_P_LN1_G), goff(l, SIMX_P_LN1_B), goff(l, SIMX_P_BO), &d1, cu, gs));
-    // e1 = dctx (gradient of the attention context, [CLS] rows), bufA[0:nseq] = gradient of the residual branch
-    RUN(simx_gemm_nt(stream, gdb, nseq, H, H, dzm, H, w.woT, H, e1, H, nullptr, nullptr, 0, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
-    RUN(simx_gemm_tn_gs(stream, gdb, H, H, nseq, dzm, H, ctxc, H, goff(l, SIMX_P_WO), H, 1, tnws, tnws_bytes, nullptr, 0, gs));
-    // attention core for the one query per sequence: e0 = dq [nseq,H]; dK, dV for every token -> dqkv[:, H:3H]
-    RUN(simx_mha_cls_bwd_hm(stream, dt, nseq, c->heads, d, cu, max_len, T, qc, a.qkv, e1, e0, dqkv, &d3, hm));
-    // Q projection ([CLS] rows): dWq, dbq, and dx = dq . Wq + (residual-branch gradient), still compact
-    RUN(simx_rows_copy(stream, dt, dt, nseq, H, cu, nullptr, xin, e2));
-    RUN(simx_gemm_tn_gs(stream, gdb, H, H, nseq, e0, H, e2, H, goff(l, SIMX_P_WQKV), H, 1, tnws, tnws_bytes, goff(l, SIMX_P_BQKV), 0, gs));
-    RUN(simx_gemm_nt(stream, gdb, nseq, H, H, e0, H, w.wqkvT, 3 * H, e1, H, nullptr, bufA, H, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
-    // back to full tensors: that gradient is zero outside the [CLS] rows
-    if (hipMemsetAsync(bufA, 0, (size_t)T * H * e, (hipStream_t)stream) != hipSuccess) {
-      simx_set_error("bert_bwd: memset failed");
-      return SIMX_ERR_HIP;
-    }
-    RUN(simx_rows_copy(stream, dt, dt, nseq, H, nullptr, cu, e1, bufA));
-    // K, V projections (every token): dx += dkv . Wkv ; dWkv, dbkv
-    if (hm) {
-      const char* dkv = dqkv + (size_t)c->heads * hm * 64 * e;                  // planes [heads, 3*heads)
-      RUN(simx_gemm_nt_hm(stream, dt, Tp, H, 2 * H, dkv, 64, w.wqkvT + (size_t)H * e, 3 * H, bufB, H, nullptr, bufA, H, nullptr, hm, 0));
-      RUN(simx_gemm_tn_gs(stream, gdb, 2 * H, H, T, dkv, 0, xin, H, goff(l, SIMX_P_WQKV) + (size_t)H * H, H, 1, tnws, tnws_bytes,
-                          goff(l, SIMX_P_BQKV) + H, hm, gs));
-    } else {
-      RUN(simx_gemm_nt(stream, gdb, Tp, H, 2 * H, dqkv + (size_t)H * e, 3 * H, w.wqkvT + (size_t)H * e, 3 * H, bufB, H, nullptr, bufA, H,
-                       SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
-      RUN(simx_gemm_tn_gs(stream, gdb, 2 * H, H, T, dqkv + (size_t)H * e, 3 * H, xin, H, goff(l, SIMX_P_WQKV) + (size_t)H * H, H, 1, tnws, tnws_bytes, goff(l, SIMX_P_BQKV) + H, 0, gs));
-    }
-    --l_top;
+    RUN(layer_bwd_cls(cx, s, l_top--, dcls));
   } else if (top && dhidden) {
-    if (hipMemcpyAsync(bufB, dhidden, (size_t)T * H * e, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+    if (hipMemcpyAsync(s.bufB, dhidden, (size_t)T * H * esz(dt), hipMemcpyDeviceToDevice, cx.stream) != hipSuccess) {
       simx_set_error("bert_bwd: copy of the hidden-state gradient failed");
       return SIMX_ERR_HIP;
     }
   } else if (top) {
-    RUN(simx_cls_scatter_gs(stream, dt, nseq, H, T, cu, dcls, bufB, gs));            // g_x = d(loss)/d(last hidden)
+    RUN(simx_cls_scatter_gs(stream, dt, nseq, H, T, cu, dcls, s.bufB, cx.gs));            // g_x = d(loss)/d(last hidden)
   }
-  for (int l = l_top; l >= layer_lo; --l) {
-    const WLayer w = wlayer(c, params, wcache, l);
-    const char* xin = layer_input(c, act, Tp, l);
-    const ALayer a = ckpt ? alayer_recompute(c, act, Tp) : alayer(c, act, Tp, l, 1);
-    const char* xinl = layer_input_lo(c, act, Tp, l);
-    const bool sl = stream_lo(c);
-    if (ckpt) RUN(layer_fwd((hipStream_t)stream, c, params, wcache, l, xin, xinl, layer_input_pl(c, act, Tp, l), a, nullptr, cu, nseq, T, Tp, max_len, 1, false, nullptr));
-    const simx_dropout d1 = drop_of(c, l, 1), d2 = drop_of(c, l, 2), d3 = drop_of(c, l, 3);
-    if (pl) {
-      // fp32 engine on operand planes (see layer_fwd): gradients that feed a GEMM leave their producer as bf16 plane pairs --
-      // bufC = dz (x dropout mask) from the LayerNorm backward, du from the DGELU epilogue, dqkv from the attention backward;
-      // the activation operand of each wgrad GEMM is converted to a bf16 pair into xconv right before its use
-      const long psH = (long)Tp * H, psF = (long)Tp * F, ps3 = (long)Tp * 3 * H;
-      RUN(simx_ln_bwd_planes(stream, T, H, (const float*)a.z2, off(l, SIMX_P_LN2_G), c->eps, (const float*)bufB, (float*)bufA, bufC, psH,
-                             goff(l, SIMX_P_LN2_G), goff(l, SIMX_P_LN2_B), goff(l, SIMX_P_B2), &d2));
-      // (the bias gradient of B1 = column sums of du comes out of this epilogue, so the W1 wgrad runs on the four-plane-stage
-      // kernel, which carries no fused bias pass; the deterministic mode keeps the wgrad kernel's ordered pass)
-      const bool b1_here = !simx_det();
-      RUN(simx_gemm_nt_planes_cs(stream, SIMX_BF16, SIMX_EPI_DGELU, Tp, F, H, bufC, H, psH, w.w2TP, H, (long)F * H, nullptr, F, nullptr,
-                                 (const float*)a.u, F, du, F, psF, nullptr, b1_here ? goff(l, SIMX_P_B1) : nullptr, T));
-      RUN(simx_planes_from(stream, SIMX_F16, SIMX_BF16, T, F, a.h, F, psF, xconv, F, psF));
-      RUN(simx_gemm_tn_planes(stream, H, F, T, bufC, H, psH, xconv, F, psF, goff(l, SIMX_P_W2), F, 1, tnws, tnws_bytes, nullptr));
-      RUN(simx_gemm_nt_planes(stream, SIMX_BF16, SIMX_EPI_NONE, Tp, H, F, du, F, psF, w.w1TP, F, (long)H * F, (float*)bufB, H, nullptr,
-                              (const float*)bufA, H, nullptr, 0, 0, nullptr));
-      RUN(simx_planes_from(stream, SIMX_F32, SIMX_BF16, T, H, a.x1, H, 0, xconv, H, psH));
-      RUN(simx_gemm_tn_planes(stream, F, H, T, du, F, psF, xconv, H, psH, goff(l, SIMX_P_W1), H, 1, tnws, tnws_bytes,
-                              b1_here ? nullptr : goff(l, SIMX_P_B1)));
-      RUN(simx_ln_bwd_planes(stream, T, H, (const float*)a.z1, off(l, SIMX_P_LN1_G), c->eps, (const float*)bufB, (float*)bufA, bufC, psH,
-                             goff(l, SIMX_P_LN1_G), goff(l, SIMX_P_LN1_B), goff(l, SIMX_P_BO), &d1));
-      RUN(simx_gemm_nt_planes(stream, SIMX_BF16, SIMX_EPI_NONE, Tp, H, H, bufC, H, psH, w.woTP, H, (long)H * H, (float*)bufB, H, nullptr, nullptr, 0,
-                              nullptr, 0, 0, nullptr));
-      RUN(simx_planes_from(stream, SIMX_F16, SIMX_BF16, T, H, a.ctx, H, psH, xconv, H, psH));
-      RUN(simx_gemm_tn_planes(stream, H, H, T, bufC, H, psH, xconv, H, psH, goff(l, SIMX_P_WO), H, 1, tnws, tnws_bytes, nullptr));
-      // (x3 attention: the QKV bias gradient = column sums of dq | dk | dv comes out of the attention backward, so the Wqkv wgrad
-      // runs on the four-plane-stage kernel too; the deterministic mode keeps the wgrad kernel's ordered pass)
-      const bool bqkv_here = simx_mha_x3_ok(d, max_len) && !simx_det();
-      if (simx_mha_x3_ok(d, max_len))
-        RUN(simx_mha_bwd_x3_bias(stream, nseq, c->heads, d, cu, max_len, T, a.qkv, ps3, a.ctx, psH, a.lse, (const float*)bufB, dqkv, ps3, &d3,
-                                 bqkv_here ? goff(l, SIMX_P_BQKV) : nullptr));
-      else
-        RUN(simx_mha_bwd_planes(stream, nseq, c->heads, d, cu, max_len, T, (const float*)a.qkv, a.ctx, psH, a.lse, (const float*)bufB, dqkv, ps3, &d3));
-      RUN(simx_gemm_nt_planes(stream, SIMX_BF16, SIMX_EPI_NONE, Tp, H, 3 * H, dqkv, 3 * H, ps3, w.wqkvTP, 3 * H, 3L * H * H, (float*)bufB, H, nullptr,
-                              (const float*)bufA, H, nullptr, 0, 0, nullptr));
-      RUN(simx_planes_from(stream, SIMX_F32, SIMX_BF16, T, H, xin, H, 0, xconv, H, psH));
-      RUN(simx_gemm_tn_planes(stream, 3 * H, H, T, dqkv, 3 * H, ps3, xconv, H, psH, goff(l, SIMX_P_WQKV), H, 1, tnws, tnws_bytes,
-                              bqkv_here ? nullptr : goff(l, SIMX_P_BQKV)));
-      continue;
-    }
-    char* dzm = hd ? bufC : bufA;        // gradient of the (dropped) dense output; bufA = gradient of the residual branch
-    // output LayerNorm : dz2, dgamma2, dbeta2, db2
-    RUN(simx_ln_bwd_res(stream, dt, T, H, a.z2, sl ? a.x1 : nullptr, sl ? a.x1l : nullptr, off(l, SIMX_P_LN2_G), c->eps, bufB, bufA,
-                        hd ? bufC : nullptr, goff(l, SIMX_P_LN2_G), goff(l, SIMX_P_LN2_B), goff(l, SIMX_P_B2), &d2, nullptr, gs));
-    // du = (dz2m . W2) * gelu'(u)
-    RUN(simx_gemm_nt(stream, gdb, Tp, F, H, dzm, H, w.w2T, H, du, F, nullptr, nullptr, 0, SIMX_EPI_DGELU, a.u, F, nullptr, 0));
-    RUN(simx_gemm_tn_gs(stream, gdb, H, F, T, dzm, H, a.h, F, goff(l, SIMX_P_W2), F, 1, tnws, tnws_bytes, nullptr, 0, gs));
-    // dx1 = du . W1 + dz2
-    RUN(simx_gemm_nt(stream, gdb, Tp, H, F, du, F, w.w1T, F, bufB, H, nullptr, bufA, H, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
-    RUN(simx_gemm_tn_gs(stream, gdb, F, H, T, du, F, a.x1, H, goff(l, SIMX_P_W1), H, 1, tnws, tnws_bytes, goff(l, SIMX_P_B1), 0, gs));
-    // attention-output LayerNorm : dz1, dgamma1, dbeta1, dbo
-    RUN(simx_ln_bwd_res(stream, dt, T, H, a.z1, sl ? xin : nullptr, sl ? xinl : nullptr, off(l, SIMX_P_LN1_G), c->eps, bufB, bufA,
-                        hd ? bufC : nullptr, goff(l, SIMX_P_LN1_G), goff(l, SIMX_P_LN1_B), goff(l, SIMX_P_BO), &d1, nullptr, gs));
-    // dctx = dz1m . Wo
-    RUN(simx_gemm_nt(stream, gdb, Tp, H, H, dzm, H, w.woT, H, bufB, H, nullptr, nullptr, 0, SIMX_EPI_NONE, nullptr, 0, nullptr, 0));
-    RUN(simx_gemm_tn_gs(stream, gdb, H, H, T, dzm, H, a.ctx, H, goff(l, SIMX_P_WO), H, 1, tnws, tnws_bytes, nullptr, 0, gs));
-    RUN(simx_mha_bwd_hm(stream, dt, nseq, c->heads, d, cu, max_len, T, a.qkv, a.ctx, a.lse, bufB, dqkv, &d3, hm));
-    // dx = dqkv . Wqkv + dz1
-    if (hm) {
-      RUN(simx_gemm_nt_hm(stream, dt, Tp, H, 3 * H, dqkv, 64, w.wqkvT, 3 * H, bufB, H, nullptr, bufA, H, nullptr, hm, 0));
-      RUN(simx_gemm_tn_gs(stream, gdb, 3 * H, H, T, dqkv, 0, xin, H, goff(l, SIMX_P_WQKV), H, 1, tnws, tnws_bytes, goff(l, SIMX_P_BQKV), hm, gs));
-    } else {
-      RUN(simx_gemm_nt(stream, gdb, Tp, H, 3 * H, dqkv, 3 * H, w.wqkvT, 3 * H, bufB, H, nullptr, bufA, H, SIMX_EPI_NONE, nullptr, 0,
-                       nullptr, 0));
-      RUN(simx_gemm_tn_gs(stream, gdb, 3 * H, H, T, dqkv, 3 * H, xin, H, goff(l, SIMX_P_WQKV), H, 1, tnws, tnws_bytes,
-                          goff(l, SIMX_P_BQKV), 0, gs));
-    }
-  }
+  for (int l = l_top; l >= layer_lo; --l) RUN(pl ? layer_bwd_planes(cx, s, l) : layer_bwd_dense(cx, s, l));
   if (layer_lo > 0) return SIMX_OK;               // the next part continues from bufB
   const simx_dropout d0 = drop_of(c, -1, 0);
-  RUN(simx_embed_ln_bwd_seq_gs(stream, dt, nseq, max_len, T, H, cu, ids, pos_ids, off(-1, SIMX_P_WORD), off(-1, SIMX_P_POS),
-                               off(-1, SIMX_P_TYPE), off(-1, SIMX_P_EMB_LN_G), c->eps, bufB, goff(-1, SIMX_P_WORD),
-                               goff(-1, SIMX_P_POS), goff(-1, SIMX_P_TYPE), goff(-1, SIMX_P_EMB_LN_G), goff(-1, SIMX_P_EMB_LN_B), &d0, gs));
-  return SIMX_OK;
+  return simx_embed_ln_bwd_seq_gs(stream, dt, nseq, max_len, T, H, cu, ids, pos_ids, cx.p(-1, SIMX_P_WORD), cx.p(-1, SIMX_P_POS),
+                                  cx.p(-1, SIMX_P_TYPE), cx.p(-1, SIMX_P_EMB_LN_G), c->eps, s.bufB, cx.g(-1, SIMX_P_WORD),
+                                  cx.g(-1, SIMX_P_POS), cx.g(-1, SIMX_P_TYPE), cx.g(-1, SIMX_P_EMB_LN_G), cx.g(-1, SIMX_P_EMB_LN_B), &d0, cx.gs);
 }
-
-// ------------------------------------------------------------------------------------------ profiler
-#include <vector>
-#include "prof.h"
-namespace {
-struct ProfRec { int id; double work; hipEvent_t a, b; bool done; };
-bool g_prof_on = false;
-std::vector<ProfRec> g_prof;
-std::vector<hipEvent_t> g_pool;
-size_t g_pool_next = 0;
-}  // namespace
-
-int simx_prof_mark(int id, hipStream_t s, double work, int end_index) {
-  if (end_index < 0) {
-    if (!g_prof_on || g_pool_next + 2 > g_pool.size()) return -1;
-    ProfRec r{id, work, g_pool[g_pool_next], g_pool[g_pool_next + 1], false};
-    g_pool_next += 2;
-    (void)hipEventRecord(r.a, s);
-    g_prof.push_back(r);
-    return (int)g_prof.size() - 1;
-  }
-  if ((size_t)end_index < g_prof.size() && !g_prof[end_index].done) {      // (scopes nest: each closes its own record)
-    (void)hipEventRecord(g_prof[end_index].b, s);
-    g_prof[end_index].done = true;
-  }
-  return end_index;
-}
-
-void simx_prof_retag(int id) {
-  if (!g_prof_on) return;
-  for (size_t i = g_prof.size(); i-- > 0;)
-    if (!g_prof[i].done) { g_prof[i].id = id; return; }
-}
-
-extern "C" int simx_prof_begin(int max_launches) {
-  while ((int)g_pool.size() < 2 * max_launches) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) { simx_set_error("prof_begin: hipEventCreate failed"); return SIMX_ERR_HIP; }
-    g_pool.push_back(e);
-  }
-  g_prof.clear();
-  g_pool_next = 0;
-  g_prof_on = true;
-  return SIMX_OK;
-}
-
-// Stops recording, waits for the recorded events and aggregates per kernel class:
-// counts[k], total_ms[k], total_work[k] for k < SIMX_K_COUNT (host arrays).
-extern "C" int simx_prof_end(int32_t* counts_host, double* total_ms_host, double* total_work_host) {
-  g_prof_on = false;
-  for (int k = 0; k < SIMX_K_COUNT; ++k) { counts_host[k] = 0; total_ms_host[k] = 0; total_work_host[k] = 0; }
-  for (auto& r : g_prof) {
-    if (!r.done) continue;
-    if (hipEventSynchronize(r.b) != hipSuccess) continue;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) continue;
-    counts_host[r.id] += 1;
-    total_ms_host[r.id] += ms;
-    total_work_host[r.id] += r.work;
-  }
-  g_prof.clear();
-  (void)hipGetLastError();      // a failed event query must not surface as the next launch's error
-  return SIMX_OK;
-}
-extern "C" int simx_prof_kernel_count(void) { return SIMX_K_COUNT; }

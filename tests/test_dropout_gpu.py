@@ -113,3 +113,69 @@ def test_large_gemm_epilogue_dropout(dev):
     ref = (r(dA) @ r(dB).T + bias) * mult + r(dres)
     err = np.abs(r(out) - ref)
     assert (err <= 2e-2 + 1.2e-2 * np.abs(ref)).all()
+
+
+def _tiny_p_worker(dtype, out_path):
+    """One process (SIMX_DETERMINISTIC is read once per process): an encoder forward + backward through the C ABI for
+    hidden_dropout = 0 and for 0.001, on buffers this test owns; the backward scratch is filled with NaN bit patterns before each
+    backward.  Writes the two gradient buffers to out_path."""
+    from simxns_amd import _lib as L
+    lib = L.load()
+    assert lib.simx_deterministic() == 1
+    dev = torch.device("cuda:0")
+    cfg = L.BertCfg({"fp16": L.SIMX_F16, "bf16": L.SIMX_BF16, "fp32": L.SIMX_F32}[dtype], 2, 256, 4, 1024, 300, 64, 2, 1e-12)
+    cfg.cls_only_last_layer = 1          # layer 1 runs the [CLS]-only backward, layer 0 the full one
+    cfg.stream_lo = 1 if dtype == "fp16" else 0
+    cfg.dropout_seed = 4321
+    ref = C.byref(cfg)
+    lens = [48, 17, 33, 5, 48, 26, 40]
+    nseq, T, max_len = len(lens), sum(lens), max(lens)
+    g = torch.Generator().manual_seed(0)
+    n = int(lib.simx_bert_param_count(ref))
+    params = (torch.randn(n, generator=g) * 0.08).to(dev)
+    for layer, kinds in [(-1, (L.P_EMB_LN_G,))] + [(l, (L.P_LN1_G, L.P_LN2_G)) for l in range(2)]:
+        for k in kinds:
+            o = int(lib.simx_bert_param_offset(ref, layer, k))
+            params[o:o + 256] += 1.0
+    ids = torch.randint(1, 300, (T,), generator=g).to(torch.int32).to(dev)
+    pos = torch.cat([torch.arange(m) for m in lens]).to(torch.int32).to(dev)
+    cu = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device=dev)
+    dcls = torch.randn(nseq, 256, generator=g).to(dev)
+    wcache = torch.empty(int(lib.simx_bert_wcache_bytes(ref)), dtype=torch.uint8, device=dev)
+    L.call("simx_bert_cast_weights", L.stream_ptr(), ref, L.ptr(params), L.ptr(wcache))
+    act = torch.empty(int(lib.simx_bert_act_bytes(ref, T, nseq, 1)), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(int(lib.simx_bert_bwd_scratch_bytes(ref, T, nseq)), dtype=torch.uint8, device=dev)
+    out = {}
+    for p in (0.0, 0.001):
+        cfg.hidden_dropout = p
+        cls = torch.empty(nseq, 256, device=dev)
+        grads = torch.zeros(n, device=dev)
+        L.call("simx_bert_fwd", L.stream_ptr(), ref, L.ptr(params), L.ptr(wcache), L.ptr(ids), L.ptr(pos), L.ptr(cu), nseq, T, max_len,
+               L.ptr(act), act.numel(), 1, L.ptr(cls), None)
+        scratch.fill_(0xFF)              # NaN in fp16, bf16 and f32
+        L.call("simx_bert_bwd", L.stream_ptr(), ref, L.ptr(params), L.ptr(wcache), L.ptr(ids), L.ptr(pos), L.ptr(cu), nseq, T, max_len,
+               L.ptr(act), act.numel(), L.ptr(dcls), L.ptr(grads), L.ptr(scratch), scratch.numel())
+        torch.cuda.synchronize()
+        out["p%g" % p] = grads.cpu().numpy()
+    np.savez(out_path, **out)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16", "fp32"])
+def test_hidden_dropout_below_one_step_is_no_dropout(tmp_path, dtype):
+    """0 < p < 1/512 is realised as NO dropout (threshold 0): the LayerNorm backward then writes no masked copy of dz, and the
+    dgrad / wgrad GEMMs must read dz itself -- not the (unwritten) masked buffer.  Parameter gradients for hidden_dropout = 0.001
+    are bit-identical to those for 0, with the backward scratch pre-filled with NaNs and ordered sums (SIMX_DETERMINISTIC=1)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "grads.npz")
+    env = dict(os.environ, SIMX_DETERMINISTIC="1")
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    code = "import sys; sys.path.insert(0, %r); from tests.test_dropout_gpu import _tiny_p_worker; _tiny_p_worker(%r, %r)" % (root, dtype, out)
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    z = np.load(out)
+    g0, g1 = z["p0"], z["p0.001"]
+    assert np.isfinite(g0).all() and np.abs(g0).max() > 0
+    assert g0.tobytes() == g1.tobytes(), "max |diff| %r, non-finite %d" % (np.nanmax(np.abs(g1 - g0)), int((~np.isfinite(g1)).sum()))

@@ -584,3 +584,77 @@ def test_no_spills_on_the_hot_path():
     assert len(ks) > 250 and "gemm_nt_p3_kernel" in names and "mha_bwd_long_kernel" in names and "gemm_tn_xq_kernel" in names
     assert check_isa.offenders(ks) == []
     assert not check_isa.ALLOW                      # nothing is exempt today; an entry needs a reason next to it
+
+
+# simx_bert_wcache_bytes, simx_bert_act_bytes (save 0, save 1), simx_bert_bwd_scratch_bytes per
+# (engine, geometry, grad_checkpoint, T, nseq).  Recorded from a build of the commit BEFORE the encoder's buffer layouts moved to
+# one walk per buffer (without a device: workspace queries plan for 256 CUs), never from the tree under test: the layouts
+# (and with them every sub-buffer's offset) are pinned to that commit.
+_PARENT_SIZES = {
+    ("fp32_planes", "base", 0, 262144, 2048): (1019215872, 30658265088, 175739240448, 11359223808),
+    ("fp32_planes", "base", 0, 4096, 128): (1019215872, 417595392, 2432827392, 193069056),
+    ("fp32_planes", "base", 0, 1000, 7): (1019215872, 104014848, 607822848, 50396160),
+    ("fp32_planes", "base", 1, 262144, 2048): (1019215872, 30658265088, 49985617920, 11359223808),
+    ("fp32_planes", "base", 1, 4096, 128): (1019215872, 417595392, 568590336, 193069056),
+    ("fp32_planes", "base", 1, 1000, 7): (1019215872, 104014848, 141763584, 50396160),
+    ("fp32_planes", "large", 0, 262144, 2048): (3623878656, 40877686784, 466448547840, 15124660224),
+    ("fp32_planes", "large", 0, 4096, 128): (3623878656, 556793856, 6468141056, 236453888),
+    ("fp32_planes", "large", 0, 1000, 7): (3623878656, 138686464, 1616523264, 75583488),
+    ("fp32_planes", "large", 1, 262144, 2048): (3623878656, 40877686784, 92417294336, 15124660224),
+    ("fp32_planes", "large", 1, 4096, 128): (3623878656, 556793856, 959447040, 236453888),
+    ("fp32_planes", "large", 1, 1000, 7): (3623878656, 138686464, 239349760, 75583488),
+    ("fp32_exact", "base", 0, 262144, 2048): (339738624, 26631733248, 155606581248, 8137998336),
+    ("fp32_exact", "base", 0, 4096, 128): (339738624, 417595392, 2432827392, 193069056),
+    ("fp32_exact", "base", 0, 1000, 7): (339738624, 104014848, 607822848, 50396160),
+    ("fp32_exact", "base", 1, 262144, 2048): (339738624, 26631733248, 36295409664, 8137998336),
+    ("fp32_exact", "base", 1, 4096, 128): (339738624, 417595392, 568590336, 193069056),
+    ("fp32_exact", "base", 1, 1000, 7): (339738624, 104014848, 141763584, 50396160),
+    ("fp32_exact", "large", 0, 262144, 2048): (1207959552, 35508977664, 413835198464, 10829692928),
+    ("fp32_exact", "large", 0, 4096, 128): (1207959552, 556793856, 6468141056, 236453888),
+    ("fp32_exact", "large", 0, 1000, 7): (1207959552, 138686464, 1616523264, 75583488),
+    ("fp32_exact", "large", 1, 262144, 2048): (1207959552, 35508977664, 61278781440, 10829692928),
+    ("fp32_exact", "large", 1, 4096, 128): (1207959552, 556793856, 959447040, 236453888),
+    ("fp32_exact", "large", 1, 1000, 7): (1207959552, 138686464, 239349760, 75583488),
+    ("bf16", "base", 0, 262144, 2048): (339738624, 13328449536, 77878788096, 4102029312),
+    ("bf16", "base", 0, 4096, 128): (339738624, 208994304, 1217593344, 129564672),
+    ("bf16", "base", 0, 1000, 7): (339738624, 52056576, 304206336, 34635264),
+    ("bf16", "base", 1, 262144, 2048): (339738624, 13328449536, 18160287744, 4102029312),
+    ("bf16", "base", 1, 4096, 128): (339738624, 208994304, 284491776, 129564672),
+    ("bf16", "base", 1, 1000, 7): (339738624, 52056576, 70930944, 34635264),
+    ("bf16", "large", 0, 262144, 2048): (1207959552, 17771266048, 207118925824, 5448400896),
+    ("bf16", "large", 0, 4096, 128): (1207959552, 278659072, 3237216256, 151781376),
+    ("bf16", "large", 0, 1000, 7): (1207959552, 69408768, 809048064, 54568960),
+    ("bf16", "large", 1, 262144, 2048): (1207959552, 17771266048, 30656167936, 5448400896),
+    ("bf16", "large", 1, 4096, 128): (1207959552, 278659072, 479985664, 151781376),
+    ("bf16", "large", 1, 1000, 7): (1207959552, 69408768, 119740416, 54568960),
+    ("fp16_stream_lo", "base", 0, 262144, 2048): (339738624, 14335082496, 82911952896, 4102029312),
+    ("fp16_stream_lo", "base", 0, 4096, 128): (339738624, 224722944, 1296236544, 129564672),
+    ("fp16_stream_lo", "base", 0, 1000, 7): (339738624, 55988736, 323867136, 34635264),
+    ("fp16_stream_lo", "base", 1, 262144, 2048): (339738624, 14335082496, 21582839808, 4102029312),
+    ("fp16_stream_lo", "base", 1, 4096, 128): (339738624, 224722944, 337969152, 129564672),
+    ("fp16_stream_lo", "base", 1, 1000, 7): (339738624, 55988736, 84300288, 34635264),
+    ("fp16_stream_lo", "large", 0, 262144, 2048): (1207959552, 19113443328, 220272263168, 5448400896),
+    ("fp16_stream_lo", "large", 0, 4096, 128): (1207959552, 299630592, 3442737152, 151781376),
+    ("fp16_stream_lo", "large", 0, 1000, 7): (1207959552, 74651648, 860428288, 54568960),
+    ("fp16_stream_lo", "large", 1, 262144, 2048): (1207959552, 19113443328, 38440796160, 5448400896),
+    ("fp16_stream_lo", "large", 1, 4096, 128): (1207959552, 299630592, 601620480, 151781376),
+    ("fp16_stream_lo", "large", 1, 1000, 7): (1207959552, 74651648, 150149120, 54568960),
+}
+_SIZE_ENGINES = {"fp32_planes": (0, 0, 0), "fp32_exact": (0, 1, 0), "bf16": (1, 0, 0), "fp16_stream_lo": (2, 0, 1)}   # dtype, f32_gemm, stream_lo
+_SIZE_GEOMETRY = {"base": (12, 768, 12, 3072), "large": (24, 1024, 16, 4096)}
+
+
+def test_buffer_sizes_pinned_to_parent_layout():
+    L = _lib()
+    lib = L.load()
+    assert len(_PARENT_SIZES) == 48
+    assert lib.simx_set_compute_cus(0) == 0              # every CU: the wgrad workspace plans follow the CU budget
+    for (eng, arch, ckpt, T, nseq), want in sorted(_PARENT_SIZES.items()):
+        dtype, f32_gemm, stream_lo = _SIZE_ENGINES[eng]
+        layers, hidden, heads, inter = _SIZE_GEOMETRY[arch]
+        cfg = L.BertCfg(dtype, layers, hidden, heads, inter, 30522, 512, 2, 1e-12)
+        cfg.grad_checkpoint, cfg.f32_gemm, cfg.stream_lo, cfg.cls_only_last_layer = ckpt, f32_gemm, stream_lo, 1
+        p = C.byref(cfg)
+        got = (lib.simx_bert_wcache_bytes(p), lib.simx_bert_act_bytes(p, T, nseq, 0), lib.simx_bert_act_bytes(p, T, nseq, 1),
+               lib.simx_bert_bwd_scratch_bytes(p, T, nseq))
+        assert got == want, (eng, arch, ckpt, T, nseq, got, want)
