@@ -406,13 +406,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h16_v5_kernel(
     V3_PIN8("s_waitcnt lgkmcnt(0)", al0, al1, al2, al3, bx0, bx1, bx2, bx3);
   }
 
-#define V3_MFMA_ROW(I, AF, B0, B1, B2, B3)                                                     \
-  acc[I][0] = H16<F>::mfma(B0, AF, acc[I][0]);             \
-  acc[I][1] = H16<F>::mfma(B1, AF, acc[I][1]);             \
-  acc[I][2] = H16<F>::mfma(B2, AF, acc[I][2]);             \
-  acc[I][3] = H16<F>::mfma(B3, AF, acc[I][3])
-#define V3_RD1(F, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=&v"(F) : "v"(ADDR) : "memory")
-#define V3_SB __builtin_amdgcn_sched_barrier(0)
   // one k-step: CUR = this k-step's A-high address, NA/NB = next k-step's A-low / B addresses; SYNC: stage boundary
 #define V5_STEP(CURA, NA, NB, BC0, BC1, BC2, BC3, BN0, BN1, BN2, BN3, SYNC, ST)                  \
   do {                                                                                         \
@@ -446,9 +439,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_h16_v5_kernel(
     V5_STEP(sc + oA1, sn + oA0, sn + oB0, by0, by1, by2, by3, bx0, bx1, bx2, bx3, true, st);
   }
 #undef V5_STEP
-#undef V3_RD1
-#undef V3_SB
-#undef V3_MFMA_ROW
 
   if (C == nullptr) return;                      // (main-loop-only measurement build, -DSIMX_MEASUREMENT_HOOKS)
   // ---- epilogue through LDS.  The memory path is REQUEST-bound (~1 request / 6 clk / CU, measured): the natural
@@ -574,15 +564,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p3_kernel(
   // (the counted vmcnt immediates of the DEEP_IN epilogue assume two stores per chunk and one input stream: EPI NONE / DGELU)
   static_assert(!(DEEP_IN && EPI == SIMX_EPI_GELU), "DEEP_IN epilogue: the vmcnt schedule has no room for the GELU pair's second store");
   const int hmR = ldc2;                           // rows of a plane (ldc2 is free: a plane-blocked C2 has pitch 64)
-  if (HM_A) lda = 64;                             // row pitch inside a plane; the stage's k offset selects the plane (P3_AK)
+  if (HM_A) lda = 64;                             // row pitch inside a plane; the stage's k offset selects the plane (P_AK)
   if (HM_I) ldin = 64;
   const uint32_t offA0 = (uint32_t)(lr * lda + ec0) * 2, offA1 = (uint32_t)(lr * lda + ec1) * 2;
   const uint32_t offB0 = (uint32_t)(lr * ldb + ec0) * 2, offB1 = (uint32_t)(lr * ldb + ec1) * 2;
   // element offset of K stage s of the A operand: s * 64 columns, or plane s of ldc2 rows x 64
-#define P3_AK(S) (HM_A ? (long)(S) * ((long)hmR * 64) : (long)(S) * 64)
-  // Epilogue-only per-lane constants are recomputed per tile from a laundered copy of the lane id (P_LANE): left to
-  // LICM they are hoisted out of the tile loop and stay live (~20 VGPRs) through the main loop, which then spills.
-#define P_LANE(L) int L = lane; asm volatile("" : "+v"(L))
+#define P_AK(S) (HM_A ? (long)(S) * ((long)hmR * 64) : (long)(S) * 64)
+#define P_BK(S) ((S) * 64)
 
   int v = blockIdx.x;
   // Tile order.  Default: the XCD-aware row-major order -- the tiles_n N-tiles of an M-panel run at the same time on neighbouring CUs of
@@ -598,84 +586,20 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p3_kernel(
   int m0, n0;
   P3_TILE(v, m0, n0);
   p3_half(B, ldb, n0, 0, ldsB, wave, offB0, offB1);
-  p3_half(A, lda, m0, P3_AK(0), lds0, wave, offA0, offA1);
+  p3_half(A, lda, m0, P_AK(0), lds0, wave, offA0, offA1);
   asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
   p3_half(B, ldb, n0, 64, ldsB + 32768u, wave, offB0, offB1);
-  p3_half(A, lda, m0, P3_AK(1), lds0 + 32768u, wave, offA0, offA1);
-  p3_half(A, lda, m0, P3_AK(2), lds0 + 65536u, wave, offA0, offA1);
+  p3_half(A, lda, m0, P_AK(1), lds0 + 32768u, wave, offA0, offA1);
+  p3_half(A, lda, m0, P_AK(2), lds0 + 65536u, wave, offA0, offA1);
   int a0 = 0, b0 = 0;                             // LDS slots of the current tile's stage 0 (A: mod 3, B: mod 2)
-  // the bias enters as the accumulators' initial value; bq* always hold the CURRENT tile's 4x4 bias columns at the
-  // top of the loop (the next tile's are requested at the last stage boundary and carried across the epilogue)
-  f32x4 bq0, bq1, bq2, bq3;
-  {
-    const float* b0 = bias ? bias + n0 + wc * 64 : reinterpret_cast<const float*>(A);
-    const uint32_t boff = (uint32_t)(fg * 16);
-    P_GLD4(bq0, boff, b0, 0); P_GLD4(bq1, boff, b0, 64); P_GLD4(bq2, boff, b0, 128); P_GLD4(bq3, boff, b0, 192);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(bq0), "+v"(bq1), "+v"(bq2), "+v"(bq3)::"memory");
-  }
+  f32x4 bq0, bq1, bq2, bq3;                     // the current tile's bias columns (p3.h, P_BIAS_FIRST)
+  P_BIAS_FIRST();
+  P_PENDING_DMA_STATE;
 
-#define V3_MFMA_ROW(I, AF, B0, B1, B2, B3)                                                     \
-  acc[I][0] = H16<F>::mfma(B0, AF, acc[I][0]);             \
-  acc[I][1] = H16<F>::mfma(B1, AF, acc[I][1]);             \
-  acc[I][2] = H16<F>::mfma(B2, AF, acc[I][2]);             \
-  acc[I][3] = H16<F>::mfma(B3, AF, acc[I][3])
-#define V3_RD1(F, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=&v"(F) : "v"(ADDR) : "memory")
-#define V3_SB __builtin_amdgcn_sched_barrier(0)
-  // (timing experiments that priced the waits of this loop -- no barrier, no vmcnt wait, no lgkmcnt waits, s_setprio around
-  // the MFMA bursts, all stores to one tile's rows -- are recorded in DESIGN.md 5 / 5b; the switches are not part of the product)
-#define P3_BOUNDARY_WAIT() asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory")
-#define P3_LGKM_WAIT "s_waitcnt lgkmcnt(0)"
-  // the 8 LDS-DMA instructions a mid-tile boundary issues go out ONE PER MFMA ROW (B in the rest of this k-step, A in the
-  // first half of the next), never as a burst right after the barrier (+5 %)
-  const char* pa_g = nullptr; const char* pb_g = nullptr;
-  uint32_t pa_slot = 0, pb_slot = 0;
-  bool pa_pend = false, pb_pend = false;
-#define P3_HA(J) do { if (pa_pend) { P_DMA16(((J) & 1) ? offA1 : offA0, pa_g + (long)(J) * 8 * lda * 2, pa_slot + (uint32_t)((J) * 1024)); if ((J) == 3) pa_pend = false; } } while (0)
-#define P3_HB(J) do { if (pb_pend) { P_DMA16(((J) & 1) ? offB1 : offB0, pb_g + (long)(J) * 8 * ldb * 2, pb_slot + (uint32_t)((J) * 1024)); if ((J) == 3) pb_pend = false; } } while (0)
-#define P3_HAX(ROW, S1) do { if ((ROW) < 4) P3_HA(ROW); } while (0)
-#define P_STEP(CURA, NA, NB, BC0, BC1, BC2, BC3, BN0, BN1, BN2, BN3, BOUNDARY, S1)               \
-  do {                                                                                         \
-    /* fragment reads are front-loaded: the last read before each pin is issued two MFMA rows ahead of it */ \
-    const uint32_t aa__ = (CURA), na__ = (NA), nb__ = (NB);                                    \
-    V3_SB; V3_MFMA_ROW(0, al0, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(ah0, aa__, 8192); V3_RD1(ah1, aa__, 10240); P3_HAX(0, S1); \
-    V3_SB; V3_MFMA_ROW(1, al1, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(ah2, aa__, 12288); V3_RD1(ah3, aa__, 14336); P3_HAX(1, S1); \
-    V3_SB; V3_MFMA_ROW(2, al2, BC0, BC1, BC2, BC3); V3_SB; P3_HAX(2, S1);                      \
-    V3_SB; V3_MFMA_ROW(3, al3, BC0, BC1, BC2, BC3); V3_SB; P3_HAX(3, S1);                      \
-    V3_SB;                                                                                     \
-    V3_PIN4(P3_LGKM_WAIT, ah0, ah1, ah2, ah3);                                       \
-    BOUNDARY();                                                                                \
-    V3_SB; V3_MFMA_ROW(4, ah0, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(al0, na__, 0); V3_RD1(BN0, nb__, 0); V3_RD1(al1, na__, 2048); P3_HB(1); P3_HAX(4, S1); \
-    V3_SB; V3_MFMA_ROW(5, ah1, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(BN1, nb__, 2048); V3_RD1(al2, na__, 4096); V3_RD1(BN2, nb__, 4096); P3_HB(2); P3_HAX(5, S1); \
-    V3_SB; V3_MFMA_ROW(6, ah2, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(al3, na__, 6144); V3_RD1(BN3, nb__, 6144); P3_HB(3); P3_HAX(6, S1); \
-    V3_SB; V3_MFMA_ROW(7, ah3, BC0, BC1, BC2, BC3);                                            \
-    V3_SB;                                                                                     \
-    V3_PIN8(P3_LGKM_WAIT, al0, al1, al2, al3, BN0, BN1, BN2, BN3);                   \
-  } while (0)
-#define P_BND_NONE() do { } while (0)
-  // stage boundary inside the tile: every fragment of stage st is in registers, stage st+1 has landed once vmcnt
-  // hits 0 (for everyone after the barrier); slot (st+par)&1 is refilled with stream stage st+2, which is the
-  // NEXT tile's stage 0 when st == nst-2
-#define P_BND_MID()                                                                            \
-  do {                                                                                         \
-    /* issue order so far: ... [B(st+1) A(st+2)] ; stage st+1 = everything but the 4 youngest (A(st+2)) */ \
-    P3_BOUNDARY_WAIT();                                                                        \
-    const bool cb__ = st + 2 < nst, ca__ = st + 3 < nst;                                       \
-    /* same issue ORDER as a burst would have (B x4, then A x4 -- the vmcnt(4) rule holds), one instruction per MFMA row */ \
-    pb_g = reinterpret_cast<const char*>(B + (long)((cb__ ? n0 : n0n) + wave * 32) * ldb + (cb__ ? st + 2 : st + 2 - nst) * 64); \
-    pb_slot = ldsB + (uint32_t)(bc * 32768 + wave * 4096);                                     \
-    pa_g = reinterpret_cast<const char*>(A + (long)((ca__ ? m0 : m0n) + wave * 32) * lda + P3_AK(ca__ ? st + 3 : st + 3 - nst)); \
-    pa_slot = lds0 + (uint32_t)(ac * 32768 + wave * 4096);                                     \
-    pb_pend = pa_pend = true;                                                                  \
-    P_DMA16(offB0, pb_g, pb_slot);                                                             \
-  } while (0)
-  // last boundary of the tile: bias and the first residual chunk are requested BEFORE the next tile's stage 1,
-  // so the epilogue can wait for them without waiting for that stage
+  // last boundary of the tile (head and tail: p3.h): between the next tile's bias and its B(1), the first residual chunk(s)
 #define P_BND_LAST()                                                                           \
   do {                                                                                         \
-    asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");                              \
-    P_LANE(lb__);                                                                              \
-    const uint32_t boff__ = (uint32_t)((lb__ >> 4) * 16);                                      \
-    P_GLD4(bq0, boff__, bptr, 0); P_GLD4(bq1, boff__, bptr, 64); P_GLD4(bq2, boff__, bptr, 128); P_GLD4(bq3, boff__, bptr, 192); \
+    P_BND_LAST_HEAD(bptr);                                                                     \
     if (HAS_IN) {                                                                              \
       const int lr__ = lb__ >> 3;                                                              \
       const uint32_t io0__ = (uint32_t)(lr__ * ldin + (((lb__ & 7) ^ (lb__ >> 4)) << 3)) * 2;  \
@@ -688,9 +612,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p3_kernel(
         P_DMA16(io0__, ibase + (long)96 * ldin, breg__ + 2048u); P_DMA16(io1__, ibase + (long)96 * ldin, breg__ + 3072u); \
       }                                                                                        \
     }                                                                                          \
-    /* next tile's stage 1 of B; its stage 2 of A goes into the slot this tile's epilogue borrows -> issued after it */ \
-    pb_g = reinterpret_cast<const char*>(B + (long)(n0n + wave * 32) * ldb + 64);              \
-    pb_slot = ldsB + (uint32_t)(bc * 32768 + wave * 4096);                                     \
+    P_BND_LAST_B1();                                                                           \
     if (!DEEP_IN) {                                                                            \
       pb_pend = true;                                                                          \
       P_DMA16(offB0, pb_g, pb_slot);                                                           \
@@ -707,41 +629,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p3_kernel(
     const char* ibase = !HAS_IN ? nullptr : reinterpret_cast<const char*>(HM_I ? in + ((long)(nw >> 6) * hmR + mw) * 64 : in + (long)mw * ldin + nw);   // uniform
 
     f32x4 acc[8][4];
-    {
-      f32x4 bi[4] = {bq0, bq1, bq2, bq3};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bi[j][e] = __uint_as_float(__float_as_uint(bi[j][e]) & bmask);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = bi[j];
-    }
+    P_ACC_INIT();
     bf16x8 al0, al1, al2, al3, ah0, ah1, ah2, ah3, bx0, bx1, bx2, bx3, by0, by1, by2, by3;
-    {
-      const uint32_t aa = lds0 + (uint32_t)(a0 * 32768) + oA0, ab = ldsB + (uint32_t)(b0 * 32768) + oB0;
-      V3_READ4(al0, al1, al2, al3, aa, 0, 2048, 4096, 6144);
-      V3_READ4(bx0, bx1, bx2, bx3, ab, 0, 2048, 4096, 6144);
-      V3_PIN8("s_waitcnt lgkmcnt(0)", al0, al1, al2, al3, bx0, bx1, bx2, bx3);
-    }
+    P_FIRST_FRAGS(lds0 + (uint32_t)(a0 * 32768) + oA0, ldsB + (uint32_t)(b0 * 32768) + oB0);
     int ac = a0, bc = b0;                         // slots of the stage being consumed
-    for (int st = 0; st < nst - 1; ++st) {
-      const int an = ac == 2 ? 0 : ac + 1, bn = bc ^ 1;
-      const uint32_t sa = lds0 + (uint32_t)(ac * 32768), sb = ldsB + (uint32_t)(bc * 32768);
-      const uint32_t na = lds0 + (uint32_t)(an * 32768), nb = ldsB + (uint32_t)(bn * 32768);
-      P_STEP(sa + oA0, sa + oA1, sb + oB1, bx0, bx1, bx2, bx3, by0, by1, by2, by3, P_BND_NONE, 1);
-      P_STEP(sa + oA1, na + oA0, nb + oB0, by0, by1, by2, by3, bx0, bx1, bx2, bx3, P_BND_MID, 0);
-      ac = an; bc = bn;
-    }
-    const uint32_t ereg = lds0 + (uint32_t)(ac * 32768 + wave * 4096);     // this wave's slice of the last stage's A slot
-    {
-      const int an = ac == 2 ? 0 : ac + 1, bn = bc ^ 1;
-      const uint32_t sa = lds0 + (uint32_t)(ac * 32768), sb = ldsB + (uint32_t)(bc * 32768);
-      const uint32_t na = lds0 + (uint32_t)(an * 32768), nb = ldsB + (uint32_t)(bn * 32768);
-      P_STEP(sa + oA0, sa + oA1, sb + oB1, bx0, bx1, bx2, bx3, by0, by1, by2, by3, P_BND_NONE, 1);
-      P_STEP(sa + oA1, na + oA0, nb + oB0, by0, by1, by2, by3, bx0, bx1, bx2, bx3, P_BND_LAST, 0);
-    }
+    uint32_t ereg;                                // this wave's slice of the last stage's A slot
+    P_TILE_STAGES(ereg);
 
     // ---- epilogue, 8 chunks of 16 rows (= accumulator row-block i), per wave, no barrier
     // (the bias registers are pinned here, BEFORE any branch: a branch between an asm load and its pin makes hipcc
@@ -933,29 +826,20 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p3_kernel(
     }
     // the borrowed A slot is free again (this wave's slice only ever holds this wave's rows): next tile's stage 2
     if (has_next) {                                // issued by the next tile's first four MFMA rows (same order: after B(1))
-      pa_g = reinterpret_cast<const char*>(A + (long)(m0n + wave * 32) * lda + P3_AK(2));
+      pa_g = reinterpret_cast<const char*>(A + (long)(m0n + wave * 32) * lda + P_AK(2));
       pa_slot = lds0 + (uint32_t)(ac * 32768 + wave * 4096);
       pa_pend = true;
     } else {
-      p3_half(A, lda, m0n, P3_AK(2), lds0 + (uint32_t)(ac * 32768), wave, offA0, offA1);
+      p3_half(A, lda, m0n, P_AK(2), lds0 + (uint32_t)(ac * 32768), wave, offA0, offA1);
     }
     if (!has_next) break;
     v = vn; m0 = m0n; n0 = n0n; a0 = ac == 2 ? 0 : ac + 1; b0 = bc ^ 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing (dummy) stage loads must land before the LDS is released
 #undef P3_TILE
-#undef P_LANE
-#undef P3_HA
-#undef P3_HAX
-#undef P3_HB
-#undef P3_AK
+#undef P_AK
+#undef P_BK
 #undef P_BND_LAST
-#undef P_BND_MID
-#undef P_BND_NONE
-#undef P_STEP
-#undef V3_RD1
-#undef V3_SB
-#undef V3_MFMA_ROW
 }
 
 
@@ -1068,20 +952,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_h16_kernel(
 
   float* o = out + (long)split * slab_stride;
   const float inv = gs_inv(gs);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wr * 64 + i * 16 + fs;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wc * 64 + j * 16 + fg * 4;
-      if (n >= N) continue;
-      float4* dst = reinterpret_cast<float4*>(o + (long)m * ldo + n);
-      float4 v = make_float4(acc[i][j][0] * inv, acc[i][j][1] * inv, acc[i][j][2] * inv, acc[i][j][3] * inv);
-      if (accumulate) { float4 c = *dst; v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w; }
-      *dst = v;
-    }
-  }
+#define TN_INV(X) ((X) * inv)
+  TN_STORE_TILES(4, o, m0 + wr * 64, n0 + wc * 64, TN_INV);
+#undef TN_INV
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1147,163 +1020,46 @@ __global__ __launch_bounds__(512, 2) void gemm_tn2_kernel(
   if (nst > 1) tn2_stage(A, lda, m0, M, B, ldb, n0, N, kb + 64, ke, smem + TN2_STAGE, wave, lane, hm_a);
 
   bf16x4 al_lo[4], al_hi[4], ah_lo[4], ah_hi[4], bx_lo[4], bx_hi[4], by_lo[4], by_hi[4];
-  // address of fragment (operand base, 16-col tile ct) for k-step base address `kbase` (stage + ks*32*512)
-#define TN2_ADDR_LO(KBASE, OP, CT) ((KBASE) + (OP) + row_lo + (uint32_t)((((CT)) ^ x_lo) << 5))
-#define TN2_ADDR_HI(KBASE, OP, CT) ((KBASE) + (OP) + row_hi + (uint32_t)((((CT)) ^ x_hi) << 5))
-#define TN2_FRAG(LO, HI) ((bf16x8){LO[0], LO[1], LO[2], LO[3], HI[0], HI[1], HI[2], HI[3]})
-#define TN2_MFMA_ROW(I, ALO, AHI, BLO, BHI)                                                                     \
+  // the main loop is p3.h's TN2_STEP (comments there); this kernel's part of it: where stream stage ST + 2 comes from, and what
+  // follows the barrier that ends stage ST
+#define TN2_ONE_A(ST, J) tn2_stage_one(A, hm_a > 0 ? 64 : lda, kb + ((ST) + 2) * 64, lds0 + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, J, oa[J])
+#define TN2_ONE_B(ST, J) tn2_stage_one(B, ldb, kb + ((ST) + 2) * 64, lds0 + 32768u + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, J, ob[J])
+#define TN2_BOUNDARY(ST, SPREAD)                                                                                \
   do {                                                                                                          \
-    const bf16x8 af__ = TN2_FRAG(ALO, AHI);                                                                     \
-    acc[I][0] = H16<F>::mfma(TN2_FRAG(BLO[0], BHI[0]), af__, acc[I][0]);    \
-    acc[I][1] = H16<F>::mfma(TN2_FRAG(BLO[1], BHI[1]), af__, acc[I][1]);    \
-    acc[I][2] = H16<F>::mfma(TN2_FRAG(BLO[2], BHI[2]), af__, acc[I][2]);    \
-    acc[I][3] = H16<F>::mfma(TN2_FRAG(BLO[3], BHI[3]), af__, acc[I][3]);    \
-    if (do_bias) {                                                                                              \
-      _Pragma("unroll") for (int e__ = 0; e__ < 4; ++e__)                                                       \
-          bsum[I] += H16<F>::one(ALO[e__]) + H16<F>::one(AHI[e__]);                                           \
-    }                                                                                                           \
-  } while (0)
-#define TN2_SB __builtin_amdgcn_sched_barrier(0)
-// (What bounds this loop was priced with timing-only variants, M = 262144 tokens, average of the four wgrad shapes: as shipped
-// 992 TFLOP/s; every stage re-reading stage 0 (all L2 hits) 1156; no operand loads at all 1445, 1614 on all-zero data.  So the
-// LDS-DMA stream itself costs the loop 20 % and the fabric / HBM misses another 14 %; an L2 prefetch of stage s+3 made it 5 %
-// SLOWER.  The 8 DMA instructions of a stage go out ONE PER MFMA ROW after the boundary: burst 1003, one (A,B) pair per row
-// 1056, one instruction per row 1080 TFLOP/s.)
-#define TN2_KSEL(S) (S)
-#define TN2_SPREAD 2
-#define TN2_PIECE(ST, J) tn2_stage_piece(A, hm_a > 0 ? 64 : lda, B, ldb, kb + TN2_KSEL((ST) + 2) * 64, lds0 + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, J, oa[J], ob[J])
-#define TN2_ONE_A(ST, J) tn2_stage_one(A, hm_a > 0 ? 64 : lda, kb + TN2_KSEL((ST) + 2) * 64, lds0 + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, J, oa[J])
-#define TN2_ONE_B(ST, J) tn2_stage_one(B, ldb, kb + TN2_KSEL((ST) + 2) * 64, lds0 + 32768u + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, J, ob[J])
-#define TN2_NOLOAD 0
-#define TN2_PIN8(TXT, X, Y) do { } while (0)     /* waits are hipcc's (counted lgkmcnt): the reads are builtins */
-
-  {
-    // A[0..3] and B of k-step 0: column tile index ct = (wave col offset)/16 + i
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      TN2_RD(al_lo[i], al_hi[i], TN2_ADDR_LO(lds0, 0u, wr * 8 + i), TN2_ADDR_HI(lds0, 0u, wr * 8 + i));
-      TN2_RD(bx_lo[i], bx_hi[i], TN2_ADDR_LO(lds0, 32768u, wc * 4 + i), TN2_ADDR_HI(lds0, 32768u, wc * 4 + i));
-    }
-    TN2_PIN8("s_waitcnt lgkmcnt(0)", al_lo, al_hi);
-    TN2_PIN8("s_waitcnt lgkmcnt(0)", bx_lo, bx_hi);
-  }
-
-  // one k-step (32 tokens): CUR = k-step base address, NXT = next k-step base address
-#define TN2_STEP(CUR, NXT, BCL, BCH, BNL, BNH, SYNC, ST)                                                        \
-  do {                                                                                                          \
-    const uint32_t cur__ = (CUR), nxt__ = (NXT);                                                                \
-    bool spread__ = false;                                                                                      \
-    const bool tail__ = TN2_SPREAD == 2 && !(SYNC) && pend;       /* second half of the previous boundary's stage */ \
-    TN2_SB; TN2_MFMA_ROW(0, al_lo[0], al_hi[0], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(ah_lo[0], ah_hi[0], TN2_ADDR_LO(cur__, 0u, wr * 8 + 4), TN2_ADDR_HI(cur__, 0u, wr * 8 + 4));         \
-    TN2_RD(ah_lo[1], ah_hi[1], TN2_ADDR_LO(cur__, 0u, wr * 8 + 5), TN2_ADDR_HI(cur__, 0u, wr * 8 + 5));         \
-    if (tail__) TN2_ONE_A((ST) - 1, 2);                                                                         \
-    TN2_SB; TN2_MFMA_ROW(1, al_lo[1], al_hi[1], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(ah_lo[2], ah_hi[2], TN2_ADDR_LO(cur__, 0u, wr * 8 + 6), TN2_ADDR_HI(cur__, 0u, wr * 8 + 6));         \
-    TN2_RD(ah_lo[3], ah_hi[3], TN2_ADDR_LO(cur__, 0u, wr * 8 + 7), TN2_ADDR_HI(cur__, 0u, wr * 8 + 7));         \
-    if (tail__) TN2_ONE_B((ST) - 1, 2);                                                                         \
-    TN2_SB; TN2_MFMA_ROW(2, al_lo[2], al_hi[2], BCL, BCH);                                                      \
-    if (tail__) TN2_ONE_A((ST) - 1, 3);                                                                         \
-    TN2_SB; TN2_MFMA_ROW(3, al_lo[3], al_hi[3], BCL, BCH);                                                      \
-    if (tail__) { TN2_ONE_B((ST) - 1, 3); pend = false; }                                                       \
-    TN2_SB;                                                                                                     \
-    TN2_PIN8("s_waitcnt lgkmcnt(0)", ah_lo, ah_hi);                                                             \
-    if (SYNC) {                                                                                                 \
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");                                             \
-      spread__ = !TN2_NOLOAD && TN2_SPREAD && ((ST) + 3 < nst || ((ST) + 3 == nst && (ke - kb) % 64 == 0));     \
-      if (TN2_NOLOAD) { }                                                                                       \
-      else if (spread__) {                                                                                      \
-        if (TN2_SPREAD == 2) { TN2_ONE_A(ST, 0); pend = true; } else TN2_PIECE(ST, 0);                          \
-      }                                                                                                         \
-      else if ((ST) + 3 < nst || ((ST) + 3 == nst && (ke - kb) % 64 == 0))                                      \
-        tn2_stage_full(A, hm_a > 0 ? 64 : lda, B, ldb, kb + TN2_KSEL((ST) + 2) * 64, lds0 + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, oa, ob); \
-      else if ((ST) + 2 < nst)                                                                                  \
-        tn2_stage(A, lda, m0, M, B, ldb, n0, N, kb + ((ST) + 2) * 64, ke, smem + ((ST) & 1) * TN2_STAGE, wave, lane, hm_a); \
-      if ((ST) + 1 == nst - 1 && (ke - kb) % 64 != 0) {                                                         \
-        /* ragged last stage: rows >= valid hold clamped copies -> zero them (both operands) */                \
-        const int valid__ = (ke - kb) - (nst - 1) * 64;                                                         \
-        char* sp__ = smem + (((ST) + 1) & 1) * TN2_STAGE;                                                       \
-        for (int idx = tid; idx < 64 * 64; idx += 512) {                                                        \
-          const int kr = idx >> 6, c16 = idx & 63;                                                              \
-          if (kr >= valid__) *reinterpret_cast<uint4*>(sp__ + kr * 512 + (c16 & 31) * 16 + (c16 >> 5) * 32768) = make_uint4(0, 0, 0, 0); \
-        }                                                                                                       \
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                         \
-      }                                                                                                         \
-    }                                                                                                           \
-    TN2_SB; TN2_MFMA_ROW(4, ah_lo[0], ah_hi[0], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(al_lo[0], al_hi[0], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 0), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 0));         \
-    TN2_RD(BNL[0], BNH[0], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 0), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 0));     \
-    TN2_RD(al_lo[1], al_hi[1], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 1), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 1));         \
-    if (SYNC && spread__) { if (TN2_SPREAD == 2) TN2_ONE_B(ST, 0); else TN2_PIECE(ST, 1); }                     \
-    TN2_SB; TN2_MFMA_ROW(5, ah_lo[1], ah_hi[1], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(BNL[1], BNH[1], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 1), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 1));     \
-    TN2_RD(al_lo[2], al_hi[2], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 2), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 2));         \
-    TN2_RD(BNL[2], BNH[2], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 2), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 2));     \
-    if (SYNC && spread__) { if (TN2_SPREAD == 2) TN2_ONE_A(ST, 1); else TN2_PIECE(ST, 2); }                     \
-    TN2_SB; TN2_MFMA_ROW(6, ah_lo[2], ah_hi[2], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(al_lo[3], al_hi[3], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 3), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 3));         \
-    TN2_RD(BNL[3], BNH[3], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 3), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 3));     \
-    if (SYNC && spread__) { if (TN2_SPREAD == 2) TN2_ONE_B(ST, 1); else TN2_PIECE(ST, 3); }                     \
-    TN2_SB; TN2_MFMA_ROW(7, ah_lo[3], ah_hi[3], BCL, BCH);                                                      \
-    TN2_SB;                                                                                                     \
-    TN2_PIN8("s_waitcnt lgkmcnt(0)", al_lo, al_hi);                                                             \
-    TN2_PIN8("s_waitcnt lgkmcnt(0)", BNL, BNH);                                                                 \
+    SPREAD = (ST) + 3 < nst || ((ST) + 3 == nst && (ke - kb) % 64 == 0);       /* stage ST + 2 exists and is full */ \
+    if (SPREAD) { TN2_ONE_A(ST, 0); pend = true; }                                                              \
+    else if ((ST) + 2 < nst)                                                                                    \
+      tn2_stage(A, lda, m0, M, B, ldb, n0, N, kb + ((ST) + 2) * 64, ke, smem + ((ST) & 1) * TN2_STAGE, wave, lane, hm_a); \
+    if ((ST) + 1 == nst - 1 && (ke - kb) % 64 != 0)                            /* ragged last stage */         \
+      TN2_ZERO_TAIL(smem + (((ST) + 1) & 1) * TN2_STAGE, (ke - kb) - (nst - 1) * 64);                      \
   } while (0)
 
+  // A[0..3] and B of k-step 0: column tile index ct = (wave col offset)/16 + i
+  TN2_FIRST_FRAGS(lds0);
   if (nst == 1 && (ke - kb) % 64 != 0) {
-    // single ragged stage: zero the tail rows before anything is consumed (fragments above are re-read)
-    const int valid = ke - kb;
-    for (int idx = tid; idx < 64 * 64; idx += 512) {
-      const int kr = idx >> 6, c16 = idx & 63;
-      if (kr >= valid) *reinterpret_cast<uint4*>(smem + kr * 512 + (c16 & 31) * 16 + (c16 >> 5) * 32768) = make_uint4(0, 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      TN2_RD(al_lo[i], al_hi[i], TN2_ADDR_LO(lds0, 0u, wr * 8 + i), TN2_ADDR_HI(lds0, 0u, wr * 8 + i));
-      TN2_RD(bx_lo[i], bx_hi[i], TN2_ADDR_LO(lds0, 32768u, wc * 4 + i), TN2_ADDR_HI(lds0, 32768u, wc * 4 + i));
-    }
-    TN2_PIN8("s_waitcnt lgkmcnt(0)", al_lo, al_hi);
-    TN2_PIN8("s_waitcnt lgkmcnt(0)", bx_lo, bx_hi);
+    // single ragged stage: zero the tail rows before anything is consumed (the fragments are re-read)
+    TN2_ZERO_TAIL(smem, ke - kb);
+    TN2_FIRST_FRAGS(lds0);
   }
-  bool pend = false;                      // TN2_SPREAD == 2: half of the last boundary's stage is still to be issued
+  bool pend = false;                      // half of the last boundary's stage is still to be issued
   for (int st = 0; st < nst; ++st) {
     const uint32_t sc = lds0 + (uint32_t)((st & 1) * TN2_STAGE), sn = lds0 + (uint32_t)(((st + 1) & 1) * TN2_STAGE);
     do_bias = dbias != nullptr && (st % bias_mod) == bias_slot;
     TN2_STEP(sc, sc + 32 * 512, bx_lo, bx_hi, by_lo, by_hi, false, st);
     TN2_STEP(sc + 32 * 512, sn, by_lo, by_hi, bx_lo, bx_hi, true, st);
   }
-#undef TN2_STEP
+#undef TN2_BOUNDARY
+#undef TN2_ONE_B
+#undef TN2_ONE_A
 
   float* o = out + (long)split * slab_stride;
   const float inv_b = gs_inv(gs), inv = scale_out ? inv_b : 1.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int m = m0 + wr * 128 + i * 16 + fs;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wc * 64 + j * 16 + fg * 4;
-      if (n >= N) continue;
-      float4* dst = reinterpret_cast<float4*>(o + (long)m * ldo + n);
-      float4 v = make_float4(acc[i][j][0] * inv, acc[i][j][1] * inv, acc[i][j][2] * inv, acc[i][j][3] * inv);
-      if (accumulate) { float4 c = *dst; v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w; }
-      *dst = v;
-    }
-  }
-  if (dbias != nullptr) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float t = bsum[i];
-      t += __shfl_xor(t, 16, 64);
-      t += __shfl_xor(t, 32, 64);
-      const int m = m0 + wr * 128 + i * 16 + fs;
-      if (fg == 0 && m < M) {
-        if (dbias_parts) dbias[(long)(split * bias_mod + bias_slot) * M + m] = t;
-        else atomicAdd(dbias + m, t * inv_b);
-      }
-    }
-  }
+#define TN_INV(X) ((X) * inv)
+#define TN_INV_B(X) ((X) * inv_b)
+  TN_STORE_TILES(8, o, m0 + wr * 128, n0 + wc * 64, TN_INV);
+  TN_FLUSH_DBIAS(TN_INV_B);
+#undef TN_INV_B
+#undef TN_INV
 }
 
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slabs, long slab_stride, int splits,

@@ -118,10 +118,7 @@ __global__ __launch_bounds__(256) void gemm_nt_p5_kernel(
     pB = reinterpret_cast<const char*>(B + (long)(n0_ + wave * 64) * ldb);
     pA = reinterpret_cast<const char*>(A + (long)(m0_ + wave * 64) * lda);
   }
-#define P5_REQ_B() asm volatile("s_mov_b32 m0, %0" ::"s"(rB) : "memory")
-#define P5_REQ_A() asm volatile("s_mov_b32 m0, %0" ::"s"(rA) : "memory")
-#define P5_PIECE_B(J) asm volatile("global_load_lds_dwordx4 %0, %1\n\ts_add_u32 m0, m0, 0x400" ::"v"(offB[J]), "s"(pB) : "memory", "scc")
-#define P5_PIECE_A(J) asm volatile("global_load_lds_dwordx4 %0, %1\n\ts_add_u32 m0, m0, 0x400" ::"v"(offA[J]), "s"(pA) : "memory", "scc")
+  // (W1_REQ_A/B, W1_PIECE_A/B, W1_ALL8: csrc/p3.h, section 4; what ends a request is this kernel's)
 #define P5_DONE_B()                                                                                                            \
   do {                                                                                                                         \
     pB += 128; rB = rBsum - rB;                                                                                                    \
@@ -132,13 +129,12 @@ __global__ __launch_bounds__(256) void gemm_nt_p5_kernel(
     pA += 128; rA = rA + 32768u >= ldsB ? rA - 65536u : rA + 32768u;                                                           \
     if (++stA == nst) { stA = 0; ++kA; int m_, n_; tile_of(kA, m_, n_); pA = reinterpret_cast<const char*>(A + (long)(m_ + wave * 64) * lda); } \
   } while (0)
-#define P5_ALL8(M_) do { M_(0); M_(1); M_(2); M_(3); M_(4); M_(5); M_(6); M_(7); } while (0)
 
   // the wave's 128 bias columns in two VGPRs (lane l: columns l and 64 + l of the wave tile); tile 0's here, tile k+1's in stage
   // nst-2 of tile k
   float vb0 = 0.f, vb1 = 0.f;
-  P5_REQ_B(); P5_ALL8(P5_PIECE_B); P5_DONE_B();
-  P5_REQ_A(); P5_ALL8(P5_PIECE_A); P5_DONE_A();                 // stage 0
+  W1_REQ_B(); W1_ALL8(W1_PIECE_B); P5_DONE_B();
+  W1_REQ_A(); W1_ALL8(W1_PIECE_A); P5_DONE_A();                 // stage 0
   if (bias) {
     int m0_, n0_;
     tile_of(0, m0_, n0_);
@@ -147,9 +143,9 @@ __global__ __launch_bounds__(256) void gemm_nt_p5_kernel(
     asm volatile("global_load_dword %0, %2, %3\n\tglobal_load_dword %1, %2, %3 offset:256" : "=&v"(vb0), "=&v"(vb1) : "v"(bo), "s"(bp) : "memory");
   }
   asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" : "+v"(vb0), "+v"(vb1)::"memory");
-  P5_REQ_B(); P5_ALL8(P5_PIECE_B); P5_DONE_B();
-  P5_REQ_A(); P5_ALL8(P5_PIECE_A); P5_DONE_A();
-  P5_REQ_A(); P5_PIECE_A(0); P5_PIECE_A(1); P5_PIECE_A(2);      // B(1) A(1) A(2): pieces 3..7 of an A request are always issued by the next E-step
+  W1_REQ_B(); W1_ALL8(W1_PIECE_B); P5_DONE_B();
+  W1_REQ_A(); W1_ALL8(W1_PIECE_A); P5_DONE_A();
+  W1_REQ_A(); W1_PIECE_A(0); W1_PIECE_A(1); W1_PIECE_A(2);      // B(1) A(1) A(2): pieces 3..7 of an A request are always issued by the next E-step
                                                                 // from here on: behind the barrier of stage g, B(g+2) then A(g+3)
 
   // Fragments, single-buffered (18 quads).  A stage is two k-steps of opposite loop order:
@@ -216,14 +212,14 @@ __global__ __launch_bounds__(256) void gemm_nt_p5_kernel(
     P5_ECOLG(0, bx, b[1] = P5_LDF(sb0__ + 1 * 2048), b[2] = P5_LDF(sb0__ + 2 * 2048), b[3] = P5_LDF(sb0__ + 3 * 2048), \
              b[4] = P5_LDF(sb0__ + 4 * 2048), b[5] = P5_LDF(sb0__ + 5 * 2048), b[6] = P5_LDF(sb0__ + 6 * 2048), \
              b[7] = P5_LDF(sb0__ + 7 * 2048), ax = P5_LDF(sa1__));                     \
-    P5_ECOLG(1, b[1], b[0] = P5_LDF(sb1__ + 0 * 2048), P5_NOP_, P5_NOP_, P5_PIECE_A(3), P5_NOP_, \
+    P5_ECOLG(1, b[1], b[0] = P5_LDF(sb1__ + 0 * 2048), P5_NOP_, P5_NOP_, W1_PIECE_A(3), P5_NOP_, \
              P5_NOP_, P5_NOP_, P5_NOP_);                                                      \
-    P5_ECOLG(2, b[2], b[1] = P5_LDF(sb1__ + 1 * 2048), P5_NOP_, P5_NOP_, P5_PIECE_A(4), P5_NOP_, \
+    P5_ECOLG(2, b[2], b[1] = P5_LDF(sb1__ + 1 * 2048), P5_NOP_, P5_NOP_, W1_PIECE_A(4), P5_NOP_, \
              P5_NOP_, P5_NOP_, P5_NOP_);                                                      \
-    P5_ECOLG(3, b[3], b[2] = P5_LDF(sb1__ + 2 * 2048), P5_NOP_, P5_NOP_, P5_PIECE_A(5), P5_NOP_, \
+    P5_ECOLG(3, b[3], b[2] = P5_LDF(sb1__ + 2 * 2048), P5_NOP_, P5_NOP_, W1_PIECE_A(5), P5_NOP_, \
              P5_NOP_, P5_NOP_, P5_NOP_);                                                      \
-    P5_ECOLG(4, b[4], b[3] = P5_LDF(sb1__ + 3 * 2048), P5_NOP_, P5_NOP_, P5_PIECE_A(6), P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_);   \
-    P5_ECOLG(5, b[5], b[4] = P5_LDF(sb1__ + 4 * 2048), P5_NOP_, P5_NOP_, P5_PIECE_A(7), P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_);   \
+    P5_ECOLG(4, b[4], b[3] = P5_LDF(sb1__ + 3 * 2048), P5_NOP_, P5_NOP_, W1_PIECE_A(6), P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_);   \
+    P5_ECOLG(5, b[5], b[4] = P5_LDF(sb1__ + 4 * 2048), P5_NOP_, P5_NOP_, W1_PIECE_A(7), P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_);   \
     P5_ECOLG(6, b[6], b[5] = P5_LDF(sb1__ + 5 * 2048), P5_NOP_, P5_NOP_, P5_DONE_A(), P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_);     \
     P5_ECOLG(7, b[7], b[6] = P5_LDF(sb1__ + 6 * 2048), P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_, P5_NOP_);         \
   } while (0)
@@ -330,22 +326,22 @@ __global__ __launch_bounds__(256) void gemm_nt_p5_kernel(
       P5_PACK1(0, 0); P5_PACK1(0, 1); P5_PACK1(0, 2); P5_PACK1(0, 3); P5_PACK1(0, 4); P5_PACK1(0, 5); P5_PACK1(0, 6); P5_PACK1(0, 7); \
     }                                                                                                                          \
     P5_OROWG(2, a[2], a[0] = P5_LDF(san__); P5_LG(LAST, 1, 0), a[1] = P5_LDF(san__ + 2048); P5_LG(LAST, 1, 1), bx = P5_LDF(sbn__); P5_LG(LAST, 1, 2), \
-             P5_REQ_B(); P5_LG(LAST, 1, 3), P5_PIECE_B(0); P5_LG(LAST, 1, 4), P5_PIECE_B(1); P5_LG(LAST, 1, 5),                \
+             W1_REQ_B(); P5_LG(LAST, 1, 3), W1_PIECE_B(0); P5_LG(LAST, 1, 4), W1_PIECE_B(1); P5_LG(LAST, 1, 5),                \
              P5_IF(da__, P5_DRAIN_WP(0)); P5_LG(LAST, 1, 6), P5_LG(LAST, 1, 7));                                               \
     P5_OROWG(3, a[3], a[2] = P5_LDF(san__ + 2 * 2048); P5_IF(da__, P5_DRAIN_W1(ua__, 0)); P5_LG(LAST, 2, 0), P5_IF(da__, P5_DRAIN_W1(ua__, 1)); P5_LG(LAST, 2, 1), \
-             P5_IF(da__, P5_DRAIN_W1(ua__, 2)); P5_LG(LAST, 2, 2), P5_PIECE_B(2); P5_IF(da__, P5_DRAIN_W1(ua__, 3)); P5_LG(LAST, 2, 3), \
+             P5_IF(da__, P5_DRAIN_W1(ua__, 2)); P5_LG(LAST, 2, 2), W1_PIECE_B(2); P5_IF(da__, P5_DRAIN_W1(ua__, 3)); P5_LG(LAST, 2, 3), \
              P5_IF(da__, P5_DRAIN_W1(ua__, 4)); P5_LG(LAST, 2, 4), P5_IF(da__, P5_DRAIN_W1(ua__, 5)); P5_LG(LAST, 2, 5),       \
-             P5_PIECE_B(3); P5_IF(da__, P5_DRAIN_W1(ua__, 6)); P5_LG(LAST, 2, 6), P5_IF(da__, P5_DRAIN_W1(ua__, 7)); P5_LG(LAST, 2, 7)); \
+             W1_PIECE_B(3); P5_IF(da__, P5_DRAIN_W1(ua__, 6)); P5_LG(LAST, 2, 6), P5_IF(da__, P5_DRAIN_W1(ua__, 7)); P5_LG(LAST, 2, 7)); \
     P5_OROWG(4, a[4], a[3] = P5_LDF(san__ + 3 * 2048); P5_LG(LAST, 3, 0), P5_IF(da__, P5_DRAIN_R(0, 0, 0)); P5_LG(LAST, 3, 1), P5_IF(da__, P5_DRAIN_SP()); P5_LG(LAST, 3, 2), \
-             P5_PIECE_B(4); P5_LG(LAST, 3, 3), P5_LG(LAST, 3, 4), P5_IF(da__, P5_DRAIN_S(ua__, 0, 0, dm__, dn__)); P5_IF(da__, P5_DRAIN_R(0, 1, 0)); P5_LG(LAST, 3, 5), \
-             P5_PIECE_B(5); P5_LG(LAST, 3, 6), P5_LG(LAST, 3, 7));                                                             \
+             W1_PIECE_B(4); P5_LG(LAST, 3, 3), P5_LG(LAST, 3, 4), P5_IF(da__, P5_DRAIN_S(ua__, 0, 0, dm__, dn__)); P5_IF(da__, P5_DRAIN_R(0, 1, 0)); P5_LG(LAST, 3, 5), \
+             W1_PIECE_B(5); P5_LG(LAST, 3, 6), P5_LG(LAST, 3, 7));                                                             \
     P5_OROWG(5, a[5], a[4] = P5_LDF(san__ + 4 * 2048); P5_LG(LAST, 4, 0), P5_LG(LAST, 4, 1), P5_IF(da__, P5_DRAIN_S(ua__, 0, 1, dm__, dn__)); P5_IF(da__, P5_DRAIN_R(1, 0, 0)); P5_LG(LAST, 4, 2), \
-             P5_PIECE_B(6); P5_LG(LAST, 4, 3), P5_LG(LAST, 4, 4), P5_IF(da__, P5_DRAIN_S(ua__, 1, 0, dm__, dn__)); P5_IF(da__, P5_DRAIN_R(1, 1, 0)); P5_LG(LAST, 4, 5), \
-             P5_PIECE_B(7); P5_LG(LAST, 4, 6), P5_IF(NEXTBIAS, P5_NEXTBIAS()); P5_LG(LAST, 4, 7));                             \
+             W1_PIECE_B(6); P5_LG(LAST, 4, 3), P5_LG(LAST, 4, 4), P5_IF(da__, P5_DRAIN_S(ua__, 1, 0, dm__, dn__)); P5_IF(da__, P5_DRAIN_R(1, 1, 0)); P5_LG(LAST, 4, 5), \
+             W1_PIECE_B(7); P5_LG(LAST, 4, 6), P5_IF(NEXTBIAS, P5_NEXTBIAS()); P5_LG(LAST, 4, 7));                             \
     P5_OROWG(6, a[6], a[5] = P5_LDF(san__ + 5 * 2048); P5_LG(LAST, 5, 0), P5_LG(LAST, 5, 1), P5_IF(da__, P5_DRAIN_S(ua__, 1, 1, dm__, dn__)); P5_LG(LAST, 5, 2), \
              P5_LG(LAST, 5, 3), P5_DONE_B(); P5_LG(LAST, 5, 4), P5_LG(LAST, 5, 5), P5_LG(LAST, 5, 6), P5_LG(LAST, 5, 7));      \
-    P5_OROWG(7, a[7], a[6] = P5_LDF(san__ + 6 * 2048); P5_LG(LAST, 6, 0), P5_LG(LAST, 6, 1), P5_REQ_A(); P5_LG(LAST, 6, 2), P5_PIECE_A(0); P5_LG(LAST, 6, 3), \
-             P5_PIECE_A(1); P5_LG(LAST, 6, 4), P5_PIECE_A(2); P5_LG(LAST, 6, 5), P5_LG(LAST, 6, 6), P5_LG(LAST, 6, 7));        \
+    P5_OROWG(7, a[7], a[6] = P5_LDF(san__ + 6 * 2048); P5_LG(LAST, 6, 0), P5_LG(LAST, 6, 1), W1_REQ_A(); P5_LG(LAST, 6, 2), W1_PIECE_A(0); P5_LG(LAST, 6, 3), \
+             W1_PIECE_A(1); P5_LG(LAST, 6, 4), W1_PIECE_A(2); P5_LG(LAST, 6, 5), P5_LG(LAST, 6, 6), P5_LG(LAST, 6, 7));        \
     if (LAST) {                                                                                                                \
       /* (an MFMA's result may be read by the VALU only some passes after issue; the hazard recognizer cannot see the MFMAs      \
          inside the inline asm, so the last row block waits explicitly) */                                                       \

@@ -107,18 +107,14 @@ __global__ __launch_bounds__(256) void gemm_tn5_kernel(
   int stA = 0, stB = 0;                                             // stage of the next request (clamped to the last one past the end)
   uint32_t rB = ldsB + (uint32_t)(wave * 8192), rA = lds0 + (uint32_t)(wave * 8192);
   const uint32_t rBsum = 2u * rB + 32768u;
-#define T5_REQ_B() asm volatile("s_mov_b32 m0, %0" ::"s"(rB) : "memory")
-#define T5_REQ_A() asm volatile("s_mov_b32 m0, %0" ::"s"(rA) : "memory")
-#define T5_PIECE_B(J) asm volatile("global_load_lds_dwordx4 %0, %1\n\ts_add_u32 m0, m0, 0x400" ::"v"(offB[J]), "s"(pB) : "memory", "scc")
-#define T5_PIECE_A(J) asm volatile("global_load_lds_dwordx4 %0, %1\n\ts_add_u32 m0, m0, 0x400" ::"v"(offA[J]), "s"(pA) : "memory", "scc")
+  // (W1_REQ_A/B, W1_PIECE_A/B, W1_ALL8: csrc/p3.h, section 4; what ends a request is this kernel's)
 #define T5_DONE_B() do { rB = rBsum - rB; if (++stB < nst) pB += strB; } while (0)
 #define T5_DONE_A() do { rA = rA + 32768u >= ldsB ? rA - 65536u : rA + 32768u; if (++stA < nst) pA += strA; } while (0)
-#define T5_ALL8(M_) do { M_(0); M_(1); M_(2); M_(3); M_(4); M_(5); M_(6); M_(7); } while (0)
-  T5_REQ_B(); T5_ALL8(T5_PIECE_B); T5_DONE_B();
-  T5_REQ_A(); T5_ALL8(T5_PIECE_A); T5_DONE_A();                     // stage 0
+  W1_REQ_B(); W1_ALL8(W1_PIECE_B); T5_DONE_B();
+  W1_REQ_A(); W1_ALL8(W1_PIECE_A); T5_DONE_A();                     // stage 0
   asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-  T5_REQ_B(); T5_ALL8(T5_PIECE_B); T5_DONE_B();
-  T5_REQ_A(); T5_ALL8(T5_PIECE_A); T5_DONE_A();                     // B(1) A(1); A(2) goes out in stage 0's first k-step like every A(g+2):
+  W1_REQ_B(); W1_ALL8(W1_PIECE_B); T5_DONE_B();
+  W1_REQ_A(); W1_ALL8(W1_PIECE_A); T5_DONE_A();                     // B(1) A(1); A(2) goes out in stage 0's first k-step like every A(g+2):
                                                                     // B(g+2) is requested behind the barrier of stage g, A(g+3) in the k-step after it
 
   // ---- fragment addressing: lane (fg, fs) supplies token row 4 fg + (fs >> 2) of a 32-row k-step, 8 B at element column
@@ -183,36 +179,36 @@ __global__ __launch_bounds__(256) void gemm_tn5_kernel(
 #define T5_KS0(BS)                                                                                             \
   do {                                                                                                         \
     const uint32_t na__ = oA + 16384u, nb__ = oB + 16384u;                                                     \
-    T5_ROW(BS, 0, 1, 0, T5_NOP_, T5_NOP_, T5_REQ_A(), T5_PIECE_A(0), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);          \
-    T5_ROW(BS, 0, 1, 1, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_A(1), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 0, 1, 2, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_A(2), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 0, 1, 3, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_A(3), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 0, 1, 4, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_A(4), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 0, 1, 5, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_A(5), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 0, 1, 6, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_A(6), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 0, 1, 7, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_A(7), T5_NOP_, T5_DONE_A(), T5_NOP_, T5_NOP_);         \
+    T5_ROW(BS, 0, 1, 0, T5_NOP_, T5_NOP_, W1_REQ_A(), W1_PIECE_A(0), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);          \
+    T5_ROW(BS, 0, 1, 1, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_A(1), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 0, 1, 2, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_A(2), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 0, 1, 3, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_A(3), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 0, 1, 4, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_A(4), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 0, 1, 5, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_A(5), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 0, 1, 6, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_A(6), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 0, 1, 7, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_A(7), T5_NOP_, T5_DONE_A(), T5_NOP_, T5_NOP_);         \
   } while (0)
   // where the eight B pieces of a request go (tools/build_variant.sh -DT5_B_WHOLE_KSTEP: over the whole k-step like A; default: its
   // first half -- B(g+2) is needed one stage later and comes from HBM like A)
 #ifdef T5_B_WHOLE_KSTEP
 #define T5_KS1_ROWS(BS)                                                                                        \
   do {                                                                                                         \
-    T5_ROW(BS, 1, 0, 0, T5_NOP_, T5_NOP_, T5_REQ_B(), T5_PIECE_B(0), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);          \
-    T5_ROW(BS, 1, 0, 1, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(1), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 1, 0, 2, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(2), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 1, 0, 3, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(3), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 1, 0, 4, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(4), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 1, 0, 5, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(5), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 1, 0, 6, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(6), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
-    T5_ROW(BS, 1, 0, 7, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(7), T5_NOP_, T5_DONE_B(), T5_NOP_, T5_NOP_);         \
+    T5_ROW(BS, 1, 0, 0, T5_NOP_, T5_NOP_, W1_REQ_B(), W1_PIECE_B(0), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);          \
+    T5_ROW(BS, 1, 0, 1, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(1), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 1, 0, 2, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(2), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 1, 0, 3, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(3), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 1, 0, 4, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(4), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 1, 0, 5, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(5), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 1, 0, 6, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(6), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);             \
+    T5_ROW(BS, 1, 0, 7, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(7), T5_NOP_, T5_DONE_B(), T5_NOP_, T5_NOP_);         \
   } while (0)
 #else
 #define T5_KS1_ROWS(BS)                                                                                        \
   do {                                                                                                         \
-    T5_ROW(BS, 1, 0, 0, T5_NOP_, T5_NOP_, T5_REQ_B(), T5_PIECE_B(0), T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(1));    \
-    T5_ROW(BS, 1, 0, 1, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(2), T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(3));       \
-    T5_ROW(BS, 1, 0, 2, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(4), T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(5));       \
-    T5_ROW(BS, 1, 0, 3, T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(6), T5_NOP_, T5_NOP_, T5_NOP_, T5_PIECE_B(7));       \
+    T5_ROW(BS, 1, 0, 0, T5_NOP_, T5_NOP_, W1_REQ_B(), W1_PIECE_B(0), T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(1));    \
+    T5_ROW(BS, 1, 0, 1, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(2), T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(3));       \
+    T5_ROW(BS, 1, 0, 2, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(4), T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(5));       \
+    T5_ROW(BS, 1, 0, 3, T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(6), T5_NOP_, T5_NOP_, T5_NOP_, W1_PIECE_B(7));       \
     T5_ROW(BS, 1, 0, 4, T5_NOP_, T5_NOP_, T5_NOP_, T5_DONE_B(), T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);               \
     T5_ROW(BS, 1, 0, 5, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);                   \
     T5_ROW(BS, 1, 0, 6, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_, T5_NOP_);                   \

@@ -48,7 +48,7 @@ __device__ __forceinline__ void xp_gelu_both(float u, float& g, float& dg) {
 }
 
 // ------------------------------------------------------------------------------------------ NT
-// The main loop is gemm_nt_p3_kernel's (csrc/gemm.hip; comments there), with stage -> (k block, term) addressing.  The
+// The main loop is the one gemm_nt_p3_kernel runs (csrc/p3.h, section 2; comments there), with stage -> (k block, term) addressing.  The
 // epilogue differs: inputs (`in`) arrive by direct 16-B global loads in the accumulator layout, one 16-row chunk ahead, all
 // waits counted; results pass through the wave's 4 KB of the A slot the tile's last stage freed and leave as full lines.
 template <typename F, int EPI, bool HAS_IN, bool DROP, bool RING>
@@ -76,9 +76,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
   const uint32_t bmask = bias ? 0xFFFFFFFFu : 0u;
   const uint32_t offA0 = (uint32_t)(lr * lda + ec0) * 2, offA1 = (uint32_t)(lr * lda + ec1) * 2;
   const uint32_t offB0 = (uint32_t)(lr * ldb + ec0) * 2, offB1 = (uint32_t)(lr * ldb + ec1) * 2;
-#define XP_AK(S) xp_off((S), a_ps, 1)
-#define XP_BK(S) xp_off((S), b_ps, 0)
-#define P_LANE(L) int L = lane; asm volatile("" : "+v"(L))
+#define P_AK(S) xp_off((S), a_ps, 1)
+#define P_BK(S) xp_off((S), b_ps, 0)
 
   int v = blockIdx.x;
   int tile = xcd_remap(v, ntiles);
@@ -102,80 +101,27 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
     p3_half(A + a_ps, lda, m0, 0, R_SLOT(2), wave, offA0, offA1);
     p3_half(A, lda, m0, 64, R_SLOT(3), wave, offA0, offA1);
   } else {
-    p3_half(B, ldb, n0, XP_BK(0), ldsB, wave, offB0, offB1);
-    p3_half(A, lda, m0, XP_AK(0), lds0, wave, offA0, offA1);
+    p3_half(B, ldb, n0, P_BK(0), ldsB, wave, offB0, offB1);
+    p3_half(A, lda, m0, P_AK(0), lds0, wave, offA0, offA1);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    p3_half(B, ldb, n0, XP_BK(1), ldsB + 32768u, wave, offB0, offB1);
-    p3_half(A, lda, m0, XP_AK(1), lds0 + 32768u, wave, offA0, offA1);
-    p3_half(A, lda, m0, XP_AK(2), lds0 + 65536u, wave, offA0, offA1);
+    p3_half(B, ldb, n0, P_BK(1), ldsB + 32768u, wave, offB0, offB1);
+    p3_half(A, lda, m0, P_AK(1), lds0 + 32768u, wave, offA0, offA1);
+    p3_half(A, lda, m0, P_AK(2), lds0 + 65536u, wave, offA0, offA1);
   }
   int a0 = 0, b0 = 0;
   f32x4 bq0, bq1, bq2, bq3;
-  {
-    const float* bp0 = bias ? bias + n0 + wc * 64 : reinterpret_cast<const float*>(A);
-    const uint32_t boff = (uint32_t)(fg * 16);
-    P_GLD4(bq0, boff, bp0, 0); P_GLD4(bq1, boff, bp0, 64); P_GLD4(bq2, boff, bp0, 128); P_GLD4(bq3, boff, bp0, 192);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(bq0), "+v"(bq1), "+v"(bq2), "+v"(bq3)::"memory");
-  }
+  P_BIAS_FIRST();
+  P_PENDING_DMA_STATE;
 
-#define V3_MFMA_ROW(I, AF, B0, B1, B2, B3)                                                     \
-  acc[I][0] = H16<F>::mfma(B0, AF, acc[I][0]);             \
-  acc[I][1] = H16<F>::mfma(B1, AF, acc[I][1]);             \
-  acc[I][2] = H16<F>::mfma(B2, AF, acc[I][2]);             \
-  acc[I][3] = H16<F>::mfma(B3, AF, acc[I][3])
-#define V3_RD1(FR, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=&v"(FR) : "v"(ADDR) : "memory")
-#define V3_SB __builtin_amdgcn_sched_barrier(0)
-#define P3_BOUNDARY_WAIT() asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory")
-#define P3_LGKM_WAIT "s_waitcnt lgkmcnt(0)"
-  const char* pa_g = nullptr; const char* pb_g = nullptr;
-  uint32_t pa_slot = 0, pb_slot = 0;
-  bool pa_pend = false, pb_pend = false;
-#define P3_HA(J) do { if (pa_pend) { P_DMA16(((J) & 1) ? offA1 : offA0, pa_g + (long)(J) * 8 * lda * 2, pa_slot + (uint32_t)((J) * 1024)); if ((J) == 3) pa_pend = false; } } while (0)
-#define P3_HB(J) do { if (pb_pend) { P_DMA16(((J) & 1) ? offB1 : offB0, pb_g + (long)(J) * 8 * ldb * 2, pb_slot + (uint32_t)((J) * 1024)); if ((J) == 3) pb_pend = false; } } while (0)
-#define P3_HAX(ROW, S1) do { if ((ROW) < 4) P3_HA(ROW); } while (0)
-#define P_STEP(CURA, NA, NB, BC0, BC1, BC2, BC3, BN0, BN1, BN2, BN3, BOUNDARY, S1)               \
-  do {                                                                                         \
-    const uint32_t aa__ = (CURA), na__ = (NA), nb__ = (NB);                                    \
-    V3_SB; V3_MFMA_ROW(0, al0, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(ah0, aa__, 8192); V3_RD1(ah1, aa__, 10240); P3_HAX(0, S1); \
-    V3_SB; V3_MFMA_ROW(1, al1, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(ah2, aa__, 12288); V3_RD1(ah3, aa__, 14336); P3_HAX(1, S1); \
-    V3_SB; V3_MFMA_ROW(2, al2, BC0, BC1, BC2, BC3); V3_SB; P3_HAX(2, S1);                      \
-    V3_SB; V3_MFMA_ROW(3, al3, BC0, BC1, BC2, BC3); V3_SB; P3_HAX(3, S1);                      \
-    V3_SB;                                                                                     \
-    V3_PIN4(P3_LGKM_WAIT, ah0, ah1, ah2, ah3);                                                 \
-    BOUNDARY();                                                                                \
-    V3_SB; V3_MFMA_ROW(4, ah0, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(al0, na__, 0); V3_RD1(BN0, nb__, 0); V3_RD1(al1, na__, 2048); P3_HB(1); P3_HAX(4, S1); \
-    V3_SB; V3_MFMA_ROW(5, ah1, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(BN1, nb__, 2048); V3_RD1(al2, na__, 4096); V3_RD1(BN2, nb__, 4096); P3_HB(2); P3_HAX(5, S1); \
-    V3_SB; V3_MFMA_ROW(6, ah2, BC0, BC1, BC2, BC3); V3_SB; V3_RD1(al3, na__, 6144); V3_RD1(BN3, nb__, 6144); P3_HB(3); P3_HAX(6, S1); \
-    V3_SB; V3_MFMA_ROW(7, ah3, BC0, BC1, BC2, BC3);                                            \
-    V3_SB;                                                                                     \
-    V3_PIN8(P3_LGKM_WAIT, al0, al1, al2, al3, BN0, BN1, BN2, BN3);                             \
-  } while (0)
-#define P_BND_NONE() do { } while (0)
-#define P_BND_MID()                                                                            \
-  do {                                                                                         \
-    P3_BOUNDARY_WAIT();                                                                        \
-    const bool cb__ = st + 2 < nst, ca__ = st + 3 < nst;                                       \
-    pb_g = reinterpret_cast<const char*>(B + (long)((cb__ ? n0 : n0n) + wave * 32) * ldb + XP_BK(cb__ ? st + 2 : st + 2 - nst)); \
-    pb_slot = ldsB + (uint32_t)(bc * 32768 + wave * 4096);                                     \
-    pa_g = reinterpret_cast<const char*>(A + (long)((ca__ ? m0 : m0n) + wave * 32) * lda + XP_AK(ca__ ? st + 3 : st + 3 - nst)); \
-    pa_slot = lds0 + (uint32_t)(ac * 32768 + wave * 4096);                                     \
-    pb_pend = pa_pend = true;                                                                  \
-    P_DMA16(offB0, pb_g, pb_slot);                                                             \
-  } while (0)
-  // last boundary of the tile: the next tile's bias and this tile's first input chunk are requested BEFORE the next tile's
-  // stage 1, so the epilogue can wait for them without waiting for that stage.  Issue order: bias x4, in x4, B(1) x4.
+  // last boundary of the tile (head and tail: p3.h), with this tile's first input chunk.  Issue order: bias x4, in x4, B(1) x4.
 #define P_BND_LAST()                                                                           \
   do {                                                                                         \
-    asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");                              \
-    P_LANE(lb__);                                                                              \
-    const uint32_t boff__ = (uint32_t)((lb__ >> 4) * 16);                                      \
-    P_GLD4(bq0, boff__, bptr, 0); P_GLD4(bq1, boff__, bptr, 64); P_GLD4(bq2, boff__, bptr, 128); P_GLD4(bq3, boff__, bptr, 192); \
+    P_BND_LAST_HEAD(bptr);                                                                     \
     if (HAS_IN) {                                                                              \
       const uint32_t io__ = (uint32_t)((lb__ & 15) * ldin + (lb__ >> 4) * 4) * 4;              \
       P_GLD4(rin[0][0], io__, ibase, 0); P_GLD4(rin[0][1], io__, ibase, 64); P_GLD4(rin[0][2], io__, ibase, 128); P_GLD4(rin[0][3], io__, ibase, 192); \
     }                                                                                          \
-    pb_g = reinterpret_cast<const char*>(B + (long)(n0n + wave * 32) * ldb + XP_BK(1));        \
-    pb_slot = ldsB + (uint32_t)(bc * 32768 + wave * 4096);                                     \
+    P_BND_LAST_B1();                                                                           \
     pb_pend = true;                                                                            \
     P_DMA16(offB0, pb_g, pb_slot);                                                             \
   } while (0)
@@ -194,10 +140,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
   } while (0)
 #define R_BND_LAST()                                                                           \
   do {                                                                                         \
-    asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");                              \
-    P_LANE(lb__);                                                                              \
-    const uint32_t boff__ = (uint32_t)((lb__ >> 4) * 16);                                      \
-    P_GLD4(bq0, boff__, bptr, 0); P_GLD4(bq1, boff__, bptr, 64); P_GLD4(bq2, boff__, bptr, 128); P_GLD4(bq3, boff__, bptr, 192); \
+    P_BND_LAST_HEAD(bptr);                                                                     \
     if (HAS_IN) {                                                                              \
       const uint32_t io__ = (uint32_t)((lb__ & 15) * ldin + (lb__ >> 4) * 4) * 4;              \
       P_GLD4(rin[0][0], io__, ibase, 0); P_GLD4(rin[0][1], io__, ibase, 64); P_GLD4(rin[0][2], io__, ibase, 128); P_GLD4(rin[0][3], io__, ibase, 192); \
@@ -225,26 +168,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
     const char* ibase = !HAS_IN ? nullptr : reinterpret_cast<const char*>(in + (long)mw * ldin + nw);   // uniform
 
     f32x4 acc[8][4];
-    {
-      f32x4 bi[4] = {bq0, bq1, bq2, bq3};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bi[j][e] = __uint_as_float(__float_as_uint(bi[j][e]) & bmask);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = bi[j];
-    }
+    P_ACC_INIT();
     bf16x8 al0, al1, al2, al3, ah0, ah1, ah2, ah3, bx0, bx1, bx2, bx3, by0, by1, by2, by3;
     f32x4 rin[2][4];                              // the epilogue's input chunks (accumulator layout), ping-pong
-    {
-      const uint32_t aa = RING ? R_SLOT(rr) + oA0 : lds0 + (uint32_t)(a0 * 32768) + oA0;
-      const uint32_t ab = RING ? ldsL + oB0 : ldsB + (uint32_t)(b0 * 32768) + oB0;
-      V3_READ4(al0, al1, al2, al3, aa, 0, 2048, 4096, 6144);
-      V3_READ4(bx0, bx1, bx2, bx3, ab, 0, 2048, 4096, 6144);
-      V3_PIN8("s_waitcnt lgkmcnt(0)", al0, al1, al2, al3, bx0, bx1, bx2, bx3);
-    }
+    P_FIRST_FRAGS(RING ? R_SLOT(rr) + oA0 : lds0 + (uint32_t)(a0 * 32768) + oA0, RING ? ldsL + oB0 : ldsB + (uint32_t)(b0 * 32768) + oB0);
     int ac = a0, bc = b0;
     uint32_t ereg;                                 // this wave's slice of the A slot the tile's last (sub-)stage frees
     if constexpr (RING) {
@@ -261,22 +188,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
         rr = (rr + 3) & 3;
       }
     } else {
-      for (int st = 0; st < nst - 1; ++st) {
-        const int an = ac == 2 ? 0 : ac + 1, bn = bc ^ 1;
-        const uint32_t sa = lds0 + (uint32_t)(ac * 32768), sb = ldsB + (uint32_t)(bc * 32768);
-        const uint32_t na = lds0 + (uint32_t)(an * 32768), nb = ldsB + (uint32_t)(bn * 32768);
-        P_STEP(sa + oA0, sa + oA1, sb + oB1, bx0, bx1, bx2, bx3, by0, by1, by2, by3, P_BND_NONE, 1);
-        P_STEP(sa + oA1, na + oA0, nb + oB0, by0, by1, by2, by3, bx0, bx1, bx2, bx3, P_BND_MID, 0);
-        ac = an; bc = bn;
-      }
-      ereg = lds0 + (uint32_t)(ac * 32768 + wave * 4096);
-      {
-        const int an = ac == 2 ? 0 : ac + 1, bn = bc ^ 1;
-        const uint32_t sa = lds0 + (uint32_t)(ac * 32768), sb = ldsB + (uint32_t)(bc * 32768);
-        const uint32_t na = lds0 + (uint32_t)(an * 32768), nb = ldsB + (uint32_t)(bn * 32768);
-        P_STEP(sa + oA0, sa + oA1, sb + oB1, bx0, bx1, bx2, bx3, by0, by1, by2, by3, P_BND_NONE, 1);
-        P_STEP(sa + oA1, na + oA0, nb + oB0, by0, by1, by2, by3, bx0, bx1, bx2, bx3, P_BND_LAST, 0);
-      }
+      P_TILE_STAGES(ereg);
     }
 
     // ---- epilogue: 8 chunks of 16 rows (= accumulator row block i) per wave, straight-line, no barrier.
@@ -413,22 +325,18 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
         p3_half(A, lda, m0n, 64, ereg - (uint32_t)(wave * 4096), wave, offA0, offA1);
       }
     } else if (has_next) {
-      pa_g = reinterpret_cast<const char*>(A + (long)(m0n + wave * 32) * lda + XP_AK(2));
+      pa_g = reinterpret_cast<const char*>(A + (long)(m0n + wave * 32) * lda + P_AK(2));
       pa_slot = lds0 + (uint32_t)(ac * 32768 + wave * 4096);
       pa_pend = true;
     } else {
-      p3_half(A, lda, m0n, XP_AK(2), lds0 + (uint32_t)(ac * 32768), wave, offA0, offA1);
+      p3_half(A, lda, m0n, P_AK(2), lds0 + (uint32_t)(ac * 32768), wave, offA0, offA1);
     }
     if (!has_next) break;
     v = vn; m0 = m0n; n0 = n0n; a0 = ac == 2 ? 0 : ac + 1; b0 = bc ^ 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#undef P_LANE
-#undef P3_HA
-#undef P3_HAX
-#undef P3_HB
-#undef XP_AK
-#undef XP_BK
+#undef P_AK
+#undef P_BK
 #undef R_KBLOCK
 #undef R_BND_LAST
 #undef R_BND2
@@ -438,17 +346,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
 #undef R_SRC
 #undef R_SLOT
 #undef P_BND_LAST
-#undef P_BND_MID
-#undef P_BND_NONE
-#undef P_STEP
-#undef V3_RD1
-#undef V3_SB
-#undef V3_MFMA_ROW
 }
 
 // ------------------------------------------------------------------------------------------ TN (wgrad)
 // slab[split][M][N] = sum over the split's tokens of  Ahi^T.Blo + Alo^T.Bhi + Ahi^T.Bhi,  A = dY planes [K, M], B = X planes
-// [K, N] (K = tokens, the row index of both).  gemm_tn2_kernel's loop (csrc/gemm.hip) with stream stage s = token block s / 3
+// [K, N] (K = tokens, the row index of both).  gemm_tn2_kernel's loop (TN2_STEP, csrc/p3.h) with stream stage s = token block s / 3
 // of term s % 3; the fused bias gradient (column sums of A) is taken from the fragments of the terms that stage Alo (1) and
 // Ahi (2), so it is the column sum of hi + lo.  A ragged last token block is three ragged stages; each is zeroed past its
 // valid rows after it has landed, as tn2 does for its one.
@@ -500,89 +402,22 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_xp_kernel(
   tn2_stage(XS_A(1), lda, m0, M, XS_B(1), ldb, n0, N, kb, ke, smem + TN2_STAGE, wave, lane, 0);     // (nst >= 3)
 
   bf16x4 al_lo[4], al_hi[4], ah_lo[4], ah_hi[4], bx_lo[4], bx_hi[4], by_lo[4], by_hi[4];
-#define TN2_ADDR_LO(KBASE, OP, CT) ((KBASE) + (OP) + row_lo + (uint32_t)((((CT)) ^ x_lo) << 5))
-#define TN2_ADDR_HI(KBASE, OP, CT) ((KBASE) + (OP) + row_hi + (uint32_t)((((CT)) ^ x_hi) << 5))
-#define TN2_FRAG(LO, HI) ((bf16x8){LO[0], LO[1], LO[2], LO[3], HI[0], HI[1], HI[2], HI[3]})
-#define TN2_MFMA_ROW(I, ALO, AHI, BLO, BHI)                                                                     \
-  do {                                                                                                          \
-    const bf16x8 af__ = TN2_FRAG(ALO, AHI);                                                                     \
-    acc[I][0] = H16<F>::mfma(TN2_FRAG(BLO[0], BHI[0]), af__, acc[I][0]);    \
-    acc[I][1] = H16<F>::mfma(TN2_FRAG(BLO[1], BHI[1]), af__, acc[I][1]);    \
-    acc[I][2] = H16<F>::mfma(TN2_FRAG(BLO[2], BHI[2]), af__, acc[I][2]);    \
-    acc[I][3] = H16<F>::mfma(TN2_FRAG(BLO[3], BHI[3]), af__, acc[I][3]);    \
-    if (do_bias) {                                                                                              \
-      _Pragma("unroll") for (int e__ = 0; e__ < 4; ++e__)                                                       \
-          bsum[I] += H16<F>::one(ALO[e__]) + H16<F>::one(AHI[e__]);                                           \
-    }                                                                                                           \
-  } while (0)
-#define TN2_SB __builtin_amdgcn_sched_barrier(0)
 #define TN2_ONE_A(ST, J) tn2_stage_one(XS_A((ST) + 2), lda, XS_K0((ST) + 2), lds0 + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, J, oa[J])
 #define TN2_ONE_B(ST, J) tn2_stage_one(XS_B((ST) + 2), ldb, XS_K0((ST) + 2), lds0 + 32768u + (uint32_t)(((ST) & 1) * TN2_STAGE), wave, J, ob[J])
-#define XS_ZERO_TAIL(BUF)                                                                                       \
+#define XS_ZERO_TAIL(BUF) TN2_ZERO_TAIL(smem + (BUF) * TN2_STAGE, (ke - kb) - (nks - 1) * 64)
+  // what follows the barrier that ends stage ST (p3.h, TN2_STEP): start stage ST + 2, zero stage ST + 1 if it is a ragged one
+#define TN2_BOUNDARY(ST, SPREAD)                                                                                \
   do {                                                                                                          \
-    const int valid__ = (ke - kb) - (nks - 1) * 64;                                                             \
-    char* sp__ = smem + (BUF) * TN2_STAGE;                                                                      \
-    for (int idx = tid; idx < 64 * 64; idx += 512) {                                                            \
-      const int kr = idx >> 6, c16 = idx & 63;                                                                  \
-      if (kr >= valid__) *reinterpret_cast<uint4*>(sp__ + kr * 512 + (c16 & 31) * 16 + (c16 >> 5) * 32768) = make_uint4(0, 0, 0, 0); \
-    }                                                                                                           \
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                             \
+    const int s2__ = (ST) + 2;                                                                                  \
+    SPREAD = s2__ < nst && XS_FULL(s2__);                                                                       \
+    if (SPREAD) { TN2_ONE_A(ST, 0); pend = true; }                                                              \
+    else if (s2__ < nst)                                                                                        \
+      tn2_stage(XS_A(s2__), lda, m0, M, XS_B(s2__), ldb, n0, N, XS_K0(s2__), ke, smem + ((ST) & 1) * TN2_STAGE, wave, lane, 0); \
+    if (ragged && (ST) + 1 < nst && XS_KS((ST) + 1) == nks - 1) XS_ZERO_TAIL(((ST) + 1) & 1);                   \
   } while (0)
 
   if (nks == 1 && ragged) XS_ZERO_TAIL(0);        // stage 0 itself is ragged: zero before anything is consumed
-  {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      TN2_RD(al_lo[i], al_hi[i], TN2_ADDR_LO(lds0, 0u, wr * 8 + i), TN2_ADDR_HI(lds0, 0u, wr * 8 + i));
-      TN2_RD(bx_lo[i], bx_hi[i], TN2_ADDR_LO(lds0, 32768u, wc * 4 + i), TN2_ADDR_HI(lds0, 32768u, wc * 4 + i));
-    }
-  }
-
-  // one k-step (32 tokens): CUR = k-step base address, NXT = next k-step base address
-#define TN2_STEP(CUR, NXT, BCL, BCH, BNL, BNH, SYNC, ST)                                                        \
-  do {                                                                                                          \
-    const uint32_t cur__ = (CUR), nxt__ = (NXT);                                                                \
-    bool spread__ = false;                                                                                      \
-    const bool tail__ = !(SYNC) && pend;       /* second half of the previous boundary's stage */               \
-    TN2_SB; TN2_MFMA_ROW(0, al_lo[0], al_hi[0], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(ah_lo[0], ah_hi[0], TN2_ADDR_LO(cur__, 0u, wr * 8 + 4), TN2_ADDR_HI(cur__, 0u, wr * 8 + 4));         \
-    TN2_RD(ah_lo[1], ah_hi[1], TN2_ADDR_LO(cur__, 0u, wr * 8 + 5), TN2_ADDR_HI(cur__, 0u, wr * 8 + 5));         \
-    if (tail__) TN2_ONE_A((ST) - 1, 2);                                                                         \
-    TN2_SB; TN2_MFMA_ROW(1, al_lo[1], al_hi[1], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(ah_lo[2], ah_hi[2], TN2_ADDR_LO(cur__, 0u, wr * 8 + 6), TN2_ADDR_HI(cur__, 0u, wr * 8 + 6));         \
-    TN2_RD(ah_lo[3], ah_hi[3], TN2_ADDR_LO(cur__, 0u, wr * 8 + 7), TN2_ADDR_HI(cur__, 0u, wr * 8 + 7));         \
-    if (tail__) TN2_ONE_B((ST) - 1, 2);                                                                         \
-    TN2_SB; TN2_MFMA_ROW(2, al_lo[2], al_hi[2], BCL, BCH);                                                      \
-    if (tail__) TN2_ONE_A((ST) - 1, 3);                                                                         \
-    TN2_SB; TN2_MFMA_ROW(3, al_lo[3], al_hi[3], BCL, BCH);                                                      \
-    if (tail__) { TN2_ONE_B((ST) - 1, 3); pend = false; }                                                       \
-    TN2_SB;                                                                                                     \
-    if (SYNC) {                                                                                                 \
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");                                             \
-      const int s2__ = (ST) + 2;                                                                                \
-      spread__ = s2__ < nst && XS_FULL(s2__);                                                                   \
-      if (spread__) { TN2_ONE_A(ST, 0); pend = true; }                                                          \
-      else if (s2__ < nst)                                                                                      \
-        tn2_stage(XS_A(s2__), lda, m0, M, XS_B(s2__), ldb, n0, N, XS_K0(s2__), ke, smem + ((ST) & 1) * TN2_STAGE, wave, lane, 0); \
-      if (ragged && (ST) + 1 < nst && XS_KS((ST) + 1) == nks - 1) XS_ZERO_TAIL(((ST) + 1) & 1);                 \
-    }                                                                                                           \
-    TN2_SB; TN2_MFMA_ROW(4, ah_lo[0], ah_hi[0], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(al_lo[0], al_hi[0], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 0), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 0));         \
-    TN2_RD(BNL[0], BNH[0], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 0), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 0));     \
-    TN2_RD(al_lo[1], al_hi[1], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 1), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 1));         \
-    if (SYNC && spread__) TN2_ONE_B(ST, 0);                                                                     \
-    TN2_SB; TN2_MFMA_ROW(5, ah_lo[1], ah_hi[1], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(BNL[1], BNH[1], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 1), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 1));     \
-    TN2_RD(al_lo[2], al_hi[2], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 2), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 2));         \
-    TN2_RD(BNL[2], BNH[2], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 2), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 2));     \
-    if (SYNC && spread__) TN2_ONE_A(ST, 1);                                                                     \
-    TN2_SB; TN2_MFMA_ROW(6, ah_lo[2], ah_hi[2], BCL, BCH); TN2_SB;                                              \
-    TN2_RD(al_lo[3], al_hi[3], TN2_ADDR_LO(nxt__, 0u, wr * 8 + 3), TN2_ADDR_HI(nxt__, 0u, wr * 8 + 3));         \
-    TN2_RD(BNL[3], BNH[3], TN2_ADDR_LO(nxt__, 32768u, wc * 4 + 3), TN2_ADDR_HI(nxt__, 32768u, wc * 4 + 3));     \
-    if (SYNC && spread__) TN2_ONE_B(ST, 1);                                                                     \
-    TN2_SB; TN2_MFMA_ROW(7, ah_lo[3], ah_hi[3], BCL, BCH);                                                      \
-    TN2_SB;                                                                                                     \
-  } while (0)
+  TN2_FIRST_FRAGS(lds0);
 
   bool pend = false;
   for (int st = 0; st < nst; ++st) {
@@ -591,44 +426,13 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_xp_kernel(
     TN2_STEP(sc, sc + 32 * 512, bx_lo, bx_hi, by_lo, by_hi, false, st);
     TN2_STEP(sc + 32 * 512, sn, by_lo, by_hi, bx_lo, bx_hi, true, st);
   }
-#undef TN2_STEP
-
   float* o = out + (long)split * slab_stride;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int m = m0 + wr * 128 + i * 16 + fs;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wc * 64 + j * 16 + fg * 4;
-      if (n >= N) continue;
-      float4* dst = reinterpret_cast<float4*>(o + (long)m * ldo + n);
-      float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      if (accumulate) { float4 c = *dst; v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w; }
-      *dst = v;
-    }
-  }
-  if (dbias != nullptr) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float t = bsum[i];
-      t += __shfl_xor(t, 16, 64);
-      t += __shfl_xor(t, 32, 64);
-      const int m = m0 + wr * 128 + i * 16 + fs;
-      if (fg == 0 && m < M) {
-        if (dbias_parts) dbias[(long)(split * bias_mod + bias_slot) * M + m] = t;
-        else atomicAdd(dbias + m, t);
-      }
-    }
-  }
+  TN_STORE_TILES(8, o, m0 + wr * 128, n0 + wc * 64, TN_KEEP);
+  TN_FLUSH_DBIAS(TN_KEEP);
+#undef TN2_BOUNDARY
 #undef XS_ZERO_TAIL
 #undef TN2_ONE_A
 #undef TN2_ONE_B
-#undef TN2_SB
-#undef TN2_MFMA_ROW
-#undef TN2_FRAG
-#undef TN2_ADDR_LO
-#undef TN2_ADDR_HI
 #undef XS_A
 #undef XS_B
 #undef XS_K0
@@ -662,15 +466,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_xq_kernel(
   const int kb = split * k_per_split;
   const int ke = min(K, kb + k_per_split);
   const int fs = lane & 15, fg = lane >> 4;
-  const int bias_slot = (tile % tiles_n) * 4 + wc, bias_mod = tiles_n * 4;
-  bool do_bias = false;
 
   f32x4 acc[8][4];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
   const int nst = (ke - kb + 31) / 32;             // 32-token stages
   const int last_valid = (ke - kb) - (nst - 1) * 32;               // rows of the last stage (32 = not ragged)
@@ -720,51 +521,40 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_xq_kernel(
   if (nst == 1 && last_valid < 32) XQ_ZERO_TAIL(0);
 
   bf16x4 al_lo[4], al_hi[4], ah_lo[4], ah_hi[4], bx_lo[4], bx_hi[4], by_lo[4], by_hi[4];
-#define XQ_ADDR_LO(TILE, CT) ((TILE) + row_lo + (uint32_t)((((CT)) ^ x_lo) << 5))
-#define XQ_ADDR_HI(TILE, CT) ((TILE) + row_hi + (uint32_t)((((CT)) ^ x_hi) << 5))
-#define TN2_FRAG(LO, HI) ((bf16x8){LO[0], LO[1], LO[2], LO[3], HI[0], HI[1], HI[2], HI[3]})
-#define XQ_MFMA_ROW(I, ALO, AHI, BLO, BHI, BIAS)                                                                \
-  do {                                                                                                          \
-    const bf16x8 af__ = TN2_FRAG(ALO, AHI);                                                                     \
-    acc[I][0] = H16<F>::mfma(TN2_FRAG(BLO[0], BHI[0]), af__, acc[I][0]);    \
-    acc[I][1] = H16<F>::mfma(TN2_FRAG(BLO[1], BHI[1]), af__, acc[I][1]);    \
-    acc[I][2] = H16<F>::mfma(TN2_FRAG(BLO[2], BHI[2]), af__, acc[I][2]);    \
-    acc[I][3] = H16<F>::mfma(TN2_FRAG(BLO[3], BHI[3]), af__, acc[I][3]);    \
-    if (false && (BIAS) && do_bias) {                                                                                    \
-      _Pragma("unroll") for (int e__ = 0; e__ < 4; ++e__)                                                       \
-          bsum[I] += H16<F>::one(ALO[e__]) + H16<F>::one(AHI[e__]);                                           \
-    }                                                                                                           \
-  } while (0)
-#define XQ_SB __builtin_amdgcn_sched_barrier(0)
+  // (p3.h: TN2_ADDR_LO / HI with no operand offset, TN2_FRAG, TN2_RD; the MFMA row is TN2_MFMA_ROW without its bias part)
+#define XQ_MFMA_ROW(I, ALO, AHI, BLO, BHI) do { TN2_MFMA4(I, ALO, AHI, BLO, BHI); } while (0)
   {   // fragments of k-step 0 of stage 0: A rows 0-3 of Ahi, B = Blo
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      TN2_RD(al_lo[i], al_hi[i], XQ_ADDR_LO(lds0, wr * 8 + i), XQ_ADDR_HI(lds0, wr * 8 + i));
-      TN2_RD(bx_lo[i], bx_hi[i], XQ_ADDR_LO(lds0 + 49152u, wc * 4 + i), XQ_ADDR_HI(lds0 + 49152u, wc * 4 + i));
+      TN2_RD(al_lo[i], al_hi[i], TN2_ADDR_LO(lds0, 0u, wr * 8 + i), TN2_ADDR_HI(lds0, 0u, wr * 8 + i));
+      TN2_RD(bx_lo[i], bx_hi[i], TN2_ADDR_LO(lds0 + 49152u, 0u, wc * 4 + i), TN2_ADDR_HI(lds0 + 49152u, 0u, wc * 4 + i));
     }
   }
   // one k-step (32 tokens of one term).  CURA: this k-step's A tile (its row fragments 4-7 are read here), NXTA / NXTB: the
   // next k-step's A and B tiles (A row fragments 0-3 and the B fragments are read here; RDB = 0: the next k-step keeps this
   // one's B fragments).  SYNC: the stage boundary sits in the middle of this k-step (every fragment of the stage's tiles
-  // that is still needed has been issued before it).  PIECES: 1 = first half of the next-next stage's DMA pieces, 2 = second.
-#define XQ_STEP(CURA, NXTA, NXTB, BCL, BCH, BNL, BNH, RDB, BIAS, SYNC, ST)                                      \
+  // that is still needed has been issued before it).  KS: the k-step's number within the stage (the second half of the DMA
+  // pieces a boundary started goes out under k-step 0).
+  // (Not p3.h's TN2_STEP: separate next-A / next-B tiles, the optional B read and a boundary every THIRD k-step would each be a
+  // parameter of the shared macro, which the two kernels that have none of them would then carry.)
+#define XQ_STEP(CURA, NXTA, NXTB, BCL, BCH, BNL, BNH, RDB, KS, SYNC, ST)                                        \
   do {                                                                                                          \
     const uint32_t cur__ = (CURA), nxa__ = (NXTA), nxb__ = (NXTB);                                              \
     bool spread__ = false;                                                                                      \
-    const bool tail__ = !(SYNC) && pend && (BIAS) == 0;       /* second half of the previous boundary's stage (k-step 0 only) */ \
-    XQ_SB; XQ_MFMA_ROW(0, al_lo[0], al_hi[0], BCL, BCH, BIAS); XQ_SB;                                           \
-    TN2_RD(ah_lo[0], ah_hi[0], XQ_ADDR_LO(cur__, wr * 8 + 4), XQ_ADDR_HI(cur__, wr * 8 + 4));                   \
-    TN2_RD(ah_lo[1], ah_hi[1], XQ_ADDR_LO(cur__, wr * 8 + 5), XQ_ADDR_HI(cur__, wr * 8 + 5));                   \
+    const bool tail__ = !(SYNC) && pend && (KS) == 0;         /* second half of the previous boundary's stage (k-step 0 only) */ \
+    TN2_SB; XQ_MFMA_ROW(0, al_lo[0], al_hi[0], BCL, BCH); TN2_SB;                                               \
+    TN2_RD(ah_lo[0], ah_hi[0], TN2_ADDR_LO(cur__, 0u, wr * 8 + 4), TN2_ADDR_HI(cur__, 0u, wr * 8 + 4));         \
+    TN2_RD(ah_lo[1], ah_hi[1], TN2_ADDR_LO(cur__, 0u, wr * 8 + 5), TN2_ADDR_HI(cur__, 0u, wr * 8 + 5));         \
     if (tail__) XQ_ONE_A((ST) + 1, 2);                                                                          \
-    XQ_SB; XQ_MFMA_ROW(1, al_lo[1], al_hi[1], BCL, BCH, BIAS); XQ_SB;                                           \
-    TN2_RD(ah_lo[2], ah_hi[2], XQ_ADDR_LO(cur__, wr * 8 + 6), XQ_ADDR_HI(cur__, wr * 8 + 6));                   \
-    TN2_RD(ah_lo[3], ah_hi[3], XQ_ADDR_LO(cur__, wr * 8 + 7), XQ_ADDR_HI(cur__, wr * 8 + 7));                   \
+    TN2_SB; XQ_MFMA_ROW(1, al_lo[1], al_hi[1], BCL, BCH); TN2_SB;                                               \
+    TN2_RD(ah_lo[2], ah_hi[2], TN2_ADDR_LO(cur__, 0u, wr * 8 + 6), TN2_ADDR_HI(cur__, 0u, wr * 8 + 6));         \
+    TN2_RD(ah_lo[3], ah_hi[3], TN2_ADDR_LO(cur__, 0u, wr * 8 + 7), TN2_ADDR_HI(cur__, 0u, wr * 8 + 7));         \
     if (tail__) XQ_ONE_B((ST) + 1, 2);                                                                          \
-    XQ_SB; XQ_MFMA_ROW(2, al_lo[2], al_hi[2], BCL, BCH, BIAS);                                                  \
+    TN2_SB; XQ_MFMA_ROW(2, al_lo[2], al_hi[2], BCL, BCH);                                                       \
     if (tail__) XQ_ONE_A((ST) + 1, 3);                                                                          \
-    XQ_SB; XQ_MFMA_ROW(3, al_lo[3], al_hi[3], BCL, BCH, BIAS);                                                  \
+    TN2_SB; XQ_MFMA_ROW(3, al_lo[3], al_hi[3], BCL, BCH);                                                       \
     if (tail__) { XQ_ONE_B((ST) + 1, 3); pend = false; }                                                        \
-    XQ_SB;                                                                                                      \
+    TN2_SB;                                                                                                     \
     if (SYNC) {                                                                                                 \
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");                                             \
       const int s2__ = (ST) + 2;                                                                                \
@@ -773,74 +563,42 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_xq_kernel(
       else if (s2__ < nst) stage_clamped(s2__, XQ_VALID(s2__));                                                 \
       if ((ST) + 1 == nst - 1 && last_valid < 32) XQ_ZERO_TAIL(((ST) + 1) & 1);                                 \
     }                                                                                                           \
-    XQ_SB; XQ_MFMA_ROW(4, ah_lo[0], ah_hi[0], BCL, BCH, BIAS); XQ_SB;                                           \
-    TN2_RD(al_lo[0], al_hi[0], XQ_ADDR_LO(nxa__, wr * 8 + 0), XQ_ADDR_HI(nxa__, wr * 8 + 0));                   \
-    if (RDB) TN2_RD(BNL[0], BNH[0], XQ_ADDR_LO(nxb__, wc * 4 + 0), XQ_ADDR_HI(nxb__, wc * 4 + 0));              \
-    TN2_RD(al_lo[1], al_hi[1], XQ_ADDR_LO(nxa__, wr * 8 + 1), XQ_ADDR_HI(nxa__, wr * 8 + 1));                   \
+    TN2_SB; XQ_MFMA_ROW(4, ah_lo[0], ah_hi[0], BCL, BCH); TN2_SB;                                               \
+    TN2_RD(al_lo[0], al_hi[0], TN2_ADDR_LO(nxa__, 0u, wr * 8 + 0), TN2_ADDR_HI(nxa__, 0u, wr * 8 + 0));         \
+    if (RDB) TN2_RD(BNL[0], BNH[0], TN2_ADDR_LO(nxb__, 0u, wc * 4 + 0), TN2_ADDR_HI(nxb__, 0u, wc * 4 + 0));    \
+    TN2_RD(al_lo[1], al_hi[1], TN2_ADDR_LO(nxa__, 0u, wr * 8 + 1), TN2_ADDR_HI(nxa__, 0u, wr * 8 + 1));         \
     if (SYNC && spread__) XQ_ONE_B((ST) + 2, 0);                                                                \
-    XQ_SB; XQ_MFMA_ROW(5, ah_lo[1], ah_hi[1], BCL, BCH, BIAS); XQ_SB;                                           \
-    if (RDB) TN2_RD(BNL[1], BNH[1], XQ_ADDR_LO(nxb__, wc * 4 + 1), XQ_ADDR_HI(nxb__, wc * 4 + 1));              \
-    TN2_RD(al_lo[2], al_hi[2], XQ_ADDR_LO(nxa__, wr * 8 + 2), XQ_ADDR_HI(nxa__, wr * 8 + 2));                   \
-    if (RDB) TN2_RD(BNL[2], BNH[2], XQ_ADDR_LO(nxb__, wc * 4 + 2), XQ_ADDR_HI(nxb__, wc * 4 + 2));              \
+    TN2_SB; XQ_MFMA_ROW(5, ah_lo[1], ah_hi[1], BCL, BCH); TN2_SB;                                               \
+    if (RDB) TN2_RD(BNL[1], BNH[1], TN2_ADDR_LO(nxb__, 0u, wc * 4 + 1), TN2_ADDR_HI(nxb__, 0u, wc * 4 + 1));    \
+    TN2_RD(al_lo[2], al_hi[2], TN2_ADDR_LO(nxa__, 0u, wr * 8 + 2), TN2_ADDR_HI(nxa__, 0u, wr * 8 + 2));         \
+    if (RDB) TN2_RD(BNL[2], BNH[2], TN2_ADDR_LO(nxb__, 0u, wc * 4 + 2), TN2_ADDR_HI(nxb__, 0u, wc * 4 + 2));    \
     if (SYNC && spread__) XQ_ONE_A((ST) + 2, 1);                                                                \
-    XQ_SB; XQ_MFMA_ROW(6, ah_lo[2], ah_hi[2], BCL, BCH, BIAS); XQ_SB;                                           \
-    TN2_RD(al_lo[3], al_hi[3], XQ_ADDR_LO(nxa__, wr * 8 + 3), XQ_ADDR_HI(nxa__, wr * 8 + 3));                   \
-    if (RDB) TN2_RD(BNL[3], BNH[3], XQ_ADDR_LO(nxb__, wc * 4 + 3), XQ_ADDR_HI(nxb__, wc * 4 + 3));              \
+    TN2_SB; XQ_MFMA_ROW(6, ah_lo[2], ah_hi[2], BCL, BCH); TN2_SB;                                               \
+    TN2_RD(al_lo[3], al_hi[3], TN2_ADDR_LO(nxa__, 0u, wr * 8 + 3), TN2_ADDR_HI(nxa__, 0u, wr * 8 + 3));         \
+    if (RDB) TN2_RD(BNL[3], BNH[3], TN2_ADDR_LO(nxb__, 0u, wc * 4 + 3), TN2_ADDR_HI(nxb__, 0u, wc * 4 + 3));    \
     if (SYNC && spread__) XQ_ONE_B((ST) + 2, 1);                                                                \
-    XQ_SB; XQ_MFMA_ROW(7, ah_lo[3], ah_hi[3], BCL, BCH, BIAS);                                                  \
-    XQ_SB;                                                                                                      \
+    TN2_SB; XQ_MFMA_ROW(7, ah_lo[3], ah_hi[3], BCL, BCH);                                                       \
+    TN2_SB;                                                                                                     \
   } while (0)
 
   bool pend = false;
   for (int st = 0; st < nst; ++st) {
     const uint32_t sc = lds0 + (uint32_t)((st & 1) * TN2_STAGE), sn = lds0 + (uint32_t)(((st + 1) & 1) * TN2_STAGE);
-    do_bias = dbias != nullptr && (st % bias_mod) == bias_slot;
     // Ahi.Blo (bx) ; Alo.Bhi (by) ; Ahi.Bhi (by, kept) -- the last k-step reads the next stage's Ahi rows 0-3 and Blo
     XQ_STEP(sc, sc + 16384u, sc + 32768u, bx_lo, bx_hi, by_lo, by_hi, 1, 0, false, st);
     XQ_STEP(sc + 16384u, sc, sc + 32768u, by_lo, by_hi, by_lo, by_hi, 0, 1, false, st);
     XQ_STEP(sc, sn, sn + 49152u, by_lo, by_hi, bx_lo, bx_hi, 1, 2, true, st);
   }
 #undef XQ_STEP
-
   float* o = out + (long)split * slab_stride;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int m = m0 + wr * 128 + i * 16 + fs;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wc * 64 + j * 16 + fg * 4;
-      if (n >= N) continue;
-      float4* dst = reinterpret_cast<float4*>(o + (long)m * ldo + n);
-      float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-      if (accumulate) { float4 c = *dst; v.x += c.x; v.y += c.y; v.z += c.z; v.w += c.w; }
-      *dst = v;
-    }
-  }
-  if (false && dbias != nullptr) {              // (this kernel carries no fused bias gradient: see the header comment)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float t = bsum[i];
-      t += __shfl_xor(t, 16, 64);
-      t += __shfl_xor(t, 32, 64);
-      const int m = m0 + wr * 128 + i * 16 + fs;
-      if (fg == 0 && m < M) {
-        if (dbias_parts) dbias[(long)(split * bias_mod + bias_slot) * M + m] = t;
-        else atomicAdd(dbias + m, t);
-      }
-    }
-  }
+  TN_STORE_TILES(8, o, m0 + wr * 128, n0 + wc * 64, TN_KEEP);
 #undef XQ_ZERO_TAIL
 #undef stage_clamped
 #undef XQ_CLAMPED_ONE
 #undef XQ_VALID
 #undef XQ_ONE_A
 #undef XQ_ONE_B
-#undef XQ_SB
 #undef XQ_MFMA_ROW
-#undef TN2_FRAG
-#undef XQ_ADDR_LO
-#undef XQ_ADDR_HI
 }
 
 // ------------------------------------------------------------------------------------------ plane producers of last resort
