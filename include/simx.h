@@ -489,10 +489,15 @@ int simx_seq_mean_bwd_gs(simx_stream_t stream, int dtype, int nseq, int H, const
  *   SIMX_LOSS_WIKI  L2  adv_lambda*adv + (1-adv_lambda)*normal                            co_training_wiki_train.py:203-228
  *   SIMX_LOSS_CEKD  L3  ce_w*NLL(target 0) + kd_w*T^2*KL(softmax(z/T)||softmax(s/T))    PROD/ProD_KD/model/models.py:668-781
  *   SIMX_LOSS_CE    L6  CrossEntropy(target 0) on s itself                                co_training_marco_train.py:228-236
+ * and the other KD_type objectives of CrossBERTKDLoss, each ce_w*NLL(target 0) + kd_w*soft (PROD/ProD_KD/model/models.py):
+ *   SIMX_LOSS_CE_LOGIT  KD_logit   soft = 0.5*mean_{b,d}(s - z)^2 (temperature unused)                        :778-780
+ *   SIMX_LOSS_CE_DKD    DKD        soft = dkd_alpha*tckd + dkd_beta*nckd, target column 0                      :784-808
+ *   SIMX_LOSS_CE_PROB   prob_loss  soft = -(1/B) sum softmax(z/T) log(softmax(s) + 1e-7)                       :738-743
  * q [B,H], ctx [B*D,H], teacher [B,D] (ignored for CE) ; outputs: sim [B,D], losses[4] =
  * {loss, aux0, aux1, correct_count}, dq [B,H], dctx [B*D,H] (gradients already divided by grad_accum).
  * If q == NULL the D logits are read from `sim` directly (no similarity, dctx receives ds [B,D]). */
-enum { SIMX_LOSS_KL = 0, SIMX_LOSS_WIKI = 1, SIMX_LOSS_CEKD = 2, SIMX_LOSS_CE = 3 };
+enum { SIMX_LOSS_KL = 0, SIMX_LOSS_WIKI = 1, SIMX_LOSS_CEKD = 2, SIMX_LOSS_CE = 3,
+       SIMX_LOSS_CE_LOGIT = 4, SIMX_LOSS_CE_DKD = 5, SIMX_LOSS_CE_PROB = 6 };
 typedef struct simx_loss_params {
   int32_t kind;
   float scale;          /* 1 or 1/sqrt(H) (--scale_simmila) */
@@ -500,6 +505,7 @@ typedef struct simx_loss_params {
   float adv_lambda;     /* L2 */
   float ce_w, kd_w;     /* L3 */
   float grad_accum;     /* loss and grads divided by this */
+  float dkd_alpha, dkd_beta;   /* SIMX_LOSS_CE_DKD: weights of the target-class and the non-target-class term */
 } simx_loss_params;
 int simx_sim_loss_fwd_bwd(simx_stream_t stream, int B, int D, int H,
                           const float* q, const float* ctx, const float* teacher,
@@ -531,6 +537,20 @@ int simx_scores_kd_fwd_bwd(simx_stream_t stream, int Q, int C, int H, int HT,
                            int q_lo, int q_n, int c_lo, int c_n,
                            float* scores, float* tscores, float* losses, float* dq_local, float* dctx_local,
                            void* ws, size_t ws_bytes);
+/* The same call for every KD_type of BiEncoderKDLoss.calc (:1006-1028); simx_scores_kd_fwd_bwd is kd_type SIMX_KD_SOFTMAX.
+ *   SIMX_KD_LOGIT     soft = 0.5 * mean_{q,c}(S - Z)^2                                         (kd_loss, :1056-1058)
+ *   SIMX_KD_DKD       soft = dkd_alpha*tckd + dkd_beta*nckd with pos_idx as the target column  (dkd_loss, :1070-1094)
+ *   SIMX_KD_BI_LOGIT  soft = 0.5*MSE(q, tq) + 0.5*MSE(ctx, tctx) on the embeddings themselves  (bi_logit, :1062-1067):
+ *                     needs HT == H, launches no teacher score product (tscores may be NULL), counts every gathered row
+ *                     in the loss and adds kd_w*loss_scale*(x - t)/(rows*H) to the local rows' gradients only.
+ * Any other kd_type returns SIMX_ERR_UNSUPPORTED. */
+enum { SIMX_KD_SOFTMAX = 0, SIMX_KD_LOGIT = 1, SIMX_KD_DKD = 2, SIMX_KD_BI_LOGIT = 3 };
+int simx_scores_kd_type_fwd_bwd(simx_stream_t stream, int kd_type, int Q, int C, int H, int HT,
+                                const float* q, const float* ctx, const float* tq, const float* tctx,
+                                const int32_t* pos_idx, float temperature, float ce_w, float kd_w, float dkd_alpha,
+                                float dkd_beta, float loss_scale, int q_lo, int q_n, int c_lo, int c_n,
+                                float* scores, float* tscores, float* losses, float* dq_local, float* dctx_local,
+                                void* ws, size_t ws_bytes);
 
 /* -------------------------------------------------------------- D1: device-side batch assembly
  * The collate of SimANS/utils/MARCO_until_new.py:204-258 (Rocketqa_v2Dataset.__getitem__ tail +

@@ -9,8 +9,10 @@ libsimx_hip.so.  What differs from the SimANS classes (simxns_amd/model/models.p
   * BiBertEncoder(args, role) (models.py:208-256);
   * Reranker carries a second head `binary = Linear(H, 2)` and returns (binary_logits [N,M,2], relevance_logits [N,M],
     None) (models.py:1232-1254);
-  * CrossBERTKDLoss / BiEncoderKDLoss / BiEncoderNllLoss are the loss classes of the same file (re-exported).
-Out of scope: ColBERT, DistilBERT students, the KD_logit / DKD loss variants.
+  * CrossBERTKDLoss / BiEncoderKDLoss / BiEncoderNllLoss are the loss classes of the same file (re-exported), with every
+    args.KD_type the reference has: KD_softmax, KD_logit, DKD (args.DKD_alpha, args.DKD_beta), prob_loss (cross-encoder
+    teacher), Bi_logit (dual-encoder teacher).
+Out of scope: ColBERT, DistilBERT students.
 """
 import torch
 from torch import nn

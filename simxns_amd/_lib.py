@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(_HERE, "libsimx_hip.so")
 
 SIMX_F32, SIMX_BF16, SIMX_F16, SIMX_F32_SPLIT_H, SIMX_F32_SPLIT_B = 0, 1, 2, 3, 4
 EPI_NONE, EPI_GELU, EPI_DGELU = 0, 1, 2
-LOSS_KL, LOSS_WIKI, LOSS_CEKD, LOSS_CE = 0, 1, 2, 3
+LOSS_KL, LOSS_WIKI, LOSS_CEKD, LOSS_CE, LOSS_CE_LOGIT, LOSS_CE_DKD, LOSS_CE_PROB = 0, 1, 2, 3, 4, 5, 6
+KD_SOFTMAX, KD_LOGIT, KD_DKD, KD_BI_LOGIT = 0, 1, 2, 3
 (P_WORD, P_POS, P_TYPE, P_EMB_LN_G, P_EMB_LN_B, P_WQKV, P_BQKV, P_WO, P_BO, P_LN1_G, P_LN1_B,
  P_W1, P_B1, P_W2, P_B2, P_LN2_G, P_LN2_B, P_POOL_W, P_POOL_B) = range(19)
 
@@ -36,7 +37,8 @@ class Dropout(C.Structure):
 
 class LossParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("scale", C.c_float), ("temperature", C.c_float), ("adv_lambda", C.c_float),
-                ("ce_w", C.c_float), ("kd_w", C.c_float), ("grad_accum", C.c_float)]
+                ("ce_w", C.c_float), ("kd_w", C.c_float), ("grad_accum", C.c_float), ("dkd_alpha", C.c_float),
+                ("dkd_beta", C.c_float)]
 
 
 _p, _i, _f, _d, _z, _l = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_long
@@ -100,6 +102,8 @@ SIGNATURES = {
     "simx_scores_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "simx_scores_nll_fwd_bwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z]),
     "simx_scores_kd_fwd_bwd": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z]),
+    "simx_scores_kd_type_fwd_bwd": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p,
+                                         _p, _z]),
     "simx_gemm_f32_workspace_bytes": (_z, [_i, _i, _i]),
     "simx_assemble_batch": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "simx_ip_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, C.c_long]),

@@ -1,9 +1,11 @@
 // Similarity + loss kernels (f32): wavefront-reduction kernels, one wave per query row.
-//   sim_loss_kernel : M1 einsum("bh,bdh->bd") + {L1 KL-distill, L2 NQ/TQ normal+adv, L3 CE+KD, L6 CE}
+//   sim_loss_kernel : M1 einsum("bh,bdh->bd") + {L1 KL-distill, L2 NQ/TQ normal+adv, L3 CE+KD (every KD_type), L6 CE}
 //                     forward AND closed-form backward in one launch -- replaces the
 //                     5+ ATen launches and two .item() syncs of co_training_marco_train.py:199-224.
 //   nll rows        : M2 log_softmax / nll_loss / argmax over the all-pairs score matrix
 //                     (SimANS/model/models.py:468-505) and dS in place.
+//   kd rows         : L4 the same rows with the KD_type objectives of BiEncoderKDLoss against the teacher's all-pairs scores;
+//                     bi_logit_rows_kernel is its Bi_logit objective, an MSE on the embeddings themselves.
 #include "common.h"
 #include "prof.h"
 
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(256) void sim_loss_kernel(int B, int D, int H, cons
     if (lp.kind == SIMX_LOSS_CE) {
       l0 = hard; l1 = hard;
       ds = act ? (p - e0) * invB : 0.f;
-    } else {
+    } else if (lp.kind == SIMX_LOSS_CEKD) {
       const float Tm = lp.temperature;
       const float sT = s / Tm, zT = z / Tm;
       const float m1 = wave_max(act ? sT : NEG), m2 = wave_max(act ? zT : NEG);
@@ -109,6 +111,57 @@ __global__ __launch_bounds__(256) void sim_loss_kernel(int B, int D, int H, cons
       l1 = hard; l2 = soft;
       l0 = lp.ce_w * hard + lp.kd_w * soft;
       ds = act ? lp.ce_w * (p - e0) * invB + lp.kd_w * (Tm * invB) * (pT - u) : 0.f;
+    } else {
+      // the other KD_type objectives of CrossBERTKDLoss: soft and dsoft = d soft / d s[b,lane]
+      const float Tm = lp.temperature;
+      float soft, dsoft;
+      if (lp.kind == SIMX_LOSS_CE_LOGIT) {
+        // KD_logit (:778-780): 0.5 * mean over all B*D elements of (s - z)^2
+        const float inv = invB / (float)D;
+        const float df = act ? s - z : 0.f;
+        soft = 0.5f * wave_sum(df * df) * inv;
+        dsoft = df * inv;
+      } else {
+        const float zT = z / Tm;
+        const float m2 = wave_max(act ? zT : NEG);
+        const float e2 = act ? expf(zT - m2) : 0.f;
+        const float u = e2 / wave_sum(e2);                             // softmax(z / T)
+        if (lp.kind == SIMX_LOSS_CE_PROB) {
+          // prob_loss (:738-743): -(1/B) sum u log(softmax(s) + eps), the student without temperature
+          const float lp_eps = logf(p + LOSS_EPS);
+          soft = wave_sum(act ? -u * lp_eps : 0.f) * invB;
+          const float g = -u * invB / (p + LOSS_EPS);
+          const float gp = wave_sum(act ? g * p : 0.f);
+          dsoft = act ? p * (g - gp) : 0.f;
+        } else {
+          // DKD (dkd_loss, :784-808), target column 0.  tckd: KL of the two-bin distributions {target, all others}, the
+          // "others" bin a sum over the non-target lanes as cat_mask forms it; nckd: KL of the softmaxes with 1000 taken
+          // off the target logit.
+          const float sT = s / Tm;
+          const float m1 = wave_max(act ? sT : NEG);
+          const float e1 = act ? expf(sT - m1) : 0.f;
+          const float pT = e1 / wave_sum(e1);
+          const bool oth = act && lane != 0;
+          const float p_gt = __shfl(pT, 0, 64), u_gt = __shfl(u, 0, 64);
+          const float p_o = wave_sum(oth ? pT : 0.f), u_o = wave_sum(oth ? u : 0.f);
+          float tckd = 0.f;
+          if (u_gt > 0.f) tckd += u_gt * (logf(u_gt) - logf(p_gt));
+          if (u_o > 0.f) tckd += u_o * (logf(u_o) - logf(p_o));
+          const float sm = sT - 1000.0f * e0, zm = zT - 1000.0f * e0;
+          const float m3 = wave_max(act ? sm : NEG), m4 = wave_max(act ? zm : NEG);
+          const float e3 = act ? expf(sm - m3) : 0.f, e4 = act ? expf(zm - m4) : 0.f;
+          const float su3 = wave_sum(e3), su4 = wave_sum(e4);
+          const float pm = e3 / su3, um = e4 / su4;
+          const float lpm = sm - m3 - logf(su3);
+          const float nckd = wave_sum((act && um > 0.f) ? um * (logf(um) - lpm) : 0.f);
+          soft = (lp.dkd_alpha * tckd + lp.dkd_beta * nckd) * Tm * Tm * invB;
+          const float tc = lane == 0 ? pT - u : pT * (p_o - u_o) / p_o;
+          dsoft = act ? (Tm * invB) * (lp.dkd_alpha * tc + lp.dkd_beta * (pm - um)) : 0.f;
+        }
+      }
+      l1 = hard; l2 = soft;
+      l0 = lp.ce_w * hard + lp.kd_w * soft;
+      ds = act ? lp.ce_w * (p - e0) * invB + lp.kd_w * dsoft : 0.f;
     }
   }
   const float ga = 1.0f / lp.grad_accum;
@@ -224,6 +277,132 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(int Q, int C, float* __res
   }
 }
 
+// L4 rows for the other KD_type objectives of BiEncoderKDLoss (same launch shape, same in-place dS as kd_rows_kernel):
+//   SIMX_KD_LOGIT     soft = 0.5 * sum_c (S - Z)^2 / C                                    (kd_loss KD_logit, :1056-1058)
+//   SIMX_KD_DKD       soft = T^2 (alpha tckd + beta nckd), target column pos_idx[i]       (dkd_loss, :1070-1094)
+//   SIMX_KD_BI_LOGIT  soft = 0 here: the hard term only, Z is not read (bi_logit_rows_kernel adds the embedding MSE)
+template <int KD>
+__global__ __launch_bounds__(256) void kd_rows_type_kernel(int Q, int C, float* __restrict__ scores, const float* __restrict__ tscores,
+                                                           const int* __restrict__ pos_idx, float T, float ce_w, float kd_w,
+                                                           float alpha, float beta, float gscale, float lscale,
+                                                           float* __restrict__ losses, float* __restrict__ det_part) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + w;
+  if (i >= Q) return;
+  float* r = scores + (long)i * C;
+  const float* z = KD == SIMX_KD_BI_LOGIT ? nullptr : tscores + (long)i * C;
+  const int pos = pos_idx[i];
+  const float iT = 1.0f / T;
+  // maxima: of S (with its arg-max); DKD also of Z/T, and of S/T and Z/T with 1000 taken off the target column
+  float m = -INFINITY, mz = -INFINITY, mm = -INFINITY, mzm = -INFINITY;
+  int am = 0x7FFFFFFF;
+  for (int c = lane; c < C; c += 64) {
+    const float v = r[c];
+    if (v > m) { m = v; am = c; }
+    if (KD == SIMX_KD_DKD) {
+      const float zc = z[c] * iT, off = c == pos ? 1000.0f : 0.f;
+      mz = fmaxf(mz, zc);
+      mm = fmaxf(mm, v * iT - off);
+      mzm = fmaxf(mzm, zc - off);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oa = __shfl_xor(am, o, 64);
+    if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+  }
+  float s1 = 0.f, sT = 0.f, sTo = 0.f, sz = 0.f, szo = 0.f, sm = 0.f, szm = 0.f;
+  if (KD == SIMX_KD_DKD) { mz = wave_max(mz); mm = wave_max(mm); mzm = wave_max(mzm); }
+  for (int c = lane; c < C; c += 64) {
+    const float v = r[c];
+    s1 += expf(v - m);
+    if (KD == SIMX_KD_DKD) {
+      const bool gt = c == pos;
+      const float zc = z[c] * iT, off = gt ? 1000.0f : 0.f;
+      const float eT = expf((v - m) * iT), eZ = expf(zc - mz);
+      sT += eT; sz += eZ;
+      if (!gt) { sTo += eT; szo += eZ; }                // the "others" bin of cat_mask: a sum of the non-target terms
+      sm += expf(v * iT - off - mm);
+      szm += expf(zc - off - mzm);
+    }
+  }
+  s1 = wave_sum(s1);
+  const float lse = m + logf(s1);
+  const float sp = r[pos];
+  float lseT = 0.f, lseM = 0.f, lseZM = 0.f, u_gt = 0.f, ko = 0.f, tckd = 0.f;
+  if (KD == SIMX_KD_DKD) {
+    sT = wave_sum(sT); sTo = wave_sum(sTo); sz = wave_sum(sz); szo = wave_sum(szo); sm = wave_sum(sm); szm = wave_sum(szm);
+    lseT = m * iT + logf(sT); lseM = mm + logf(sm); lseZM = mzm + logf(szm);
+    const float p_gt = expf(sp * iT - lseT), p_o = sTo / sT, u_o = szo / sz;
+    u_gt = expf(z[pos] * iT - (mz + logf(sz)));
+    if (u_gt > 0.f) tckd += u_gt * (logf(u_gt) - logf(p_gt));
+    if (u_o > 0.f) tckd += u_o * (logf(u_o) - logf(p_o));
+    ko = (p_o - u_o) / p_o;
+  }
+  float soft = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = r[c];
+    const bool gt = c == pos;
+    const float p1 = expf(v - lse);
+    float d = 0.f;                                      // d soft / d S[i,c]
+    if (KD == SIMX_KD_LOGIT) {
+      const float df = v - z[c];
+      soft = fmaf(df, df, soft);
+      d = df / (float)C;
+    } else if (KD == SIMX_KD_DKD) {
+      const float off = gt ? 1000.0f : 0.f;
+      const float pT = expf(v * iT - lseT);
+      const float lpm = v * iT - off - lseM, lum = z[c] * iT - off - lseZM;
+      const float um = expf(lum);
+      if (um > 0.f) soft += um * (lum - lpm);
+      d = T * (alpha * (gt ? pT - u_gt : pT * ko) + beta * (expf(lpm) - um));
+    }
+    r[c] = gscale * (ce_w * (p1 - (gt ? 1.f : 0.f)) + kd_w * d);
+  }
+  soft = wave_sum(soft);
+  if (KD == SIMX_KD_LOGIT) soft *= 0.5f / (float)C;
+  if (KD == SIMX_KD_DKD) soft = (alpha * tckd + beta * soft) * T * T;
+  if (lane == 0) {
+    const float hard = lse - sp;
+    loss_row_out(losses, det_part, i, (ce_w * hard + kd_w * soft) * lscale / (float)Q, hard / (float)Q, soft / (float)Q, am == pos ? 1.f : 0.f);
+  }
+}
+
+// Bi_logit (bi_logit, :1062-1067): 0.5 * MSE(q, tq) + 0.5 * MSE(ctx, tctx) on the gathered embeddings, one wave per row
+// (rows [0,Q) = q, [Q,Q+C) = ctx).  Every row counts in the loss; only the local rows get kd_w * lscale * (x - t) / (rows * H)
+// added to the gradient the score products left in dq_local / dctx_local.
+__global__ __launch_bounds__(256) void bi_logit_rows_kernel(int Q, int C, int H, const float* __restrict__ q, const float* __restrict__ ctx,
+                                                            const float* __restrict__ tq, const float* __restrict__ tctx, float kd_w,
+                                                            float lscale, int q_lo, int q_n, int c_lo, int c_n,
+                                                            float* __restrict__ dq_local, float* __restrict__ dctx_local,
+                                                            float* __restrict__ losses, float* __restrict__ det_part) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + w;
+  if (i >= Q + C) return;
+  const bool isq = i < Q;
+  const int row = isq ? i : i - Q, rows = isq ? Q : C;
+  const int lo = isq ? q_lo : c_lo, n = isq ? q_n : c_n;
+  const float* x = (isq ? q : ctx) + (long)row * H;
+  const float* t = (isq ? tq : tctx) + (long)row * H;
+  float* d = isq ? dq_local : dctx_local;
+  const bool local = d != nullptr && row >= lo && row < lo + n;
+  if (local) d += (long)(row - lo) * H;
+  const float inv = 1.0f / ((float)rows * (float)H);
+  const float gw = kd_w * lscale * inv;
+  float acc = 0.f;
+  for (int h = lane; h < H; h += 64) {
+    const float df = x[h] - t[h];
+    acc = fmaf(df, df, acc);
+    if (local) d[h] += gw * df;
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) {
+    const float soft = 0.5f * acc * inv;
+    loss_row_out(losses, det_part, i, kd_w * lscale * soft, 0.f, soft, 0.f);
+  }
+}
+
 // strided f32 GEMM from gemm.hip
 extern "C" int simx_gemm_f32_strided(simx_stream_t stream, int M, int N, int K, const float* A, long a_rs, long a_cs,
                                      const float* B, long b_ks, long b_ns, float* C, int ldc, int accumulate);
@@ -245,7 +424,7 @@ extern "C" int simx_sim_loss_fwd_bwd(simx_stream_t stream, int B, int D, int H, 
   SIMX_PROF(SIMX_K_LOSS, s, 16.0 * B * D * (H > 0 ? H : 1));
   SIMX_REQUIRE(lp != nullptr, SIMX_ERR_BAD_SHAPE, "sim_loss: params are NULL");
   SIMX_REQUIRE(B > 0 && D > 0 && D <= 64, SIMX_ERR_UNSUPPORTED, "sim_loss: need 0 < D=%d <= 64", D);
-  SIMX_REQUIRE(lp->kind >= 0 && lp->kind <= 3, SIMX_ERR_UNSUPPORTED, "sim_loss: kind %d", lp->kind);
+  SIMX_REQUIRE(lp->kind >= 0 && lp->kind <= SIMX_LOSS_CE_PROB, SIMX_ERR_UNSUPPORTED, "sim_loss: kind %d", lp->kind);
   SIMX_REQUIRE(lp->kind == SIMX_LOSS_CE || teacher != nullptr, SIMX_ERR_BAD_SHAPE, "sim_loss: teacher logits missing");
   SIMX_REQUIRE(q == nullptr || (ctx && dq && H > 0), SIMX_ERR_BAD_SHAPE, "sim_loss: q given without ctx/dq");
   SIMX_REQUIRE(sim && losses && dctx, SIMX_ERR_BAD_SHAPE, "sim_loss: NULL output");
@@ -287,27 +466,42 @@ extern "C" int simx_scores_nll_fwd_bwd(simx_stream_t stream, int Q, int C, int H
   return SIMX_OK;
 }
 
-extern "C" int simx_scores_kd_fwd_bwd(simx_stream_t stream, int Q, int C, int H, int HT, const float* q, const float* ctx,
-                                      const float* tq, const float* tctx, const int32_t* pos_idx, float temperature,
-                                      float ce_w, float kd_w, float loss_scale, int q_lo, int q_n, int c_lo, int c_n,
-                                      float* scores, float* tscores, float* losses, float* dq_local, float* dctx_local,
-                                      void* ws, size_t ws_bytes) {
+extern "C" int simx_scores_kd_type_fwd_bwd(simx_stream_t stream, int kd_type, int Q, int C, int H, int HT, const float* q,
+                                           const float* ctx, const float* tq, const float* tctx, const int32_t* pos_idx,
+                                           float temperature, float ce_w, float kd_w, float dkd_alpha, float dkd_beta,
+                                           float loss_scale, int q_lo, int q_n, int c_lo, int c_n, float* scores, float* tscores,
+                                           float* losses, float* dq_local, float* dctx_local, void* ws, size_t ws_bytes) {
   hipStream_t s = (hipStream_t)stream;
+  SIMX_REQUIRE(kd_type >= SIMX_KD_SOFTMAX && kd_type <= SIMX_KD_BI_LOGIT, SIMX_ERR_UNSUPPORTED, "scores_kd: kd_type %d", kd_type);
+  const bool bi = kd_type == SIMX_KD_BI_LOGIT;
   SIMX_REQUIRE(Q > 0 && C > 0 && H > 0 && HT > 0, SIMX_ERR_BAD_SHAPE, "scores_kd: bad shape");
+  SIMX_REQUIRE(!bi || H == HT, SIMX_ERR_BAD_SHAPE, "scores_kd: Bi_logit compares embeddings, teacher width %d != student width %d", HT, H);
   SIMX_REQUIRE(temperature > 0.f, SIMX_ERR_BAD_SHAPE, "scores_kd: temperature must be > 0");
   SIMX_REQUIRE(q_lo >= 0 && q_n >= 0 && q_lo + q_n <= Q && c_lo >= 0 && c_n >= 0 && c_lo + c_n <= C, SIMX_ERR_BAD_SHAPE,
                "scores_kd: local slot out of range");
-  SIMX_REQUIRE(q && ctx && tq && tctx && pos_idx && scores && tscores && losses, SIMX_ERR_BAD_SHAPE, "scores_kd: NULL argument");
+  SIMX_REQUIRE(q && ctx && tq && tctx && pos_idx && scores && (tscores || bi) && losses, SIMX_ERR_BAD_SHAPE, "scores_kd: NULL argument");
   if (hipMemsetAsync(losses, 0, 4 * sizeof(float), s) != hipSuccess) { simx_set_error("scores_kd: memset failed"); return SIMX_ERR_HIP; }
   int rc = simx_gemm_f32_strided(stream, Q, C, H, q, H, 1, ctx, 1, H, scores, C, 0);          // S = q ctx^T
   if (rc) return rc;
-  rc = simx_gemm_f32_strided(stream, Q, C, HT, tq, HT, 1, tctx, 1, HT, tscores, C, 0);        // Z = tq tctx^T
-  if (rc) return rc;
+  if (!bi) {
+    rc = simx_gemm_f32_strided(stream, Q, C, HT, tq, HT, 1, tctx, 1, HT, tscores, C, 0);      // Z = tq tctx^T
+    if (rc) return rc;
+  }
   const float ls = loss_scale == 0.f ? 1.f : loss_scale;
   float* det = nullptr;
   if (int rcd = loss_det_begin(s, Q, &det)) return rcd;
-  hipLaunchKernelGGL(kd_rows_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, s, Q, C, scores, tscores, pos_idx, temperature, ce_w, kd_w,
-                     ls / (float)Q, ls, losses, det);
+  const dim3 grid(cdiv(Q, 4)), block(256);
+  if (kd_type == SIMX_KD_SOFTMAX)
+    hipLaunchKernelGGL(kd_rows_kernel, grid, block, 0, s, Q, C, scores, tscores, pos_idx, temperature, ce_w, kd_w, ls / (float)Q, ls, losses, det);
+  else if (kd_type == SIMX_KD_LOGIT)
+    hipLaunchKernelGGL(kd_rows_type_kernel<SIMX_KD_LOGIT>, grid, block, 0, s, Q, C, scores, tscores, pos_idx, temperature, ce_w, kd_w,
+                       dkd_alpha, dkd_beta, ls / (float)Q, ls, losses, det);
+  else if (kd_type == SIMX_KD_DKD)
+    hipLaunchKernelGGL(kd_rows_type_kernel<SIMX_KD_DKD>, grid, block, 0, s, Q, C, scores, tscores, pos_idx, temperature, ce_w, kd_w,
+                       dkd_alpha, dkd_beta, ls / (float)Q, ls, losses, det);
+  else
+    hipLaunchKernelGGL(kd_rows_type_kernel<SIMX_KD_BI_LOGIT>, grid, block, 0, s, Q, C, scores, tscores, pos_idx, temperature, ce_w, kd_w,
+                       dkd_alpha, dkd_beta, ls / (float)Q, ls, losses, det);
   SIMX_CHECK_LAUNCH("kd_rows");
   if (det) { rc = simx_det_reduce(s, det, 4L, Q, 4, losses, nullptr, nullptr, nullptr); if (rc) return rc; }
   if (q_n > 0 && dq_local) {
@@ -318,5 +512,21 @@ extern "C" int simx_scores_kd_fwd_bwd(simx_stream_t stream, int Q, int C, int H,
     rc = simx_gemm_f32_strided_ws(stream, c_n, H, Q, scores + c_lo, 1, C, q, H, 1, dctx_local, H, 0, ws, ws_bytes);
     if (rc) return rc;
   }
+  if (bi) {                                                                                   // + kd_w * embedding MSE, after the products
+    if (int rcd = loss_det_begin(s, Q + C, &det)) return rcd;
+    hipLaunchKernelGGL(bi_logit_rows_kernel, dim3(cdiv(Q + C, 4)), block, 0, s, Q, C, H, q, ctx, tq, tctx, kd_w, ls, q_lo, q_n, c_lo, c_n,
+                       dq_local, dctx_local, losses, det);
+    SIMX_CHECK_LAUNCH("bi_logit_rows");
+    if (det) return simx_det_reduce(s, det, 4L, Q + C, 4, losses, nullptr, nullptr, nullptr);
+  }
   return SIMX_OK;
+}
+
+extern "C" int simx_scores_kd_fwd_bwd(simx_stream_t stream, int Q, int C, int H, int HT, const float* q, const float* ctx,
+                                      const float* tq, const float* tctx, const int32_t* pos_idx, float temperature,
+                                      float ce_w, float kd_w, float loss_scale, int q_lo, int q_n, int c_lo, int c_n,
+                                      float* scores, float* tscores, float* losses, float* dq_local, float* dctx_local,
+                                      void* ws, size_t ws_bytes) {
+  return simx_scores_kd_type_fwd_bwd(stream, SIMX_KD_SOFTMAX, Q, C, H, HT, q, ctx, tq, tctx, pos_idx, temperature, ce_w, kd_w, 0.f, 0.f,
+                                     loss_scale, q_lo, q_n, c_lo, c_n, scores, tscores, losses, dq_local, dctx_local, ws, ws_bytes);
 }

@@ -324,19 +324,33 @@ class BiEncoderNllLoss(object):
         return dot_product_scores
 
 
+def _kd_args(args, table, cls_name):
+    """(KD_type, DKD_alpha, DKD_beta) of ``args`` checked against the objectives ``cls_name`` has: the cases in which the
+    reference prints a message and exits (PROD/ProD_KD/model/models.py:735-737, 744-746, 1021-1023, 1026-1028)."""
+    kd_type = getattr(args, "KD_type", "KD_softmax")
+    if kd_type not in table:
+        raise ValueError("--KD_type %r: %s knows %s" % (kd_type, cls_name, ", ".join(sorted(table))))
+    alpha, beta = getattr(args, "DKD_alpha", None), getattr(args, "DKD_beta", None)
+    if kd_type == "DKD" and (alpha is None or beta is None):
+        raise ValueError("--KD_type DKD needs --DKD_alpha and --DKD_beta")
+    return kd_type, alpha, beta
+
+
 class CrossBERTKDLoss(object):
-    """PROD/ProD_KD/model/models.py:668-760 (L3): CE_WEIGHT * NLL(log_softmax(sim), 0) + KD_WEIGHT * kd_loss(sim, teacher)
-    on the per-query block similarity; KD_type "KD_softmax" (the shipped configuration)."""
+    """PROD/ProD_KD/model/models.py:668-827 (L3): CE_WEIGHT * NLL(log_softmax(sim), 0) + KD_WEIGHT * soft(sim, teacher) on the
+    per-query block similarity; soft by args.KD_type: "KD_softmax" (the shipped configuration), "KD_logit", "DKD"
+    (args.DKD_alpha, args.DKD_beta) or "prob_loss"."""
 
     def calc(self, args, q_vectors, ctx_vectors, relevance_logits, hard_negative_idx_per_question: list = None,
              loss_scale: float = None, LwF=False, ori_q_vector=None, ori_ctx_vectors=None):
-        if getattr(args, "KD_type", "KD_softmax") != "KD_softmax":
-            raise NotImplementedError("KD_type %r: only KD_softmax runs on the HIP path" % args.KD_type)
+        kd_type, alpha, beta = _kd_args(args, ops.CROSS_KD_KINDS, "CrossBERTKDLoss")
+        if LwF and kd_type not in ("KD_softmax", "KD_logit"):    # kd_loss (:772-781) defines no value for the other types
+            raise ValueError("LwF (--open_LwF) runs kd_loss with --KD_type, which is KD_softmax or KD_logit there, not %r" % kd_type)
         loss, correct, _, _ = ops.cross_kd_loss(q_vectors, ctx_vectors, relevance_logits, args.TEMPERATURE,
-                                                args.CE_WEIGHT, args.KD_WEIGHT)
+                                                args.CE_WEIGHT, args.KD_WEIGHT, kd_type, alpha, beta)
         if LwF:                                      # + LwF_WEIGHT * kd_loss(scores, scores of the frozen student) (:687-690, 748-750)
             ori_scores = ops.block_scores(ori_q_vector, ori_ctx_vectors)
-            lwf, _, _, _ = ops.cross_kd_loss(q_vectors, ctx_vectors, ori_scores, args.TEMPERATURE, 0.0, args.LwF_WEIGHT)
+            lwf, _, _, _ = ops.cross_kd_loss(q_vectors, ctx_vectors, ori_scores, args.TEMPERATURE, 0.0, args.LwF_WEIGHT, kd_type)
             loss = loss + lwf
         if loss_scale:
             loss = loss * loss_scale
@@ -344,19 +358,19 @@ class CrossBERTKDLoss(object):
 
 
 class BiEncoderKDLoss(object):
-    """PROD/ProD_KD/model/models.py:970-1038 (L4): the same loss on all-pairs scores of the student embeddings against
-    all-pairs scores of the teacher (dual-encoder) embeddings."""
+    """PROD/ProD_KD/model/models.py:970-1113 (L4): the same loss on all-pairs scores of the student embeddings against
+    all-pairs scores of the teacher (dual-encoder) embeddings; soft by args.KD_type: "KD_softmax", "KD_logit", "DKD"
+    (target = the positive's column) or "Bi_logit" (MSE between the embeddings themselves, equal widths)."""
 
     def calc(self, args, q_vectors, ctx_vectors, teacher_q_vector, teacher_ctxs_vector, positive_idx_per_question: list,
              hard_negative_idx_per_question: list = None, loss_scale: float = None, local_q=None, local_ctx=None):
         if teacher_q_vector is None or teacher_ctxs_vector is None:
             loss, correct = ops.inbatch_nll_loss(q_vectors, ctx_vectors, positive_idx_per_question, loss_scale, local_q, local_ctx)
             return loss, correct.to(torch.long)
-        if getattr(args, "KD_type", "KD_softmax") != "KD_softmax":
-            raise NotImplementedError("KD_type %r: only KD_softmax runs on the HIP path" % args.KD_type)
+        kd_type, alpha, beta = _kd_args(args, ops.BI_KD_TYPES, "BiEncoderKDLoss")
         loss, _, _, correct = ops.bi_kd_loss(q_vectors, ctx_vectors, teacher_q_vector, teacher_ctxs_vector,
                                              positive_idx_per_question, args.TEMPERATURE, args.CE_WEIGHT, args.KD_WEIGHT,
-                                             loss_scale, local_q, local_ctx)
+                                             loss_scale, local_q, local_ctx, kd_type, alpha, beta)
         return loss, correct.to(torch.long)
 
     @staticmethod

@@ -63,9 +63,25 @@ class _LogitLossFn(torch.autograd.Function):
         return dz * g, None, None
 
 
-def _lp(kind, scale=1.0, temperature=1.0, adv_lambda=0.0, ce_w=0.0, kd_w=0.0, grad_accum=1.0):
+def _lp(kind, scale=1.0, temperature=1.0, adv_lambda=0.0, ce_w=0.0, kd_w=0.0, grad_accum=1.0, dkd_alpha=0.0, dkd_beta=0.0):
     return L.LossParams(kind, float(scale), float(temperature), float(adv_lambda), float(ce_w), float(kd_w),
-                        float(grad_accum))
+                        float(grad_accum), float(dkd_alpha), float(dkd_beta))
+
+
+# KD_type (PROD --KD_type) -> loss kind of the block form / kd_type of the all-pairs form
+CROSS_KD_KINDS = {"KD_softmax": L.LOSS_CEKD, "KD_logit": L.LOSS_CE_LOGIT, "DKD": L.LOSS_CE_DKD, "prob_loss": L.LOSS_CE_PROB}
+BI_KD_TYPES = {"KD_softmax": L.KD_SOFTMAX, "KD_logit": L.KD_LOGIT, "DKD": L.KD_DKD, "Bi_logit": L.KD_BI_LOGIT}
+
+
+def _kd_kind(table, kd_type, dkd_alpha, dkd_beta):
+    """Validated (kind, alpha, beta) of a kd_type; raises before anything touches the device."""
+    if kd_type not in table:
+        raise ValueError("kd_type %r: this loss knows %s" % (kd_type, ", ".join(sorted(table))))
+    if kd_type != "DKD":
+        return table[kd_type], 0.0, 0.0
+    if dkd_alpha is None or dkd_beta is None:
+        raise ValueError("kd_type 'DKD' needs dkd_alpha and dkd_beta")
+    return table[kd_type], float(dkd_alpha), float(dkd_beta)
 
 
 def kl_distill_loss(q, ctx_vectors, teacher_logits, temperature_distill=1.0, scale_simmila=False, grad_accum=1):
@@ -85,10 +101,13 @@ def wiki_normal_adv_loss(q, ctx_vectors, reranker_logits, temperature_normal=1.0
     return loss, allv[1], allv[2], sim
 
 
-def cross_kd_loss(q, ctx_vectors, relevance_logits, temperature=4.0, ce_weight=0.1, kd_weight=0.9):
-    """PROD CrossBERTKDLoss.calc (KD_softmax).  -> (loss, correct_count, hard, soft)."""
+def cross_kd_loss(q, ctx_vectors, relevance_logits, temperature=4.0, ce_weight=0.1, kd_weight=0.9, kd_type="KD_softmax",
+                  dkd_alpha=None, dkd_beta=None):
+    """PROD CrossBERTKDLoss.calc: ce_weight * hard + kd_weight * soft, soft chosen by ``kd_type`` (KD_softmax, KD_logit,
+    DKD with ``dkd_alpha`` / ``dkd_beta``, prob_loss).  -> (loss, correct_count, hard, soft)."""
+    kind, alpha, beta = _kd_kind(CROSS_KD_KINDS, kd_type, dkd_alpha, dkd_beta)
     loss, allv, _ = _SimLossFn.apply(q, ctx_vectors, relevance_logits,
-                                     _lp(L.LOSS_CEKD, 1.0, temperature, 0.0, ce_weight, kd_weight))
+                                     _lp(kind, 1.0, temperature, 0.0, ce_weight, kd_weight, dkd_alpha=alpha, dkd_beta=beta))
     return loss, allv[3], allv[1], allv[2]
 
 
@@ -154,37 +173,44 @@ def inbatch_nll_loss(q_vectors, ctx_vectors, positive_idx_per_question, loss_sca
 
 class _KdFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, c, tq, tc, pos_idx, T, ce_w, kd_w, loss_scale, q_lo, q_n, c_lo, c_n):
+    def forward(ctx, q, c, tq, tc, pos_idx, T, ce_w, kd_w, loss_scale, q_lo, q_n, c_lo, c_n, kd, alpha, beta):
         q, c, tq, tc = _f32c(q), _f32c(c), _f32c(tq.detach()), _f32c(tc.detach())
         Q, H = q.shape
         Cn, HT = c.shape[0], tq.shape[1]
+        bi = kd == L.KD_BI_LOGIT
+        if bi and (tq.shape != q.shape or tc.shape != c.shape):
+            raise ValueError("Bi_logit compares embeddings: teacher shapes %s / %s differ from the student's %s / %s"
+                             % (tuple(tq.shape), tuple(tc.shape), tuple(q.shape), tuple(c.shape)))
         pos = torch.as_tensor(pos_idx, dtype=torch.int32, device=q.device).contiguous()
         scores = torch.empty(Q, Cn, dtype=torch.float32, device=q.device)
-        tscores = torch.empty(Q, Cn, dtype=torch.float32, device=q.device)
+        tscores = None if bi else torch.empty(Q, Cn, dtype=torch.float32, device=q.device)
         losses = torch.empty(4, dtype=torch.float32, device=q.device)
         dq, dc = torch.zeros_like(q), torch.zeros_like(c)
         ws, wsb = _scores_ws(Q, Cn, H, q_n, c_n, q.device)
-        L.call("simx_scores_kd_fwd_bwd", L.stream_ptr(), Q, Cn, H, HT, L.ptr(q), L.ptr(c), L.ptr(tq), L.ptr(tc), L.ptr(pos),
-               float(T), float(ce_w), float(kd_w), float(loss_scale or 1.0), q_lo, q_n, c_lo, c_n, L.ptr(scores),
-               L.ptr(tscores), L.ptr(losses), C.c_void_p(dq.data_ptr() + q_lo * H * 4), C.c_void_p(dc.data_ptr() + c_lo * H * 4),
-               L.ptr(ws) if wsb else None, wsb)
+        L.call("simx_scores_kd_type_fwd_bwd", L.stream_ptr(), kd, Q, Cn, H, HT, L.ptr(q), L.ptr(c), L.ptr(tq), L.ptr(tc), L.ptr(pos),
+               float(T), float(ce_w), float(kd_w), float(alpha), float(beta), float(loss_scale or 1.0), q_lo, q_n, c_lo, c_n,
+               L.ptr(scores), L.ptr(tscores), L.ptr(losses), C.c_void_p(dq.data_ptr() + q_lo * H * 4),
+               C.c_void_p(dc.data_ptr() + c_lo * H * 4), L.ptr(ws) if wsb else None, wsb)
         ctx.save_for_backward(dq, dc)
         return losses[0], losses.detach()
 
     @staticmethod
     def backward(ctx, g, g_all):
         dq, dc = ctx.saved_tensors
-        return (dq * g, dc * g) + (None,) * 11
+        return (dq * g, dc * g) + (None,) * 14
 
 
 def bi_kd_loss(q_vectors, ctx_vectors, teacher_q_vector, teacher_ctxs_vector, positive_idx_per_question, temperature=4.0,
-               ce_weight=0.1, kd_weight=0.9, loss_scale=None, local_q=None, local_ctx=None):
-    """BiEncoderKDLoss.calc with KD_type == "KD_softmax" (PROD/ProD_KD/model/models.py:970-1038): all-pairs scores of
-    the student and of the (constant) teacher embeddings; -> (loss, hard, soft, correct_count)."""
+               ce_weight=0.1, kd_weight=0.9, loss_scale=None, local_q=None, local_ctx=None, kd_type="KD_softmax",
+               dkd_alpha=None, dkd_beta=None):
+    """BiEncoderKDLoss.calc (PROD/ProD_KD/model/models.py:970-1038): all-pairs scores of the student and of the (constant)
+    teacher embeddings, soft term chosen by ``kd_type`` (KD_softmax, KD_logit, DKD with ``dkd_alpha`` / ``dkd_beta``), or
+    Bi_logit: an MSE between student and teacher embeddings of the same width.  -> (loss, hard, soft, correct_count)."""
+    kd, alpha, beta = _kd_kind(BI_KD_TYPES, kd_type, dkd_alpha, dkd_beta)
     q_lo, q_n = local_q if local_q is not None else (0, q_vectors.shape[0])
     c_lo, c_n = local_ctx if local_ctx is not None else (0, ctx_vectors.shape[0])
     loss, allv = _KdFn.apply(q_vectors, ctx_vectors, teacher_q_vector, teacher_ctxs_vector, positive_idx_per_question,
-                             temperature, ce_weight, kd_weight, loss_scale, q_lo, q_n, c_lo, c_n)
+                             temperature, ce_weight, kd_weight, loss_scale, q_lo, q_n, c_lo, c_n, kd, alpha, beta)
     return loss, allv[1], allv[2], allv[3]
 
 
