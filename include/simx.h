@@ -627,6 +627,33 @@ int simx_adamw_step_sc(simx_stream_t stream, float* p, float* g, float* m, float
                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                        const float* sqnorm, float max_norm, float grad_scale, int zero_grad, const float* scaler);
 
+/* LAMB (PROD/ProD_KD/utils/lamb.py:60-123, get_optimizer's --optimizer lamb) over a flat f32 buffer that holds several
+ * parameter tensors ("segments") back to back, at any element offset.  Per segment, with g the gradient times the clip
+ * coefficient and grad_scale exactly as in simx_adamw_step:
+ *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  u = m / (sqrt(v) + eps) + wd_seg p       (no bias correction)
+ *   weight_norm = min(|p|_2, 10);  adam_norm = |u|_2;  trust_ratio = 1 if either is 0, else weight_norm / adam_norm
+ *   p -= lr * trust_ratio * u
+ * The work is cut into chunks of at most SIMX_LAMB_CHUNK elements that never cross a segment; the plan is three tables the
+ * caller builds once and keeps on the device:
+ *   chunks[nchunk]        {segment, length, element offset}, ordered by offset; the chunks of one segment are consecutive
+ *   seg_chunks[nseg][2]   {first chunk, number of chunks} of every segment
+ *   seg_wd[nseg]          the weight decay of every segment
+ * Elements that belong to no segment (a tower's never-computed pooler slots) are not touched at all, gradient included.
+ * simx_lamb_plan_check validates HOST copies of the tables against the segments' element ranges seg_range[nseg][2] =
+ * {offset, length} (ascending, disjoint, inside n): every chunk lies in its segment and the chunks of a segment tile it.
+ * simx_lamb_step = three launches on `stream`: moments + per-chunk partial sums (partials: 2 * nchunk floats of scratch),
+ * per-segment norms -> stats[nseg][3] = {weight_norm, adam_norm, trust_ratio} (the state the reference keeps per parameter),
+ * update + zero_grad.  beta1, beta2 are doubles: 1 - beta is taken in double, as the reference's Python does, and rounded once.
+ * No float atomics, fixed summation order (bit-reproducible), no host read.  `scaler` (may be NULL) is
+ * the loss-scaler state above: when its skip flag [3] is set, p, m, v and stats keep their bits and only g is zeroed. */
+#define SIMX_LAMB_CHUNK 4096
+typedef struct { int32_t seg; int32_t len; int64_t off; } simx_lamb_chunk_t;
+int simx_lamb_chunk(void);
+int simx_lamb_plan_check(const simx_lamb_chunk_t* chunks, int nchunk, const int* seg_chunks, const int64_t* seg_range, int nseg, size_t n);
+int simx_lamb_step(simx_stream_t stream, float* p, float* g, float* m, float* v, size_t n, const simx_lamb_chunk_t* chunks, int nchunk,
+                   const int* seg_chunks, const float* seg_wd, int nseg, float* stats, float* partials, float lr, double beta1,
+                   double beta2, float eps, const float* sqnorm, float max_norm, float grad_scale, int zero_grad, const float* scaler);
+
 /* ------------------------------------------------------------------ measurement
  * Optional per-launch timing with HIP events recorded on the launch stream (bench.py's live roofline
  * figure).  simx_prof_begin(max_launches) starts recording; simx_prof_end() stops, waits for the

@@ -129,6 +129,9 @@ SIGNATURES = {
     "simx_scaler_update": (_i, [_p, _p, _p]),
     "simx_deterministic": (_i, []),
     "simx_adamw_step_sc": (_i, [_p, _p, _p, _p, _p, _z, _f, _f, _f, _f, _f, _i, _p, _f, _f, _i, _p]),
+    "simx_lamb_chunk": (_i, []),
+    "simx_lamb_plan_check": (_i, [_p, _i, _p, _p, _i, _z]),
+    "simx_lamb_step": (_i, [_p, _p, _p, _p, _p, _z, _p, _i, _p, _p, _i, _p, _p, _f, _d, _d, _f, _p, _f, _f, _i, _p]),
     "simx_gemm_nt_planes_ok": (_i, [_i, _i, _i]),
     "simx_gemm_nt_planes": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _l, _p, _i, _l, _p, _i, _p, _p, _i, _p, _i, _l, _dp]),
     "simx_gemm_nt_planes_cs": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _l, _p, _i, _l, _p, _i, _p, _p, _i, _p, _i, _l, _dp, _p, _i]),

@@ -20,7 +20,7 @@ from torch.utils.data import DataLoader, RandomSampler
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from simxns_amd import ops                                                           # noqa: E402
 from simxns_amd.model.models import BiBertEncoder, HFBertEncoder, Reranker            # noqa: E402
-from simxns_amd.optim import FusedAdamW, LinearWarmupSchedule                         # noqa: E402
+from simxns_amd.optim import FusedAdamW, FusedLamb, LinearWarmupSchedule              # noqa: E402
 from simxns_amd.utils.MARCO_until_new import Rocketqa_v2Dataset, HashTokenizer        # noqa: E402
 from simxns_amd.utils.dpr_utils import (CheckpointState, get_model_obj,               # noqa: E402
                                         load_states_from_checkpoint, save_checkpoint_state)
@@ -30,10 +30,13 @@ logger = logging.getLogger(__name__)
 
 
 def get_optimizer(args, model, weight_decay=0.0, lr=0.0, eps=0.0):
-    """co_training_marco_train.py:57-69 ('bias' / 'LayerNorm.weight' never decay; only adamW is known)."""
+    """co_training_marco_train.py:57-69 ('bias' / 'LayerNorm.weight' never decay); `lamb` is the Lamb of utils/lamb.py that
+    the sibling recipes' get_optimizer builds (PROD/ProD_KD/utils/dpr_utils.py:80-92)."""
     if args.optimizer == "adamW":
         return FusedAdamW(model, lr=lr, eps=eps, weight_decay=weight_decay)
-    raise Exception("optimizer {0} not recognized! Can only be adamW".format(args.optimizer))
+    if args.optimizer == "lamb":
+        return FusedLamb(model, lr=lr, eps=eps, weight_decay=weight_decay)
+    raise Exception("optimizer {0} not recognized! Can only be lamb or adamW".format(args.optimizer))
 
 
 def get_bert_reader_components(args, **kwargs):

@@ -189,3 +189,184 @@ extern "C" int simx_adamw_step_sc(simx_stream_t stream, float* p, float* g, floa
   SIMX_CHECK_LAUNCH("adamw");
   return SIMX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- LAMB
+// PROD/ProD_KD/utils/lamb.py:60-123 (the Lamb of get_optimizer's --optimizer lamb) over a flat f32 buffer.  The update of every
+// parameter tensor ("segment") is scaled by its trust ratio min(|p|, 10) / |u|, u = m / (sqrt(v) + eps) + wd * p, so the buffer is
+// cut into chunks of at most SIMX_LAMB_CHUNK elements that never cross a segment boundary:
+//   pass A   (one workgroup per chunk)  m, v updated and stored; sum p^2 and sum u^2 of the chunk -> partials[2c], [2c + 1]
+//   finalize (one wave per segment)     partials added in a fixed order -> stats[seg] = {weight_norm, adam_norm, trust_ratio}
+//   pass B   (one workgroup per chunk)  u recomputed from the unchanged p and the stored m, v; p -= lr * ratio * u; g = 0
+// 44 B/param (A: 16 read + 8 written, B: 12 + 8).  No float atomics and a fixed element -> thread -> lane order in every sum, so
+// the replicas of a data-parallel job get the same bits; no host read; on a step the fp16 loss scaler skips only g is written.
+// lamb_u is the ONE statement of u: both passes must round it alike, so the multiply-add is spelled out, not left to contraction.
+__device__ __forceinline__ float lamb_u(float p, float m, float v, float eps, float wd) {
+  return __fmaf_rn(wd, p, m / (sqrtf(v) + eps));
+}
+__device__ __forceinline__ bool lamb_chunk_ok(const simx_lamb_chunk_t& c, size_t n, int nseg) {
+  return c.seg >= 0 && c.seg < nseg && c.len > 0 && c.len <= SIMX_LAMB_CHUNK && c.off >= 0 && (size_t)c.off + (size_t)c.len <= n;
+}
+// scalar head up to 16-byte alignment (the buffers are 16-B aligned, so that is the element offset mod 4), float4 body, scalar tail
+__device__ __forceinline__ void lamb_split(const simx_lamb_chunk_t& c, int& head, int& body4) {
+  head = (int)((4 - (c.off & 3)) & 3);
+  if (head > c.len) head = c.len;
+  body4 = (c.len - head) / 4;
+}
+
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, size_t n, const simx_lamb_chunk_t* __restrict__ chunks,
+                                                           const float* __restrict__ seg_wd, int nseg, float* __restrict__ partials,
+                                                           float beta1, float beta2, float omb1, float omb2, float eps,
+                                                           const float* __restrict__ sqnorm, float max_norm, float grad_scale, const float* __restrict__ scaler) {
+  __shared__ float part[8];
+  if (scaler && scaler[3] != 0.f) return;
+  const simx_lamb_chunk_t c = chunks[blockIdx.x];
+  if (!lamb_chunk_ok(c, n, nseg)) return;
+  float coef = grad_scale;
+  if (sqnorm && max_norm > 0.f) {
+    const float total = sqrtf(*sqnorm) * grad_scale;
+    coef *= fminf(1.0f, max_norm / (total + 1e-6f));
+  }
+  const float wd = seg_wd[c.seg];
+  int head, body4;
+  lamb_split(c, head, body4);
+  p += c.off; g += c.off; m += c.off; v += c.off;
+  float sp = 0.f, su = 0.f;
+  auto one = [&](int i) {
+    const float gg = g[i] * coef, pv = p[i];
+    const float mn = beta1 * m[i] + omb1 * gg, vn = beta2 * v[i] + omb2 * gg * gg;
+    m[i] = mn; v[i] = vn;
+    const float u = lamb_u(pv, mn, vn, eps, wd);
+    sp += pv * pv; su += u * u;
+  };
+  for (int i = threadIdx.x; i < body4; i += 256) {
+    const float4 pv = reinterpret_cast<const float4*>(p + head)[i], gv = reinterpret_cast<const float4*>(g + head)[i];
+    float4 mv = reinterpret_cast<float4*>(m + head)[i], vv = reinterpret_cast<float4*>(v + head)[i];
+    const float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float gg = gp[e] * coef;
+      mp[e] = beta1 * mp[e] + omb1 * gg;
+      vp[e] = beta2 * vp[e] + omb2 * gg * gg;
+      const float u = lamb_u(pp[e], mp[e], vp[e], eps, wd);
+      sp += pp[e] * pp[e]; su += u * u;
+    }
+    reinterpret_cast<float4*>(m + head)[i] = mv;
+    reinterpret_cast<float4*>(v + head)[i] = vv;
+  }
+  if ((int)threadIdx.x < head) one(threadIdx.x);
+  const int t0 = head + body4 * 4;
+  if (t0 + (int)threadIdx.x < c.len) one(t0 + threadIdx.x);
+  sp = wave_sum(sp); su = wave_sum(su);
+  if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = sp; part[4 + (threadIdx.x >> 6)] = su; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[2 * (size_t)blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+    partials[2 * (size_t)blockIdx.x + 1] = (part[4] + part[5]) + (part[6] + part[7]);
+  }
+}
+
+__global__ __launch_bounds__(64) void lamb_ratio_kernel(const float* __restrict__ partials, const int* __restrict__ seg_chunks, int nchunk,
+                                                        float* __restrict__ stats, const float* __restrict__ scaler) {
+  if (scaler && scaler[3] != 0.f) return;
+  const int first = seg_chunks[2 * blockIdx.x], count = seg_chunks[2 * blockIdx.x + 1];
+  if (first < 0 || count < 1 || first > nchunk - count) return;
+  float sp = 0.f, su = 0.f;
+  for (int i = threadIdx.x; i < count; i += 64) {          // lane l adds chunks l, l + 64, ... in chunk order; then the fixed lane tree
+    sp += partials[2 * (size_t)(first + i)];
+    su += partials[2 * (size_t)(first + i) + 1];
+  }
+  sp = wave_sum(sp); su = wave_sum(su);
+  if (threadIdx.x == 0) {
+    const float wn = fminf(sqrtf(sp), 10.0f), an = sqrtf(su);
+    float* st = stats + 3 * (size_t)blockIdx.x;
+    st[0] = wn; st[1] = an; st[2] = (wn == 0.f || an == 0.f) ? 1.0f : wn / an;
+  }
+}
+
+__global__ __launch_bounds__(256) void lamb_update_kernel(float* __restrict__ p, float* __restrict__ g, const float* __restrict__ m,
+                                                          const float* __restrict__ v, size_t n, const simx_lamb_chunk_t* __restrict__ chunks,
+                                                          const float* __restrict__ seg_wd, int nseg, const float* __restrict__ stats,
+                                                          float lr, float eps, int zero_grad, const float* __restrict__ scaler) {
+  const simx_lamb_chunk_t c = chunks[blockIdx.x];
+  if (!lamb_chunk_ok(c, n, nseg)) return;
+  const bool skip = scaler && scaler[3] != 0.f;              // overflow: parameters, moments and stats keep their bits
+  if (skip && !zero_grad) return;
+  int head, body4;
+  lamb_split(c, head, body4);
+  p += c.off; g += c.off; m += c.off; v += c.off;
+  const float wd = seg_wd[c.seg];
+  const float ns = skip ? 0.f : -(lr * stats[3 * (size_t)c.seg + 2]);
+  auto one = [&](int i) {
+    if (!skip) p[i] = __fmaf_rn(ns, lamb_u(p[i], m[i], v[i], eps, wd), p[i]);
+    if (zero_grad) g[i] = 0.f;
+  };
+  for (int i = threadIdx.x; i < body4; i += 256) {
+    if (!skip) {
+      float4 pv = reinterpret_cast<float4*>(p + head)[i];
+      const float4 mv = reinterpret_cast<const float4*>(m + head)[i], vv = reinterpret_cast<const float4*>(v + head)[i];
+      float* pp = &pv.x; const float* mp = &mv.x; const float* vp = &vv.x;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pp[e] = __fmaf_rn(ns, lamb_u(pp[e], mp[e], vp[e], eps, wd), pp[e]);
+      reinterpret_cast<float4*>(p + head)[i] = pv;
+    }
+    if (zero_grad) reinterpret_cast<float4*>(g + head)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  if ((int)threadIdx.x < head) one(threadIdx.x);
+  const int t0 = head + body4 * 4;
+  if (t0 + (int)threadIdx.x < c.len) one(t0 + threadIdx.x);
+}
+
+extern "C" int simx_lamb_chunk(void) { return SIMX_LAMB_CHUNK; }
+
+extern "C" int simx_lamb_plan_check(const simx_lamb_chunk_t* chunks, int nchunk, const int* seg_chunks, const int64_t* seg_range,
+                                    int nseg, size_t n) {
+  SIMX_REQUIRE(chunks && seg_chunks && seg_range, SIMX_ERR_BAD_SHAPE, "lamb_plan_check: null table");
+  SIMX_REQUIRE(nseg >= 1 && nchunk >= nseg && n > 0, SIMX_ERR_BAD_SHAPE, "lamb_plan_check: nseg %d, nchunk %d, n %zu", nseg, nchunk, n);
+  int next = 0;
+  long long end_prev = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const int first = seg_chunks[2 * s], count = seg_chunks[2 * s + 1];
+    const long long lo = (long long)seg_range[2 * s], len = (long long)seg_range[2 * s + 1];
+    SIMX_REQUIRE(lo >= end_prev && len >= 1 && (size_t)(lo + len) <= n, SIMX_ERR_BAD_SHAPE,
+                 "lamb_plan_check: segment %d [%lld, +%lld) overlaps its predecessor or leaves the buffer of %zu", s, lo, len, n);
+    SIMX_REQUIRE(first == next && count >= 1 && count <= nchunk - first, SIMX_ERR_BAD_SHAPE,
+                 "lamb_plan_check: segment %d owns chunks [%d, +%d), expected them to start at %d", s, first, count, next);
+    long long at = lo;
+    for (int c = first; c < first + count; ++c) {
+      SIMX_REQUIRE(chunks[c].seg == s && chunks[c].off == at && chunks[c].len >= 1 && chunks[c].len <= SIMX_LAMB_CHUNK &&
+                   at + chunks[c].len <= lo + len, SIMX_ERR_BAD_SHAPE,
+                   "lamb_plan_check: chunk %d (segment %d, offset %lld, %d elements) crosses or leaves segment %d [%lld, +%lld)", c,
+                   chunks[c].seg, (long long)chunks[c].off, chunks[c].len, s, lo, len);
+      at += chunks[c].len;
+    }
+    SIMX_REQUIRE(at == lo + len, SIMX_ERR_BAD_SHAPE, "lamb_plan_check: the chunks of segment %d cover %lld of its %lld elements", s, at - lo, len);
+    next = first + count;
+    end_prev = lo + len;
+  }
+  SIMX_REQUIRE(next == nchunk, SIMX_ERR_BAD_SHAPE, "lamb_plan_check: %d chunks belong to no segment", nchunk - next);
+  return SIMX_OK;
+}
+
+extern "C" int simx_lamb_step(simx_stream_t stream, float* p, float* g, float* m, float* v, size_t n, const simx_lamb_chunk_t* chunks,
+                              int nchunk, const int* seg_chunks, const float* seg_wd, int nseg, float* stats, float* partials, float lr,
+                              double beta1, double beta2, float eps, const float* sqnorm, float max_norm, float grad_scale, int zero_grad,
+                              const float* scaler) {
+  SIMX_PROF(SIMX_K_ADAMW, stream, 44.0 * n);
+  SIMX_REQUIRE(p && g && m && v && chunks && seg_chunks && seg_wd && stats && partials, SIMX_ERR_BAD_SHAPE, "lamb_step: null pointer");
+  SIMX_REQUIRE(n > 0 && nseg >= 1 && nchunk >= nseg, SIMX_ERR_BAD_SHAPE, "lamb_step: n %zu, nseg %d, nchunk %d", n, nseg, nchunk);
+  // (1 - beta in double, rounded once: the reference hands Python's 1 - beta to the tensor op, and 1.0f - 0.999f is off by 5e-5 of itself)
+  SIMX_REQUIRE(simx_al16(p) && simx_al16(g) && simx_al16(m) && simx_al16(v) && simx_al16(chunks), SIMX_ERR_BAD_SHAPE,
+               "lamb_step: buffers not 16-B aligned");
+  hipLaunchKernelGGL(lamb_moments_kernel, dim3((unsigned)nchunk), dim3(256), 0, (hipStream_t)stream, (const float*)p, (const float*)g, m, v,
+                     n, chunks, seg_wd, nseg, partials, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, sqnorm, max_norm,
+                     grad_scale, scaler);
+  SIMX_CHECK_LAUNCH("lamb_moments");
+  hipLaunchKernelGGL(lamb_ratio_kernel, dim3((unsigned)nseg), dim3(64), 0, (hipStream_t)stream, (const float*)partials, seg_chunks, nchunk,
+                     stats, scaler);
+  SIMX_CHECK_LAUNCH("lamb_ratio");
+  hipLaunchKernelGGL(lamb_update_kernel, dim3((unsigned)nchunk), dim3(256), 0, (hipStream_t)stream, p, g, (const float*)m, (const float*)v,
+                     n, chunks, seg_wd, nseg, (const float*)stats, lr, eps, zero_grad, scaler);
+  SIMX_CHECK_LAUNCH("lamb_update");
+  return SIMX_OK;
+}

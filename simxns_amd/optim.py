@@ -270,6 +270,15 @@ class FusedAdamW(object):
         """Returns the device scalar holding the squared global grad norm (before clipping)."""
         lr = self.param_groups[0]["lr"]
         self.step_count += 1
+        bufs, sq, clip, grad_scale, sc = self._prepare(max_grad_norm, world_size)
+        self._apply(bufs, lr, sq if clip else None, float(max_grad_norm or 0.0), grad_scale, sc)
+        self._sq = sq
+        return sq
+
+    def _prepare(self, max_grad_norm, world_size):
+        """Everything of a step that is not the update rule: joins the towers' streams, completes the gradient reduction,
+        collects the flat buffers, takes the deterministic squared norm and lets the loss scaler judge it.
+        -> ([(p, g, state, engine or None)], squared norm, clip?, 1/W, scaler state or None)"""
         dev = self.towers[0][1].flat.device if self.towers else self.extra[0].device
         cur = torch.cuda.current_stream()
         for m, e in self.towers:                       # a tower's backward may have run on a side stream (BiBertEncoder)
@@ -301,10 +310,15 @@ class FusedAdamW(object):
         if self.scaler is not None:
             self.scaler.update(sq)                # device side: skip + halve on overflow, count, grow
             sc = self.scaler.state(dev)
+        return bufs, sq, clip, grad_scale, sc
+
+    def _apply(self, bufs, lr, sq, max_norm, grad_scale, sc):
+        """The update rule over the prepared buffers (`sq`: None when the step does not clip)."""
+        s = L.stream_ptr()
         for p_, g_, st_, e_ in bufs:
             L.call("simx_adamw_step_sc", s, L.ptr(p_), L.ptr(g_), L.ptr(st_["m"]), L.ptr(st_["v"]), p_.numel(), lr,
                    self.betas[0], self.betas[1], self.eps, 0.0, self.step_count,
-                   L.ptr(sq) if clip else None, float(max_grad_norm or 0.0), grad_scale, 1, L.ptr(sc))
+                   L.ptr(sq), max_norm, grad_scale, 1, L.ptr(sc))
             if e_ is not None:
                 e_.mark_weights_dirty()
         # (on an overflow-skipped fp16 step the decay factor below is 1: the device flag, no host read)
@@ -312,19 +326,26 @@ class FusedAdamW(object):
         if self.wd > 0.0:
             self._decay_towers(lr, keep)
         if self.extra:
-            st = self.state["extra"]
             nodecay = self._extra_no_decay()
-            o = 0
-            for p in self.extra:
-                n = p.numel()
-                p.copy_(st["p"][o:o + n].view_as(p))
+            f = 1.0 - lr * self.wd if keep is None else 1.0 - lr * self.wd * keep
+
+            def decay(p):
                 if self.wd > 0.0 and id(p) not in nodecay:      # same grouping rule as the towers (:59-65)
-                    p.mul_(1.0 - lr * self.wd if keep is None else 1.0 - lr * self.wd * keep)
-                if p.grad is not None:
-                    p.grad.zero_()
-                o += n
-        self._sq = sq
-        return sq
+                    p.mul_(f)
+            self._scatter_extra(decay)
+
+    def _scatter_extra(self, after=None):
+        """The packed extra parameters back into their tensors (`after(p)`: what the update still owes each), gradients zeroed."""
+        st = self.state["extra"]
+        o = 0
+        for p in self.extra:
+            n = p.numel()
+            p.copy_(st["p"][o:o + n].view_as(p))
+            if after is not None:
+                after(p)
+            if p.grad is not None:
+                p.grad.zero_()
+            o += n
 
     def _extra_no_decay(self):
         return {id(p) for n, p in self.model.named_parameters() if any(nd in n for nd in ("bias", "LayerNorm.weight"))}
@@ -365,6 +386,13 @@ class FusedAdamW(object):
                 o += n
         return out
 
+    _group_defaults = {"correct_bias": True}         # what the reference's optimizer class adds to every param group
+
+    def _state_extras(self):
+        """None: every parameter has a state entry of step / exp_avg / exp_avg_sq.  A subclass returns {id(param): further
+        entries} for the parameters that have stepped; the others get no entry."""
+        return None
+
     def state_dict(self):
         """torch.optim.Optimizer.state_dict() of the reference's transformers.AdamW: {'state': {i: {'step', 'exp_avg',
         'exp_avg_sq'}}, 'param_groups': [decay group, no-decay group]} -- a checkpoint written here resumes in the reference
@@ -375,11 +403,16 @@ class FusedAdamW(object):
         # (fp16: steps the scaler skipped did not age the moments -- apex skips optimizer.step() on them as well)
         applied = self.step_count if self.scaler is None else self.scaler.snapshot()["applied_steps"]
         if applied > 0:
+            more = self._state_extras()
             for i, (n, p, g) in enumerate(order):
+                if more is not None and id(p) not in more:
+                    continue
                 mv, vv = views[id(p)]
                 state[i] = {"step": applied, "exp_avg": mv.detach().cpu().clone(), "exp_avg_sq": vv.detach().cpu().clone()}
+                if more is not None:
+                    state[i].update(more[id(p)])
         lr = self.param_groups[0]["lr"]
-        base = dict(lr=lr, initial_lr=self.base_lr, betas=tuple(self.betas), eps=self.eps, correct_bias=True)
+        base = dict(lr=lr, initial_lr=self.base_lr, betas=tuple(self.betas), eps=self.eps, **self._group_defaults)
         n0 = sum(1 for _, _, g in order if g == 0)
         out = {"state": state,
                "param_groups": [dict(base, weight_decay=self.wd, params=list(range(n0))),
@@ -433,6 +466,164 @@ class FusedAdamW(object):
         g0 = sd["param_groups"][0]
         self.param_groups[0]["lr"] = float(g0.get("lr", self.lr))
         self.base_lr = float(g0.get("initial_lr", self.base_lr))
+
+
+_NO_DECAY = ("bias", "LayerNorm.weight")
+_LAMB_CHUNK_T = [("seg", "<i4"), ("len", "<i4"), ("off", "<i8")]      # simx_lamb_chunk_t (include/simx.h)
+_LAMB_SCALARS = ("weight_norm", "adam_norm", "trust_ratio")
+
+
+def lamb_chunk_plan(segs, chunk):
+    """The host side of simx_lamb_step's plan.  `segs`: [(offset, elements, weight decay)] ascending and disjoint.
+    -> (chunks [simx_lamb_chunk_t], seg_chunks int32 [nseg, 2], seg_range int64 [nseg, 2], seg_wd f32 [nseg]) as NumPy arrays:
+    every segment is cut into chunks of `chunk` elements and a ragged last one, so no chunk crosses a segment."""
+    import numpy as np
+    parts, seg_chunks, at = [], np.zeros((len(segs), 2), np.int32), 0
+    for i, (off, n, wd) in enumerate(segs):
+        k = (n + chunk - 1) // chunk
+        c = np.zeros(k, dtype=_LAMB_CHUNK_T)
+        start = np.arange(k, dtype=np.int64) * chunk
+        c["seg"], c["off"], c["len"] = i, off + start, np.minimum(chunk, n - start)
+        parts.append(c)
+        seg_chunks[i] = (at, k)
+        at += k
+    chunks = np.concatenate(parts) if parts else np.zeros(0, dtype=_LAMB_CHUNK_T)
+    seg_range = np.array([(off, n) for off, n, wd in segs], dtype=np.int64).reshape(len(segs), 2)
+    return chunks, seg_chunks, seg_range, np.array([wd for off, n, wd in segs], dtype=np.float32)
+
+
+class FusedLamb(FusedAdamW):
+    """Lamb(lr, eps, weight_decay) of PROD/ProD_KD/utils/lamb.py (get_optimizer's --optimizer lamb; no bias correction, trust
+    ratio min(|p|, 10) / |u| per parameter tensor) with the reference's no-decay grouping.  Everything that is not the update
+    rule -- towers, the extra-parameter buffer, gradient reduction, loss scaler, norm, schedule view -- is FusedAdamW's.
+
+    One parameter = one HF tensor = one segment of simx_lamb_step's plan: an entry of the engine's layout (the fused QKV slots
+    are three segments each), or one packed extra parameter.  The reference skips parameters whose gradient is None; here
+    that is a tower's pooler.dense.* (never computed) and any extra parameter without a gradient: they are in no segment and
+    keep their bits, also under weight decay."""
+
+    _group_defaults = {}
+
+    def __init__(self, model, lr=1e-3, eps=1e-6, weight_decay=0.0, betas=(0.9, 0.999), process_group=None):
+        super(FusedLamb, self).__init__(model, lr=lr, eps=eps, weight_decay=weight_decay, betas=betas, process_group=process_group)
+        self._plan = None
+        self._carry = {}        # id(param) -> (weight_norm, adam_norm, trust_ratio) waiting for a plan that holds the parameter
+
+    # ---- the segment table ---------------------------------------------------------------------------------------------
+    def segments(self, live_extra=None):
+        """[(name in the model, buffer, element offset, elements, weight decay, parameter)] by buffer, ascending in offset
+        within each (the plan's order; engine.layout is in HF registration order, where a layer's query bias comes between
+        its query and key weights while the flat buffer holds the three weights back to back): buffer i < number of towers is
+        tower i's flat buffer, the last one the packed extra parameters (`live_extra`: one flag per extra parameter, False
+        leaves it out; None takes all)."""
+        names = {}
+        for n, p in self.model.named_parameters():
+            names.setdefault(id(p), n)
+        wd = lambda n: 0.0 if any(k in n for k in _NO_DECAY) else self.wd
+        out = []
+        for b, (m, e) in enumerate(self.towers):
+            own = dict(m.named_parameters())
+            for key, off, shape in sorted(e.layout, key=lambda entry: entry[1]):
+                if key.startswith("pooler.") or key not in own:
+                    continue
+                p = own[key]
+                out.append((names[id(p)], b, int(off), p.numel(), wd(names[id(p)]), p))
+        o = 0
+        for j, p in enumerate(self.extra):
+            if live_extra is None or live_extra[j]:
+                out.append((names[id(p)], len(self.towers), o, p.numel(), wd(names[id(p)]), p))
+            o += p.numel()
+        return out
+
+    def _plan_for(self, dev):
+        """The plan tables of every buffer on `dev`, built once (again only when the device, or the set of extra parameters
+        that carry a gradient, changes) and checked on the host by simx_lamb_plan_check before they are uploaded.  All
+        segments' stats rows live in ONE device tensor (NaN = not computed yet), so trust_ratios() is one copy."""
+        import numpy as np
+        live = tuple(p.grad is not None for p in self.extra)
+        key = (str(dev), live)
+        if self._plan is not None and self._plan["key"] == key:
+            return self._plan
+        if self._plan is not None:                       # rows computed so far follow their parameters into the new plan
+            self._carry.update(self._stats_rows())
+        lib = L.load()
+        chunk = int(lib.simx_lamb_chunk())
+        segs = self.segments(live)
+        sizes = [e.flat.numel() for m, e in self.towers] + ([self._extra_state(dev)["p"].numel()] if self.extra else [])
+        stats = np.full((len(segs), 3), np.nan, dtype=np.float32)
+        for i, sg in enumerate(segs):
+            if id(sg[5]) in self._carry:
+                stats[i] = self._carry.pop(id(sg[5]))
+        dstats = torch.from_numpy(stats).to(dev)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+        bufs, row, most = [], 0, 1
+        for b, n in enumerate(sizes):
+            mine = [sg for sg in segs if sg[1] == b]
+            if not mine:
+                bufs.append(None)
+                continue
+            chunks, seg_chunks, seg_range, seg_wd = lamb_chunk_plan([(sg[2], sg[3], sg[4]) for sg in mine], chunk)
+            hp = lambda a: a.ctypes.data_as(L.C.c_void_p)
+            L.call("simx_lamb_plan_check", hp(chunks), len(chunks), hp(seg_chunks), hp(seg_range), len(mine), n)
+            bufs.append({"chunks": up(chunks), "nchunk": len(chunks), "seg_chunks": up(seg_chunks), "seg_wd": up(seg_wd),
+                         "nseg": len(mine), "stats": dstats[row:row + len(mine)]})
+            row += len(mine)
+            most = max(most, len(chunks))
+        self._plan = {"key": key, "segs": segs, "bufs": bufs, "stats": dstats,
+                      "partials": torch.empty(2 * most, dtype=torch.float32, device=dev)}
+        return self._plan
+
+    def _stats_rows(self):
+        """{id(param): (weight_norm, adam_norm, trust_ratio)} of the current plan: one device-to-host copy."""
+        if self._plan is None:
+            return {}
+        rows = self._plan["stats"].cpu().numpy()
+        return {id(sg[5]): tuple(float(x) for x in rows[i]) for i, sg in enumerate(self._plan["segs"])}
+
+    def trust_ratios(self):
+        """{parameter name: (weight_norm, adam_norm, trust_ratio)} of the last applied step, for every parameter that steps
+        (what the reference's log_lamb_rs puts into its histograms).  One device-to-host copy."""
+        rows = self._stats_rows()
+        return {sg[0]: rows[id(sg[5])] for sg in (self._plan["segs"] if self._plan is not None else [])}
+
+    # ---- the update rule -----------------------------------------------------------------------------------------------
+    def _apply(self, bufs, lr, sq, max_norm, grad_scale, sc):
+        plan = self._plan_for(bufs[0][0].device)
+        s = L.stream_ptr()
+        for (p_, g_, st_, e_), b in zip(bufs, plan["bufs"]):
+            if b is None:
+                continue
+            L.call("simx_lamb_step", s, L.ptr(p_), L.ptr(g_), L.ptr(st_["m"]), L.ptr(st_["v"]), p_.numel(), L.ptr(b["chunks"]),
+                   b["nchunk"], L.ptr(b["seg_chunks"]), L.ptr(b["seg_wd"]), b["nseg"], L.ptr(b["stats"]), L.ptr(plan["partials"]),
+                   lr, self.betas[0], self.betas[1], self.eps, L.ptr(sq), max_norm, grad_scale, 1, L.ptr(sc))
+            if e_ is not None:
+                e_.mark_weights_dirty()
+        if self.extra:
+            self._scatter_extra()                        # (the decay is inside u)
+
+    # ---- state interchange: torch.optim.Optimizer.state_dict() of the reference's Lamb ----------------------------------
+    def _state_extras(self):
+        """Parameters in a segment (or still waiting for one after a load) have stepped; the three scalars appear once they
+        have been computed or loaded (an AdamW-shaped state carries none: the next step computes them)."""
+        rows = dict(self._carry)
+        rows.update(self._stats_rows())
+        out = {}
+        for pid, row in rows.items():
+            out[pid] = {} if any(x != x for x in row) else {k: torch.tensor(x, dtype=torch.float32) for k, x in zip(_LAMB_SCALARS, row)}
+        return out
+
+    def load_state_dict(self, sd):
+        """Reads the reference's Lamb layout and, moments only, transformers.AdamW's (and FusedAdamW's formats)."""
+        super(FusedLamb, self).load_state_dict(sd)
+        if "state" not in sd:
+            return
+        nan = float("nan")
+        self._plan, self._carry = None, {}
+        stepping = {id(sg[5]) for sg in self.segments()}       # (an AdamW state has entries for the pooler slots as well)
+        for i, (n, p, g) in enumerate(self._ref_param_order()):
+            st = sd["state"].get(i, sd["state"].get(str(i)))
+            if st is not None and id(p) in stepping:
+                self._carry[id(p)] = tuple(float(st[k]) if k in st else nan for k in _LAMB_SCALARS)
 
 
 class LinearWarmupSchedule(object):
