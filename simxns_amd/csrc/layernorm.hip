@@ -5,6 +5,24 @@
 // wave-level butterflies only (no LDS, no barriers) in the forward kernels.  Backward kernels keep
 // per-lane column partial sums (dgamma, dbeta, dbias / dtype0) across the rows a workgroup walks and
 // flush them once with f32 atomics.
+//
+// Every step of the row algorithm is written once; the five row kernels are the walks over rows around them:
+//
+//   piece                                         ln_fwd  embed_ln_fwd  ln_bwd  embed_ln_bwd  embed_ln_bwd_seq
+//   ln_cols      the lane's live column vectors     x          x          x          x              x    (inside every piece below)
+//   LnRowIn      prefetched input row: issue/take   x                     x (z and dy)
+//   embed_row    word + position + type rows                   x                     x              x
+//   embed_dy     dy row x dropout multiplier                                         x              x
+//   ln_centre    sum -> mean -> subtract          (fused)      x          x          x              x
+//   ln_rstd      centred squares -> rstd          (fused)      x          through ln_row_bwd
+//   ln_store_row affine, dropout, 3-way store       x          x
+//   ln_row_bwd   xhat, column partials, dz                                x          x              x
+//   flush3       the three column-gradient sums                           x          x              x    (flush_cols each)
+//
+// Host: one launcher per kernel (ln_fwd_launch, ln_bwd_launch, embed_ln_fwd_launch; the two embedding backwards have one entry
+// point each), ln_det_ws for the deterministic mode's workspace, ln_planes_ok for the f32 engine's plane buffers.  The row
+// utilities below the LayerNorm kernels (cls gather / scatter, rows_copy, drop_residual_rows, stream_rows, seq_mean) share
+// nothing with them but Raw4.  (fused): ln_fwd_kernel keeps the two statistics steps in one register pass -- see there.
 #include <type_traits>
 #include "common.h"
 #include "prof.h"
@@ -66,21 +84,141 @@ __device__ __forceinline__ void st4_planes(bf16_t* p, long plane_stride, const f
   *reinterpret_cast<uint2*>(p + plane_stride) = make_uint2(l0, l1);
 }
 
+// ------------------------------------------------------------------------------------------ the row algorithm, step by step
+// f(v, c) for the lane's live vectors: vector v holds columns c .. c + 3, c = (v * 64 + lane) * 4 < H
+template <int VPL, typename F>
+__device__ __forceinline__ void ln_cols(int H, int lane, F&& f) {
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    const int c = (v * 64 + lane) * 4;
+    if (c < H) f(v, c);
+  }
+}
+
+// One input row, prefetched: issue(row) starts the loads and leaves them packed, take() unpacks them when the row's turn comes.
+// RES ("f32-grade residual stream" of the 16-bit engines, simx.h stream_lo): the row is  z = d + r_hi + r_lo  -- the dense
+// output (bias and dropout applied by the GEMM epilogue, no residual) plus the residual stream kept as a 16-bit value and ONE
+// correction byte (lo8, common.h: x = hi + (b - 128) ulp(hi) / 256, 4 elements per dword; rl may be NULL) -- summed in f32.
+template <typename T, int VPL, bool RES>
+struct LnRowIn {
+  int H, lane;
+  const T* __restrict__ z;
+  const T* __restrict__ rh;
+  const uint8_t* __restrict__ rl;
+  Raw4<T> nx[VPL], nh[RES ? VPL : 1];
+  uint32_t nl[RES ? VPL : 1];
+  __device__ __forceinline__ LnRowIn(int H_, int lane_, const T* z_, const T* rh_, const uint8_t* rl_) : H(H_), lane(lane_), z(z_), rh(rh_), rl(rl_) {}
+  __device__ __forceinline__ void issue(int row) {
+    ln_cols<VPL>(H, lane, [&](int v, int c) {
+      nx[v].load(z + (long)row * H + c);
+      if constexpr (RES) { nh[v].load(rh + (long)row * H + c); if (rl) nl[v] = *reinterpret_cast<const uint32_t*>(rl + (long)row * H + c); }
+    });
+  }
+  __device__ __forceinline__ void take(float (&x)[VPL][4], float& sum) {
+    sum = 0.f;
+    ln_cols<VPL>(H, lane, [&](int v, int) {
+      nx[v].unpack(x[v]);
+      if constexpr (RES) {
+        float a[4];
+        nh[v].unpack(a);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[v][e] += a[e];
+        if (rl) {
+          lo8_decode4<T>(nh[v].w0(), nh[v].w1(), nl[v], a);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) x[v][e] += a[e];
+        }
+      }
+      sum += x[v][0] + x[v][1] + x[v][2] + x[v][3];
+    });
+  }
+};
+
+// the embedding row: word + position + type-0 rows, and its sum
+template <int VPL>
+__device__ __forceinline__ void embed_row(int H, int lane, const float* __restrict__ wr, const float* __restrict__ pr,
+                                          const float* __restrict__ typew, float (&x)[VPL][4], float& sum) {
+  sum = 0.f;
+  ln_cols<VPL>(H, lane, [&](int v, int c) {
+    float a[4], b[4], t[4];
+    ld4(wr + c, a);
+    ld4(pr + c, b);
+    ld4(typew + c, t);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x[v][e] = a[e] + b[e] + t[e]; sum += x[v][e]; }
+  });
+}
+
+// the embedding backward's dy row: the gradient of the dropped output x the row's dropout multipliers
+template <typename T, int VPL>
+__device__ __forceinline__ void embed_dy(int H, int lane, const T* __restrict__ dr, const DropCtx& drop, int row, float (&dy)[VPL][4]) {
+  ln_cols<VPL>(H, lane, [&](int v, int c) {
+    ld4(dr + c, dy[v]);
+    if (drop.thr) { float m4[4]; drop_mult4(drop, (uint32_t)row, (uint32_t)c, m4); dy[v][0] *= m4[0]; dy[v][1] *= m4[1]; dy[v][2] *= m4[2]; dy[v][3] *= m4[3]; }
+  });
+}
+
+// sum -> mean -> centred row
+template <int VPL>
+__device__ __forceinline__ void ln_centre(int H, int lane, float sum, float (&x)[VPL][4]) {
+  const float mu = wave_sum(sum) / (float)H;
+  ln_cols<VPL>(H, lane, [&](int v, int) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[v][e] -= mu;
+  });
+}
+
+// centred row -> 1 / sqrt(var + eps).  Every square is rounded before it is added (contract off: no fused multiply-add), so the
+// variance -- and through rstd every output of the five kernels -- does not depend on how the compiler shapes this loop.
+template <int VPL>
+__device__ __forceinline__ float ln_rstd(int H, int lane, float (&x)[VPL][4], float eps) {
+  float sq = 0.f;
+  ln_cols<VPL>(H, lane, [&](int v, int) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sq += x[v][e] * x[v][e];
+  });
+  return 1.0f / sqrtf(wave_sum(sq) / (float)H + eps);
+}
+
+// y = xc * rstd * gamma + beta (x dropout multiplier when drop is given and on), stored one of three ways: as T; as T plus the
+// correction byte of what the 16-bit rounding of y drops (ylo: the stream then carries ~19 significand bits from layer to layer
+// -- apex O1 keeps it in fp32: residual additions promote to fp32 and LayerNorm is an fp32 function there -- at 3 B per element);
+// as f32 plus the fp16 plane pair the next GEMM stages (yp: f32 engine, "operand planes")
+template <typename T, int VPL>
+__device__ __forceinline__ void ln_store_row(int H, int lane, int row, float (&x)[VPL][4], float rstd, const float* gamma,
+                                             const float* beta, const DropCtx* drop, T* __restrict__ y, uint8_t* __restrict__ ylo,
+                                             bf16_t* __restrict__ yp, long yps) {
+  T* yr = y + (long)row * H;
+  ln_cols<VPL>(H, lane, [&](int v, int c) {
+    float g[4], b[4], o[4];
+    ld4(gamma + c, g);
+    ld4(beta + c, b);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = x[v][e] * rstd * g[e] + b[e];
+    if (drop && drop->thr) { float m4[4]; drop_mult4(*drop, (uint32_t)row, (uint32_t)c, m4); o[0] *= m4[0]; o[1] *= m4[1]; o[2] *= m4[2]; o[3] *= m4[3]; }
+    if (ylo) {
+      float rr[4];
+      uint32_t w0, w1;
+      st4_residue(yr + c, o, rr, w0, w1);
+      *reinterpret_cast<uint32_t*>(ylo + (long)row * H + c) = lo8_encode4<T>(w0, w1, rr);
+    } else {
+      st4(yr + c, o);
+      if constexpr (std::is_same<T, float>::value) { if (yp) st4_planes<f16_t>(yp + (long)row * H + c, yps, o); }
+    }
+  });
+}
+
 // One wave per row, rows strided by 4 inside a block; the next row's loads are issued before this row's
 // reductions, and gamma/beta are read from LDS so the row body never queues behind those loads on vmcnt.
-// RES ("f32-grade residual stream" of the 16-bit engines, simx.h stream_lo): the input row is  z = d + r_hi + r_lo  -- the
-// dense output (bias and dropout applied by the GEMM epilogue, no residual) plus the residual stream kept as a 16-bit value
-// and ONE correction byte (lo8, common.h: x = hi + (b - 128) ulp(hi) / 256) -- summed in f32, and the result leaves as
-// y_hi = round16(y) and the byte that encodes y - y_hi: the stream carries ~19 significand bits from layer to layer (apex O1
-// keeps it in fp32: residual additions promote to fp32 and LayerNorm is an fp32 function there) at 3 B per element, and z
-// never makes a round trip through HBM.
+// RES: the input row is rebuilt from the dense output and the residual stream (LnRowIn) and the result leaves as
+// y_hi = round16(y) and the byte that encodes y - y_hi (ln_store_row), so z never makes a round trip through HBM.
 template <typename T, int VPL, bool RES>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(int rows, int H, int rows_per_block, const T* __restrict__ z,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      float eps, T* __restrict__ y, const T* __restrict__ rh,
                                                      const uint8_t* __restrict__ rl, uint8_t* __restrict__ ylo,
                                                      bf16_t* __restrict__ yp = nullptr, long yps = 0) {
-  // yp (f32 engine, "operand planes"): y also leaves as the fp16 plane pair the next GEMM stages
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sgam = reinterpret_cast<float*>(smem);
   float* sbet = sgam + H;
@@ -89,73 +227,24 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(int rows, int H, int rows_p
   __syncthreads();
   const int r0 = blockIdx.x * rows_per_block;
   const int r1 = min(rows, r0 + rows_per_block);
-  Raw4<T> nx[VPL], nh[RES ? VPL : 1];
-  uint32_t nl[RES ? VPL : 1];                     // the residual's correction bytes (lo8, common.h), 4 elements per dword
-  auto issue = [&](int row) {
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        nx[v].load(z + (long)row * H + c);
-        if (RES) { nh[v].load(rh + (long)row * H + c); if (rl) nl[v] = *reinterpret_cast<const uint32_t*>(rl + (long)row * H + c); }
-      }
-    }
-  };
-  if (r0 + w < r1) issue(r0 + w);
+  LnRowIn<T, VPL, RES> in(H, lane, z, rh, rl);
+  if (r0 + w < r1) in.issue(r0 + w);
   for (int row = r0 + w; row < r1; row += 4) {
     float x[VPL][4];
-    float sum = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        nx[v].unpack(x[v]);
-        if (RES) {
-          float a[4];
-          nh[v].unpack(a);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) x[v][e] += a[e];
-          if (rl) {
-            lo8_decode4<T>(nh[v].w0(), nh[v].w1(), nl[v], a);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[v][e] += a[e];
-          }
-        }
-        sum += x[v][0] + x[v][1] + x[v][2] + x[v][3];
-      }
-    }
-    if (row + 4 < r1) issue(row + 4);
+    float sum;
+    in.take(x, sum);
+    if (row + 4 < r1) in.issue(row + 4);
+    // ln_centre + ln_rstd in ONE pass over the registers, as this kernel always had them: as two guarded passes the stream forward
+    // for H > 768 (<16-bit, 4, true>) needs 74 / 76 VGPRs instead of 72 and loses a wave of occupancy.  Same operations, same order.
     const float mu = wave_sum(sum) / (float)H;
     float sq = 0.f;
+    ln_cols<VPL>(H, lane, [&](int v, int) {
+#pragma clang fp contract(off)
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[v][e] -= mu; sq += x[v][e] * x[v][e]; }
-    }
+      for (int e = 0; e < 4; ++e) { x[v][e] -= mu; sq += x[v][e] * x[v][e]; }
+    });
     const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)H + eps);
-    T* yr = y + (long)row * H;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        float g[4], b[4], o[4];
-        ld4(sgam + c, g);
-        ld4(sbet + c, b);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = x[v][e] * rstd * g[e] + b[e];
-        if (RES && ylo) {                       // the correction: what the 16-bit rounding of y drops, one byte per element
-          float rr[4];
-          uint32_t w0, w1;
-          st4_residue(yr + c, o, rr, w0, w1);
-          *reinterpret_cast<uint32_t*>(ylo + (long)row * H + c) = lo8_encode4<T>(w0, w1, rr);
-        } else {
-          st4(yr + c, o);
-          if constexpr (std::is_same<T, float>::value) { if (yp) st4_planes<f16_t>(yp + (long)row * H + c, yps, o); }
-        }
-      }
-    }
+    ln_store_row<T, VPL>(H, lane, row, x, rstd, sgam, sbet, nullptr, y, RES ? ylo : nullptr, yp, yps);
   }
 }
 
@@ -169,54 +258,12 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(int rows, int H, cons
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + w;
   if (row >= rows) return;
-  const float* wr = word + (long)ids[row] * H;
-  const float* pr = posw + (long)pos[row] * H;
   float x[LN_VPL][4];
-  float sum = 0.f;
-#pragma unroll
-  for (int v = 0; v < LN_VPL; ++v) {
-    const int c = (v * 64 + lane) * 4;
-    if (c < H) {
-      float a[4], b[4], t[4];
-      ld4(wr + c, a);
-      ld4(pr + c, b);
-      ld4(typew + c, t);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { x[v][e] = a[e] + b[e] + t[e]; sum += x[v][e]; }
-    }
-  }
-  const float mu = wave_sum(sum) / (float)H;
-  float sq = 0.f;
-#pragma unroll
-  for (int v = 0; v < LN_VPL; ++v) {
-    const int c = (v * 64 + lane) * 4;
-    if (c < H)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { x[v][e] -= mu; sq += x[v][e] * x[v][e]; }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)H + eps);
-  T* yr = y + (long)row * H;
-#pragma unroll
-  for (int v = 0; v < LN_VPL; ++v) {
-    const int c = (v * 64 + lane) * 4;
-    if (c < H) {
-      float g[4], b[4], o[4];
-      ld4(gamma + c, g);
-      ld4(beta + c, b);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = x[v][e] * rstd * g[e] + b[e];
-      if (drop.thr) { float m4[4]; drop_mult4(drop, (uint32_t)row, (uint32_t)c, m4); o[0] *= m4[0]; o[1] *= m4[1]; o[2] *= m4[2]; o[3] *= m4[3]; }
-      if (ylo) {                                 // residual-stream correction (simx.h stream_lo)
-        float rr[4];
-        uint32_t w0, w1;
-        st4_residue(yr + c, o, rr, w0, w1);
-        *reinterpret_cast<uint32_t*>(ylo + (long)row * H + c) = lo8_encode4<T>(w0, w1, rr);
-      } else {
-        st4(yr + c, o);
-        if constexpr (std::is_same<T, float>::value) { if (yp) st4_planes<f16_t>(yp + (long)row * H + c, yps, o); }
-      }
-    }
-  }
+  float sum;
+  embed_row(H, lane, word + (long)ids[row] * H, posw + (long)pos[row] * H, typew, x, sum);
+  ln_centre(H, lane, sum, x);
+  const float rstd = ln_rstd(H, lane, x, eps);
+  ln_store_row<T, LN_VPL>(H, lane, row, x, rstd, gamma, beta, &drop, y, ylo, yp, yps);
 }
 
 // shared row-backward: given centred x (in/out: becomes xhat), dy -> dz ; accumulates column partials
@@ -224,38 +271,27 @@ template <int VPL>
 __device__ __forceinline__ void ln_row_bwd(int H, int lane, float (&x)[VPL][4], float (&dy)[VPL][4],
                                            const float* __restrict__ gamma, float eps, float (&dz)[VPL][4],
                                            float (&pg)[VPL][4], float (&pb)[VPL][4]) {
-  float sq = 0.f;
-#pragma unroll
-  for (int v = 0; v < VPL; ++v)
-    if ((v * 64 + lane) * 4 < H)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sq += x[v][e] * x[v][e];
-  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)H + eps);
+  const float rstd = ln_rstd(H, lane, x, eps);
   float s1 = 0.f, s2 = 0.f;
+  ln_cols<VPL>(H, lane, [&](int v, int c) {
+    float g[4];
+    ld4(gamma + c, g);
 #pragma unroll
-  for (int v = 0; v < VPL; ++v) {
-    const int c = (v * 64 + lane) * 4;
-    if (c < H) {
-      float g[4];
-      ld4(gamma + c, g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        x[v][e] *= rstd;                       // xhat
-        pg[v][e] += dy[v][e] * x[v][e];
-        pb[v][e] += dy[v][e];
-        dy[v][e] *= g[e];                      // dxhat
-        s1 += dy[v][e];
-        s2 += dy[v][e] * x[v][e];
-      }
+    for (int e = 0; e < 4; ++e) {
+      x[v][e] *= rstd;                       // xhat
+      pg[v][e] += dy[v][e] * x[v][e];
+      pb[v][e] += dy[v][e];
+      dy[v][e] *= g[e];                      // dxhat
+      s1 += dy[v][e];
+      s2 += dy[v][e] * x[v][e];
     }
-  }
+  });
   s1 = wave_sum(s1) / (float)H;
   s2 = wave_sum(s2) / (float)H;
+  ln_cols<VPL>(H, lane, [&](int v, int) {
 #pragma unroll
-  for (int v = 0; v < VPL; ++v)
-    if ((v * 64 + lane) * 4 < H)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dz[v][e] = rstd * (dy[v][e] - s1 - x[v][e] * s2);
+    for (int e = 0; e < 4; ++e) dz[v][e] = rstd * (dy[v][e] - s1 - x[v][e] * s2);
+  });
 }
 
 template <int VPL>
@@ -263,13 +299,10 @@ __device__ __forceinline__ void flush_cols(int H, int lane, int w, float (&p)[VP
                                            float* sred /* [4][H] */, float mul = 1.0f, float* det = nullptr) {
   // sum the 4 waves' partials through LDS, wave 0 issues the atomics (det: this workgroup's partial row of the
   // deterministic mode -- stored unscaled, det_reduce_kernel adds the rows in workgroup order)
+  ln_cols<VPL>(H, lane, [&](int v, int c) {
 #pragma unroll
-  for (int v = 0; v < VPL; ++v) {
-    const int c = (v * 64 + lane) * 4;
-    if (c < H)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sred[w * H + c + e] = p[v][e];
-  }
+    for (int e = 0; e < 4; ++e) sred[w * H + c + e] = p[v][e];
+  });
   __syncthreads();
   // all four waves issue the atomics, each instruction on 64 CONSECUTIVE columns (4 cache lines; the lane-owns-4-columns
   // layout would touch 16) -- every block of the grid adds into the same H addresses, so the L2 transaction count of
@@ -281,10 +314,22 @@ __device__ __forceinline__ void flush_cols(int H, int lane, int w, float (&p)[VP
   __syncthreads();
 }
 
+// the tail of the backward kernels: the workgroup's three column sums (dthird: dbias / dtype0, NULL skips it) x inv, by atomics or
+// -- deterministic mode -- into partial row block_index of det_part
+template <int VPL>
+__device__ __forceinline__ void flush3(int H, int lane, int w, float* sred, float (&pg)[VPL][4], float (&pb)[VPL][4], float (&pz)[VPL][4],
+                                       float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dthird, float inv,
+                                       float* __restrict__ det_part, long block_index) {
+  float* dp = det_part ? det_part + block_index * 3 * H : nullptr;
+  flush_cols(H, lane, w, pg, dgamma, sred, inv, dp);
+  flush_cols(H, lane, w, pb, dbeta, sred, inv, dp ? dp + H : nullptr);
+  if (dthird) flush_cols(H, lane, w, pz, dthird, sred, inv, dp ? dp + 2 * H : nullptr);
+}
+
 // One wave per row, rows strided by 4 inside a block.  The loads of row+4 are issued before row is processed
 // (gamma comes from LDS so nothing in the row body queues behind them on vmcnt), which doubles the bytes each
 // wave keeps in flight; the three column partials stay in registers and are flushed once per block.
-// RES: the LayerNorm input is rebuilt as z = d + r_hi + r_lo (see ln_fwd_kernel), rl may be NULL.
+// RES: the LayerNorm input is rebuilt as z = d + r_hi + r_lo (LnRowIn), rl may be NULL.
 template <typename T, int VPL, bool RES>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(int rows, int H, int rows_per_block, const T* __restrict__ z,
                                                      const float* __restrict__ gamma, float eps, const T* __restrict__ dyp,
@@ -309,74 +354,34 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int rows, int H, int rows_p
   // CU made it slower).
   (void)rows_per_block;
   const int r0 = blockIdx.x * 4, r1 = rows, rstep = (int)gridDim.x * 4;
-  Raw4<T> nx[VPL], nd[VPL], nh[RES ? VPL : 1];
-  uint32_t nl[RES ? VPL : 1];
-  auto issue = [&](int row) {
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        nx[v].load(z + (long)row * H + c);
-        nd[v].load(dyp + (long)row * H + c);
-        if (RES) { nh[v].load(rh + (long)row * H + c); if (rl) nl[v] = *reinterpret_cast<const uint32_t*>(rl + (long)row * H + c); }
-      }
-    }
-  };
-  if (r0 + w < r1) issue(r0 + w);
+  LnRowIn<T, VPL, RES> in(H, lane, z, rh, rl);
+  LnRowIn<T, VPL, false> din(H, lane, dyp, nullptr, nullptr);
+  if (r0 + w < r1) { in.issue(r0 + w); din.issue(r0 + w); }
   for (int row = r0 + w; row < r1; row += rstep) {
     float x[VPL][4], dy[VPL][4], dz[VPL][4];
-    float sum = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        nx[v].unpack(x[v]);
-        nd[v].unpack(dy[v]);
-        if (RES) {
-          float a[4];
-          nh[v].unpack(a);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) x[v][e] += a[e];
-          if (rl) {
-            lo8_decode4<T>(nh[v].w0(), nh[v].w1(), nl[v], a);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[v][e] += a[e];
-          }
-        }
-        sum += x[v][0] + x[v][1] + x[v][2] + x[v][3];
-      }
-    }
-    if (row + rstep < r1) issue(row + rstep);
-    const float mu = wave_sum(sum) / (float)H;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) x[v][e] -= mu;
+    float sum, dsum;
+    in.take(x, sum);
+    din.take(dy, dsum);
+    if (row + rstep < r1) { in.issue(row + rstep); din.issue(row + rstep); }
+    ln_centre(H, lane, sum, x);
     ln_row_bwd(H, lane, x, dy, sgam, eps, dz, pg, pb);
     T* o = dzp + (long)row * H;
+    ln_cols<VPL>(H, lane, [&](int v, int c) {
+      st4(o + c, dz[v]);
+      if (drop.thr) {                      // gradient of the dropped dense output (feeds dgrad / wgrad / bias grad)
+        float m4[4];
+        drop_mult4(drop, (uint32_t)(row_keys ? row_keys[row] : row), (uint32_t)c, m4);   // keys: rows gathered from a larger tensor
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        st4(o + c, dz[v]);
-        if (drop.thr) {                      // gradient of the dropped dense output (feeds dgrad / wgrad / bias grad)
-          float m4[4];
-          drop_mult4(drop, (uint32_t)(row_keys ? row_keys[row] : row), (uint32_t)c, m4);   // keys: rows gathered from a larger tensor
-#pragma unroll
-          for (int e = 0; e < 4; ++e) dz[v][e] *= m4[e];
-          if (!dzpl) st4(dzm + (long)row * H + c, dz[v]);
-        }
-        if constexpr (std::is_same<T, float>::value) { if (dzpl) st4_planes<bf16_t>(dzpl + (long)row * H + c, dzps, dz[v]); }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pz[v][e] += dz[v][e];
+        for (int e = 0; e < 4; ++e) dz[v][e] *= m4[e];
+        if (!dzpl) st4(dzm + (long)row * H + c, dz[v]);
       }
-    }
+      if constexpr (std::is_same<T, float>::value) { if (dzpl) st4_planes<bf16_t>(dzpl + (long)row * H + c, dzps, dz[v]); }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pz[v][e] += dz[v][e];
+    });
   }
-  const float inv = gs_inv(gs);                          // dy / dz travel multiplied by the loss scale; parameter gradients do not
-  float* dp = det_part ? det_part + (long)blockIdx.x * 3 * H : nullptr;
-  flush_cols(H, lane, w, pg, dgamma, sred, inv, dp);
-  flush_cols(H, lane, w, pb, dbeta, sred, inv, dp ? dp + H : nullptr);
-  if (dbias) flush_cols(H, lane, w, pz, dbias, sred, inv, dp ? dp + 2 * H : nullptr);
+  // dy / dz travel multiplied by the loss scale; parameter gradients do not
+  flush3(H, lane, w, sred, pg, pb, pz, dgamma, dbeta, dbias, gs_inv(gs), det_part, (long)blockIdx.x);
 }
 
 template <typename T, int VPL>
@@ -398,52 +403,26 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(int rows, int H, int 
   const int r1 = min(rows, r0 + rows_per_block);
   for (int row = r0 + w; row < r1; row += 4) {
     const long wid = ids[row], pid = pos[row];
-    const float* wr = word + wid * H;
-    const float* pr = posw + pid * H;
-    const T* dr = dyp + (long)row * H;
     float x[VPL][4], dy[VPL][4], dz[VPL][4];
-    float sum = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        float a[4], b[4], t[4];
-        ld4(wr + c, a);
-        ld4(pr + c, b);
-        ld4(typew + c, t);
-        ld4(dr + c, dy[v]);
-        if (drop.thr) { float m4[4]; drop_mult4(drop, (uint32_t)row, (uint32_t)c, m4); dy[v][0] *= m4[0]; dy[v][1] *= m4[1]; dy[v][2] *= m4[2]; dy[v][3] *= m4[3]; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[v][e] = a[e] + b[e] + t[e]; sum += x[v][e]; }
-      }
-    }
-    const float mu = wave_sum(sum) / (float)H;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) x[v][e] -= mu;
+    float sum;
+    embed_row(H, lane, word + wid * H, posw + pid * H, typew, x, sum);
+    embed_dy(H, lane, dyp + (long)row * H, drop, row, dy);
+    ln_centre(H, lane, sum, x);
     ln_row_bwd(H, lane, x, dy, gamma, eps, dz, pg, pb);
+    ln_cols<VPL>(H, lane, [&](int v, int c) {
+      if (det_rows)                              // deterministic mode: the table scatters are done by det_scatter_rows_kernel
+        *reinterpret_cast<float4*>(det_rows + (long)row * H + c) = make_float4(dz[v][0] * inv, dz[v][1] * inv, dz[v][2] * inv, dz[v][3] * inv);
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        if (det_rows)                              // deterministic mode: the table scatters are done by det_scatter_rows_kernel
-          *reinterpret_cast<float4*>(det_rows + (long)row * H + c) = make_float4(dz[v][0] * inv, dz[v][1] * inv, dz[v][2] * inv, dz[v][3] * inv);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (!det_rows) {
-            atomicAdd(dword + wid * H + c + e, dz[v][e] * inv);
-            atomicAdd(dpos + pid * H + c + e, dz[v][e] * inv);
-          }
-          pz[v][e] += dz[v][e];
+      for (int e = 0; e < 4; ++e) {
+        if (!det_rows) {
+          atomicAdd(dword + wid * H + c + e, dz[v][e] * inv);
+          atomicAdd(dpos + pid * H + c + e, dz[v][e] * inv);
         }
+        pz[v][e] += dz[v][e];
       }
-    }
+    });
   }
-  float* dp = det_part ? det_part + (long)blockIdx.x * 3 * H : nullptr;
-  flush_cols(H, lane, w, pg, dgamma, sred, inv, dp);
-  flush_cols(H, lane, w, pb, dbeta, sred, inv, dp ? dp + H : nullptr);
-  flush_cols(H, lane, w, pz, dtype0, sred, inv, dp ? dp + 2 * H : nullptr);
+  flush3(H, lane, w, sred, pg, pb, pz, dgamma, dbeta, dtype0, inv, det_part, (long)blockIdx.x);
 }
 
 // Position-major embedding backward: wave w of block (pg, sc) owns ONE in-sequence position p = 4 pg + w and walks the
@@ -479,40 +458,17 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_seq_kernel(int nseq, int seq
     const int row = t0 + p;
     const long wid = ids[row];
     pid = pos[row];
-    const float* wr = word + wid * H;
-    const float* pr = posw + pid * H;
-    const T* dr = dyp + (long)row * H;
     float x[VPL][4], dy[VPL][4], dz[VPL][4];
-    float sum = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        float a[4], b[4], t[4];
-        ld4(wr + c, a);
-        ld4(pr + c, b);
-        ld4(typew + c, t);
-        ld4(dr + c, dy[v]);
-        if (drop.thr) { float m4[4]; drop_mult4(drop, (uint32_t)row, (uint32_t)c, m4); dy[v][0] *= m4[0]; dy[v][1] *= m4[1]; dy[v][2] *= m4[2]; dy[v][3] *= m4[3]; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[v][e] = a[e] + b[e] + t[e]; sum += x[v][e]; }
-      }
-    }
-    const float mu = wave_sum(sum) / (float)H;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) x[v][e] -= mu;
+    float sum;
+    embed_row(H, lane, word + wid * H, posw + pid * H, typew, x, sum);
+    embed_dy(H, lane, dyp + (long)row * H, drop, row, dy);
+    ln_centre(H, lane, sum, x);
     ln_row_bwd(H, lane, x, dy, gamma, eps, dz, pg, pb);
+    ln_cols<VPL>(H, lane, [&](int v, int c) {
+      *reinterpret_cast<float4*>(patch + c) = make_float4(dz[v][0] * inv, dz[v][1] * inv, dz[v][2] * inv, dz[v][3] * inv);
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H) {
-        *reinterpret_cast<float4*>(patch + c) = make_float4(dz[v][0] * inv, dz[v][1] * inv, dz[v][2] * inv, dz[v][3] * inv);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pz[v][e] += dz[v][e];
-      }
-    }
+      for (int e = 0; e < 4; ++e) pz[v][e] += dz[v][e];
+    });
     __builtin_amdgcn_wave_barrier();
     float* wrow = det_rows ? det_rows + (long)row * H : dword + wid * H;   // deterministic mode: rows out, scattered in token order later
 #pragma unroll
@@ -523,18 +479,12 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_seq_kernel(int nseq, int seq
     __builtin_amdgcn_wave_barrier();
   }
   if (pid >= 0 && !det_rows) {                       // this wave's position row: its sum over the chunk's sequences
+    ln_cols<VPL>(H, lane, [&](int v, int c) {
 #pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-      const int c = (v * 64 + lane) * 4;
-      if (c < H)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) atomicAdd(dpos + pid * H + c + e, pz[v][e] * inv);
-    }
+      for (int e = 0; e < 4; ++e) atomicAdd(dpos + pid * H + c + e, pz[v][e] * inv);
+    });
   }
-  float* dp = det_part ? det_part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 3 * H : nullptr;
-  flush_cols(H, lane, w, pg, dgamma, sred, inv, dp);
-  flush_cols(H, lane, w, pb, dbeta, sred, inv, dp ? dp + H : nullptr);
-  flush_cols(H, lane, w, pz, dtype0, sred, inv, dp ? dp + 2 * H : nullptr);
+  flush3(H, lane, w, sred, pg, pb, pz, dgamma, dbeta, dtype0, inv, det_part, (long)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 template <typename T>
@@ -649,6 +599,12 @@ static int ln_check(int dtype, int T, int H, const char* who) {
   return SIMX_OK;
 }
 
+// plane pair buffer of the f32 engine's entry points (lo plane at + stride elements): 8-byte stores into both planes
+static int ln_planes_ok(const void* planes, long stride, const char* who) {
+  SIMX_REQUIRE(planes && stride % 4 == 0 && (((uintptr_t)planes) & 7) == 0, SIMX_ERR_BAD_SHAPE, "%s: bad plane buffer", who);
+  return SIMX_OK;
+}
+
 // rows per block for the row-looping LN kernels: ~2 blocks per CU measured best on MI355X (sweep in DESIGN.md)
 static int ln_rows_per_block(int T, const char* env, int dflt) {
   const char* e = getenv(env);
@@ -659,6 +615,32 @@ static int ln_rows_per_block(int T, const char* env, int dflt) {
 static int bwd_rows_per_block(int T) { return ln_rows_per_block(T, "SIMX_LN_BWD_BLOCKS", 768); }
 // vectors per lane by hidden size (186 -> 140 VGPRs for H = 768)
 #define LN_BY_H(TT, LAUNCH) do { if (H <= 256) LAUNCH(TT, 1); else if (H <= 768) LAUNCH(TT, 3); else LAUNCH(TT, 4); } while (0)
+
+// Workspace of the deterministic mode (SIMX_DETERMINISTIC=1; both pointers stay NULL without it): one row of 3 x H column partials
+// per workgroup, which simx_det_reduce adds in workgroup order, and -- embedding backwards, row_count = T -- the scaled dz rows
+// that simx_det_scatter_rows adds into the tables in token order.
+struct LnDetWs { float *part = nullptr, *rows = nullptr; };
+static int ln_det_ws(hipStream_t s, int nblk, int H, int row_count, LnDetWs* ws) {
+  if (!simx_det()) return SIMX_OK;
+  ws->part = simx_det_ws(s, ((size_t)nblk * 3 * H + (size_t)row_count * H) * sizeof(float));
+  if (!ws->part) return SIMX_ERR_WORKSPACE;
+  if (row_count) ws->rows = ws->part + (size_t)nblk * 3 * H;
+  return SIMX_OK;
+}
+
+// ln_fwd_kernel in the form the arguments ask for: RES with res_hi; res_lo / y_lo (16-bit dtypes) and the plane pair (f32) optional
+static int ln_fwd_launch(hipStream_t s, int dtype, int T, int H, const void* d, const void* res_hi, const void* res_lo, const float* gamma,
+                         const float* beta, float eps, void* y, void* y_lo, void* y_planes, long plane_stride, const char* who) {
+  const int rpb = ln_rows_per_block(T, "SIMX_LN_FWD_BLOCKS", 1 << 30);   // 16 rows (4 per wave) per block measured best
+  const size_t lds = (size_t)2 * H * sizeof(float);
+#define LF(TT, V) hipLaunchKernelGGL((res_hi ? ln_fwd_kernel<TT, V, true> : ln_fwd_kernel<TT, V, false>), dim3(cdiv(T, rpb)), dim3(256), lds, s, T, H, \
+                                     rpb, (const TT*)d, gamma, beta, eps, (TT*)y, (const TT*)res_hi, (const uint8_t*)res_lo, (uint8_t*)y_lo,        \
+                                     (bf16_t*)y_planes, plane_stride)
+  SIMX_DISPATCH3(dtype, TT, LN_BY_H(TT, LF));
+#undef LF
+  SIMX_CHECK_LAUNCH(who);
+  return SIMX_OK;
+}
 
 extern "C" int simx_ln_fwd(simx_stream_t stream, int dtype, int T, int H, const void* z, const float* gamma,
                            const float* beta, float eps, void* y) {
@@ -672,17 +654,7 @@ extern "C" int simx_ln_fwd_res(simx_stream_t stream, int dtype, int T, int H, co
   int rc = ln_check(dtype, T, H, "ln_fwd");
   if (rc) return rc;
   SIMX_REQUIRE(res_hi || (!res_lo && !y_lo), SIMX_ERR_BAD_SHAPE, "ln_fwd_res: res_lo / y_lo need res_hi");
-  hipStream_t s = (hipStream_t)stream;
-  const int rpb = ln_rows_per_block(T, "SIMX_LN_FWD_BLOCKS", 1 << 30);   // 16 rows (4 per wave) per block measured best
-  const size_t lds = (size_t)2 * H * sizeof(float);
-#define LF(TT, V) do { if (res_hi) hipLaunchKernelGGL((ln_fwd_kernel<TT, V, true>), dim3(cdiv(T, rpb)), dim3(256), lds, s, T, H, rpb, (const TT*)d, gamma, beta, \
-                                    eps, (TT*)y, (const TT*)res_hi, (const uint8_t*)res_lo, (uint8_t*)y_lo);                                    \
-                       else hipLaunchKernelGGL((ln_fwd_kernel<TT, V, false>), dim3(cdiv(T, rpb)), dim3(256), lds, s, T, H, rpb, (const TT*)d, gamma, beta, \
-                                    eps, (TT*)y, (const TT*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr); } while (0)
-  SIMX_DISPATCH3(dtype, TT, LN_BY_H(TT, LF));
-#undef LF
-  SIMX_CHECK_LAUNCH("ln_fwd");
-  return SIMX_OK;
+  return ln_fwd_launch((hipStream_t)stream, dtype, T, H, d, res_hi, res_lo, gamma, beta, eps, y, y_lo, /*y_planes*/ nullptr, /*plane_stride*/ 0, "ln_fwd");
 }
 
 // f32 engine with operand planes: y (f32) and its fp16 plane pair (y_planes, lo at + plane_stride elements; leading dimension H)
@@ -691,15 +663,30 @@ extern "C" int simx_ln_fwd_planes(simx_stream_t stream, int T, int H, const floa
   SIMX_PROF(SIMX_K_LN_FWD, stream, (double)T * H * 12);
   int rc = ln_check(SIMX_F32, T, H, "ln_fwd_planes");
   if (rc) return rc;
-  SIMX_REQUIRE(y_planes && plane_stride % 4 == 0 && (((uintptr_t)y_planes) & 7) == 0, SIMX_ERR_BAD_SHAPE, "ln_fwd_planes: bad plane buffer");
-  hipStream_t s = (hipStream_t)stream;
-  const int rpb = ln_rows_per_block(T, "SIMX_LN_FWD_BLOCKS", 1 << 30);
-  const size_t lds = (size_t)2 * H * sizeof(float);
-#define LFP(TT, V) hipLaunchKernelGGL((ln_fwd_kernel<float, V, false>), dim3(cdiv(T, rpb)), dim3(256), lds, s, T, H, rpb, z, gamma, beta, eps, y, \
-                                      (const float*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr, (bf16_t*)y_planes, plane_stride)
-  LN_BY_H(float, LFP);
-#undef LFP
-  SIMX_CHECK_LAUNCH("ln_fwd_planes");
+  rc = ln_planes_ok(y_planes, plane_stride, "ln_fwd_planes");
+  if (rc) return rc;
+  return ln_fwd_launch((hipStream_t)stream, SIMX_F32, T, H, z, /*res_hi*/ nullptr, /*res_lo*/ nullptr, gamma, beta, eps, y, /*y_lo*/ nullptr, y_planes,
+                       plane_stride, "ln_fwd_planes");
+}
+
+// ln_bwd_kernel in the form the arguments ask for (RES with res_hi; masked copy or bf16 plane pair of the dropped output's
+// gradient), and the ordered sums of the deterministic mode
+static int ln_bwd_launch(hipStream_t s, int dtype, int T, int H, const void* z, const void* res_hi, const void* res_lo, const float* gamma,
+                         float eps, const void* dy, void* dz, void* dz_masked, void* dzm_planes, long plane_stride, float* dgamma,
+                         float* dbeta, float* dbias, const DropCtx& drop, const int32_t* row_keys, const float* gs, const char* who) {
+  const int rpb = bwd_rows_per_block(T);
+  const size_t lds = (size_t)5 * H * sizeof(float);
+  const int nblk = cdiv(T, rpb);
+  LnDetWs det;
+  int rc = ln_det_ws(s, nblk, H, 0, &det);
+  if (rc) return rc;
+#define LB(TT, V) hipLaunchKernelGGL((res_hi ? ln_bwd_kernel<TT, V, true> : ln_bwd_kernel<TT, V, false>), dim3(nblk), dim3(256), lds, s, T, H, rpb,    \
+                                     (const TT*)z, gamma, eps, (const TT*)dy, (TT*)dz, dgamma, dbeta, dbias, (TT*)dz_masked, drop, row_keys, gs,     \
+                                     (const TT*)res_hi, (const uint8_t*)res_lo, det.part, (bf16_t*)dzm_planes, plane_stride)
+  SIMX_DISPATCH3(dtype, TT, LN_BY_H(TT, LB));
+#undef LB
+  SIMX_CHECK_LAUNCH(who);
+  if (det.part) return simx_det_reduce(s, det.part, 3L * H, nblk, H, dgamma, dbeta, dbias, gs);
   return SIMX_OK;
 }
 
@@ -736,24 +723,8 @@ extern "C" int simx_ln_bwd_res(simx_stream_t stream, int dtype, int T, int H, co
   SIMX_REQUIRE(res_hi || !res_lo, SIMX_ERR_BAD_SHAPE, "ln_bwd_res: res_lo needs res_hi");
   const DropCtx drop = make_drop(dropd);
   SIMX_REQUIRE(!drop.thr || dz_masked, SIMX_ERR_BAD_SHAPE, "ln_bwd: dropout needs the dz_masked output");
-  hipStream_t s = (hipStream_t)stream;
-  const int rpb = bwd_rows_per_block(T);
-  const size_t lds = (size_t)5 * H * sizeof(float);
-  const int nblk = cdiv(T, rpb);
-  float* det = nullptr;
-  if (simx_det()) {
-    det = simx_det_ws(s, (size_t)nblk * 3 * H * sizeof(float));
-    if (!det) return SIMX_ERR_WORKSPACE;
-  }
-#define LB(TT, V) do { if (res_hi) hipLaunchKernelGGL((ln_bwd_kernel<TT, V, true>), dim3(cdiv(T, rpb)), dim3(256), lds, s, T, H, rpb, (const TT*)z, gamma, eps, \
-                                    (const TT*)dy, (TT*)dz, dgamma, dbeta, dbias, (TT*)dz_masked, drop, row_keys, gs, (const TT*)res_hi, (const uint8_t*)res_lo, det); \
-                       else hipLaunchKernelGGL((ln_bwd_kernel<TT, V, false>), dim3(cdiv(T, rpb)), dim3(256), lds, s, T, H, rpb, (const TT*)z, gamma, eps, \
-                                    (const TT*)dy, (TT*)dz, dgamma, dbeta, dbias, (TT*)dz_masked, drop, row_keys, gs, (const TT*)nullptr, (const uint8_t*)nullptr, det); } while (0)
-  SIMX_DISPATCH3(dtype, TT, LN_BY_H(TT, LB));
-#undef LB
-  SIMX_CHECK_LAUNCH("ln_bwd");
-  if (det) return simx_det_reduce(s, det, 3L * H, nblk, H, dgamma, dbeta, dbias, gs);
-  return SIMX_OK;
+  return ln_bwd_launch((hipStream_t)stream, dtype, T, H, z, res_hi, res_lo, gamma, eps, dy, dz, dz_masked, /*dzm_planes*/ nullptr, /*plane_stride*/ 0,
+                       dgamma, dbeta, dbias, drop, row_keys, gs, "ln_bwd");
 }
 
 // f32 engine with operand planes: dz (f32, the residual branch's gradient) and the bf16 plane pair of the dropped dense
@@ -763,24 +734,19 @@ extern "C" int simx_ln_bwd_planes(simx_stream_t stream, int T, int H, const floa
   SIMX_PROF(SIMX_K_LN_BWD, stream, (double)T * H * 16);
   int rc = ln_check(SIMX_F32, T, H, "ln_bwd_planes");
   if (rc) return rc;
-  SIMX_REQUIRE(dzm_planes && plane_stride % 4 == 0 && (((uintptr_t)dzm_planes) & 7) == 0, SIMX_ERR_BAD_SHAPE, "ln_bwd_planes: bad plane buffer");
-  const DropCtx drop = make_drop(dropd);
-  hipStream_t s = (hipStream_t)stream;
-  const int rpb = bwd_rows_per_block(T);
-  const size_t lds = (size_t)5 * H * sizeof(float);
-  const int nblk = cdiv(T, rpb);
-  float* det = nullptr;
-  if (simx_det()) {
-    det = simx_det_ws(s, (size_t)nblk * 3 * H * sizeof(float));
-    if (!det) return SIMX_ERR_WORKSPACE;
-  }
-#define LBP(TT, V) hipLaunchKernelGGL((ln_bwd_kernel<float, V, false>), dim3(cdiv(T, rpb)), dim3(256), lds, s, T, H, rpb, z, gamma, eps, dy, dz, dgamma, dbeta, \
-                                      dbias, (float*)nullptr, drop, (const int*)nullptr, (const float*)nullptr, (const float*)nullptr,                     \
-                                      (const uint8_t*)nullptr, det, (bf16_t*)dzm_planes, plane_stride)
-  LN_BY_H(float, LBP);
-#undef LBP
-  SIMX_CHECK_LAUNCH("ln_bwd_planes");
-  if (det) return simx_det_reduce(s, det, 3L * H, nblk, H, dgamma, dbeta, dbias, nullptr);
+  rc = ln_planes_ok(dzm_planes, plane_stride, "ln_bwd_planes");
+  if (rc) return rc;
+  return ln_bwd_launch((hipStream_t)stream, SIMX_F32, T, H, z, /*res_hi*/ nullptr, /*res_lo*/ nullptr, gamma, eps, dy, dz, /*dz_masked*/ nullptr, dzm_planes,
+                       plane_stride, dgamma, dbeta, dbias, make_drop(dropd), /*row_keys*/ nullptr, /*gs*/ nullptr, "ln_bwd_planes");
+}
+
+// embed_ln_fwd_kernel: out_lo (16-bit dtypes) and the plane pair (f32) optional
+static int embed_ln_fwd_launch(hipStream_t s, int dtype, int T, int H, const int32_t* ids, const int32_t* pos_ids, const float* word,
+                               const float* posw, const float* typew, const float* gamma, const float* beta, float eps, void* out,
+                               const DropCtx& drop, void* out_lo, void* out_planes, long plane_stride, const char* who) {
+  SIMX_DISPATCH3(dtype, TT, hipLaunchKernelGGL((embed_ln_fwd_kernel<TT>), dim3(cdiv(T, 4)), dim3(256), 0, s, T, H, ids, pos_ids, word, posw, typew,
+                                               gamma, beta, eps, (TT*)out, drop, (uint8_t*)out_lo, (bf16_t*)out_planes, plane_stride));
+  SIMX_CHECK_LAUNCH(who);
   return SIMX_OK;
 }
 
@@ -791,11 +757,10 @@ extern "C" int simx_embed_ln_fwd_planes(simx_stream_t stream, int T, int H, cons
   SIMX_PROF(SIMX_K_EMBED_FWD, stream, (double)T * H * 12);
   int rc = ln_check(SIMX_F32, T, H, "embed_ln_fwd_planes");
   if (rc) return rc;
-  SIMX_REQUIRE(out_planes && plane_stride % 4 == 0 && (((uintptr_t)out_planes) & 7) == 0, SIMX_ERR_BAD_SHAPE, "embed_ln_fwd_planes: bad plane buffer");
-  hipLaunchKernelGGL((embed_ln_fwd_kernel<float>), dim3(cdiv(T, 4)), dim3(256), 0, (hipStream_t)stream, T, H, ids, pos_ids, word, posw, typew, gamma,
-                     beta, eps, out, drop, (uint8_t*)nullptr, (bf16_t*)out_planes, plane_stride);
-  SIMX_CHECK_LAUNCH("embed_ln_fwd_planes");
-  return SIMX_OK;
+  rc = ln_planes_ok(out_planes, plane_stride, "embed_ln_fwd_planes");
+  if (rc) return rc;
+  return embed_ln_fwd_launch((hipStream_t)stream, SIMX_F32, T, H, ids, pos_ids, word, posw, typew, gamma, beta, eps, out, drop, /*out_lo*/ nullptr, out_planes,
+                             plane_stride, "embed_ln_fwd_planes");
 }
 
 extern "C" int simx_embed_ln_fwd(simx_stream_t stream, int dtype, int T, int H, const int32_t* ids, const int32_t* pos_ids,
@@ -816,22 +781,18 @@ extern "C" int simx_embed_ln_fwd_lo(simx_stream_t stream, int dtype, int T, int 
   SIMX_PROF(SIMX_K_EMBED_FWD, stream, (double)T * H * (4 + simx_esz(dtype)));
   int rc = ln_check(dtype, T, H, "embed_ln_fwd");
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  SIMX_DISPATCH3(dtype, TT, hipLaunchKernelGGL((embed_ln_fwd_kernel<TT>), dim3(cdiv(T, 4)), dim3(256), 0, s, T, H, ids, pos_ids, word,
-                                               posw, typew, gamma, beta, eps, (TT*)out, drop, (uint8_t*)out_lo));
-  SIMX_CHECK_LAUNCH("embed_ln_fwd");
-  return SIMX_OK;
+  return embed_ln_fwd_launch((hipStream_t)stream, dtype, T, H, ids, pos_ids, word, posw, typew, gamma, beta, eps, out, drop, out_lo, /*out_planes*/ nullptr,
+                             /*plane_stride*/ 0, "embed_ln_fwd");
 }
 
-// deterministic mode: the kernels left the scaled dz rows in det_rows and one column partial per workgroup in det_part
-static int embed_det_finish(hipStream_t s, int T, int H, const int32_t* ids, const int32_t* pos_ids, const float* det_part,
-                            const float* det_rows, int nblk, float* dword, float* dpos, float* dtype0, float* dgamma, float* dbeta,
-                            const float* gs) {
-  int rc = simx_det_scatter_rows(s, T, H, ids, det_rows, dword, 4096);
+// deterministic mode: the kernels left the scaled dz rows in det.rows and one column partial per workgroup in det.part
+static int embed_det_finish(hipStream_t s, int T, int H, const int32_t* ids, const int32_t* pos_ids, const LnDetWs& det, int nblk,
+                            float* dword, float* dpos, float* dtype0, float* dgamma, float* dbeta, const float* gs) {
+  int rc = simx_det_scatter_rows(s, T, H, ids, det.rows, dword, 4096);
   if (rc) return rc;
-  rc = simx_det_scatter_rows(s, T, H, pos_ids, det_rows, dpos, 512);
+  rc = simx_det_scatter_rows(s, T, H, pos_ids, det.rows, dpos, 512);
   if (rc) return rc;
-  return simx_det_reduce(s, det_part, 3L * H, nblk, H, dgamma, dbeta, dtype0, gs);
+  return simx_det_reduce(s, det.part, 3L * H, nblk, H, dgamma, dbeta, dtype0, gs);
 }
 
 extern "C" int simx_embed_ln_bwd(simx_stream_t stream, int dtype, int T, int H, const int32_t* ids, const int32_t* pos_ids,
@@ -854,18 +815,15 @@ extern "C" int simx_embed_ln_bwd_ex(simx_stream_t stream, int dtype, int T, int 
   const size_t lds = (size_t)4 * H * sizeof(float);
   const float* gs = nullptr;
   const int nblk = cdiv(T, rpb);
-  float *det = nullptr, *det_rows = nullptr;
-  if (simx_det()) {
-    det = simx_det_ws(s, ((size_t)nblk * 3 * H + (size_t)T * H) * sizeof(float));
-    if (!det) return SIMX_ERR_WORKSPACE;
-    det_rows = det + (size_t)nblk * 3 * H;
-  }
+  LnDetWs det;
+  rc = ln_det_ws(s, nblk, H, T, &det);
+  if (rc) return rc;
 #define EB(TT, V) hipLaunchKernelGGL((embed_ln_bwd_kernel<TT, V>), dim3(nblk), dim3(256), lds, s, T, H, rpb, ids, pos_ids, word, posw, \
-                                    typew, gamma, eps, (const TT*)dy, dword, dpos, dtype0, dgamma, dbeta, drop, gs, det, det_rows)
+                                    typew, gamma, eps, (const TT*)dy, dword, dpos, dtype0, dgamma, dbeta, drop, gs, det.part, det.rows)
   SIMX_DISPATCH3(dtype, TT, LN_BY_H(TT, EB));
 #undef EB
   SIMX_CHECK_LAUNCH("embed_ln_bwd");
-  if (det) return embed_det_finish(s, T, H, ids, pos_ids, det, det_rows, nblk, dword, dpos, dtype0, dgamma, dbeta, gs);
+  if (det.part) return embed_det_finish(s, T, H, ids, pos_ids, det, nblk, dword, dpos, dtype0, dgamma, dbeta, gs);
   return SIMX_OK;
 }
 
@@ -895,18 +853,15 @@ extern "C" int simx_embed_ln_bwd_seq_gs(simx_stream_t stream, int dtype, int nse
   const dim3 grid(pgroups, cdiv(nseq, spb));
   const size_t lds = (size_t)(4 * H + 4 * LN_VPL * 256) * sizeof(float);      // column-flush scratch + per-wave scatter patches
   const int nblk = (int)(grid.x * grid.y);
-  float *det = nullptr, *det_rows = nullptr;
-  if (simx_det()) {
-    det = simx_det_ws(s, ((size_t)nblk * 3 * H + (size_t)T * H) * sizeof(float));
-    if (!det) return SIMX_ERR_WORKSPACE;
-    det_rows = det + (size_t)nblk * 3 * H;
-  }
+  LnDetWs det;
+  rc = ln_det_ws(s, nblk, H, T, &det);
+  if (rc) return rc;
 #define ES(TT, V) hipLaunchKernelGGL((embed_ln_bwd_seq_kernel<TT, V>), grid, dim3(256), lds, s, nseq, spb, H, cu_seqlens, ids, pos_ids, word, \
-                                    posw, typew, gamma, eps, (const TT*)dy, dword, dpos, dtype0, dgamma, dbeta, drop, gs, det, det_rows)
+                                    posw, typew, gamma, eps, (const TT*)dy, dword, dpos, dtype0, dgamma, dbeta, drop, gs, det.part, det.rows)
   SIMX_DISPATCH3(dtype, TT, LN_BY_H(TT, ES));
 #undef ES
   SIMX_CHECK_LAUNCH("embed_ln_bwd_seq");
-  if (det) return embed_det_finish(s, T, H, ids, pos_ids, det, det_rows, nblk, dword, dpos, dtype0, dgamma, dbeta, gs);
+  if (det.part) return embed_det_finish(s, T, H, ids, pos_ids, det, nblk, dword, dpos, dtype0, dgamma, dbeta, gs);
   return SIMX_OK;
 }
 
