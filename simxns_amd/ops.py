@@ -137,67 +137,61 @@ def _scores_ws(Q, Cn, H, q_n, c_n, device):
     return (torch.empty(n, dtype=torch.uint8, device=device) if n else None), n
 
 
-class _NllFn(torch.autograd.Function):
+class _ScoresFn(torch.autograd.Function):
+    """The all-pairs losses.  kd: None for the NLL form, else (kd_type, teacher q, teacher ctx, T, ce_w, kd_w, alpha, beta)
+    with the teacher's (constant) embeddings."""
+
     @staticmethod
-    def forward(ctx, q, c, pos_idx, loss_scale, q_lo, q_n, c_lo, c_n):
+    def forward(ctx, q, c, pos_idx, loss_scale, q_lo, q_n, c_lo, c_n, kd):
         q, c = _f32c(q), _f32c(c)
         Q, H = q.shape
         Cn = c.shape[0]
+        if kd is not None:
+            kd_type, tq, tc, T, ce_w, kd_w, alpha, beta = kd
+            tq, tc = _f32c(tq.detach()), _f32c(tc.detach())
+            bi = kd_type == L.KD_BI_LOGIT
+            if bi and (tq.shape != q.shape or tc.shape != c.shape):
+                raise ValueError("Bi_logit compares embeddings: teacher shapes %s / %s differ from the student's %s / %s"
+                                 % (tuple(tq.shape), tuple(tc.shape), tuple(q.shape), tuple(c.shape)))
         pos = torch.as_tensor(pos_idx, dtype=torch.int32, device=q.device).contiguous()
         scores = torch.empty(Q, Cn, dtype=torch.float32, device=q.device)
         losses = torch.empty(4, dtype=torch.float32, device=q.device)
-        dq = torch.zeros_like(q)
-        dc = torch.zeros_like(c)
+        dq, dc = torch.zeros_like(q), torch.zeros_like(c)
         ws, wsb = _scores_ws(Q, Cn, H, q_n, c_n, q.device)
-        L.call("simx_scores_nll_fwd_bwd", L.stream_ptr(), Q, Cn, H, L.ptr(q), L.ptr(c), L.ptr(pos),
-               float(loss_scale or 1.0), q_lo, q_n, c_lo, c_n, L.ptr(scores), None, L.ptr(losses),
-               C.c_void_p(dq.data_ptr() + q_lo * H * 4), C.c_void_p(dc.data_ptr() + c_lo * H * 4), L.ptr(ws) if wsb else None, wsb)
+        scale_slots = (float(loss_scale or 1.0), q_lo, q_n, c_lo, c_n)
+        outs = (L.ptr(losses), C.c_void_p(dq.data_ptr() + q_lo * H * 4), C.c_void_p(dc.data_ptr() + c_lo * H * 4),
+                L.ptr(ws) if wsb else None, wsb)
+        if kd is None:
+            L.call("simx_scores_nll_fwd_bwd", L.stream_ptr(), Q, Cn, H, L.ptr(q), L.ptr(c), L.ptr(pos), *scale_slots,
+                   L.ptr(scores), None, *outs)
+        else:
+            tscores = None if bi else torch.empty(Q, Cn, dtype=torch.float32, device=q.device)
+            L.call("simx_scores_kd_type_fwd_bwd", L.stream_ptr(), kd_type, Q, Cn, H, tq.shape[1], L.ptr(q), L.ptr(c), L.ptr(tq), L.ptr(tc),
+                   L.ptr(pos), float(T), float(ce_w), float(kd_w), float(alpha), float(beta), *scale_slots, L.ptr(scores),
+                   L.ptr(tscores), *outs)
         ctx.save_for_backward(dq, dc)
         return losses[0], losses.detach()
 
     @staticmethod
     def backward(ctx, g, g_all):
         dq, dc = ctx.saved_tensors
-        return dq * g, dc * g, None, None, None, None, None, None
+        return (dq * g, dc * g) + (None,) * 7
+
+
+def _slots(q_vectors, ctx_vectors, local_q, local_ctx):
+    """(q_lo, q_n, c_lo, c_n): the rows that carry gradient; default all rows."""
+    q_lo, q_n = local_q if local_q is not None else (0, q_vectors.shape[0])
+    c_lo, c_n = local_ctx if local_ctx is not None else (0, ctx_vectors.shape[0])
+    return q_lo, q_n, c_lo, c_n
 
 
 def inbatch_nll_loss(q_vectors, ctx_vectors, positive_idx_per_question, loss_scale=None, local_q=None, local_ctx=None):
     """dot_product_scores + log_softmax + nll_loss(mean) + argmax count (models.py:468-505).
     local_q / local_ctx = (lo, n): rows that carry gradient (multi-GPU gather semantics,
     PROD/ProD_base/train_DE_model_marco.py:251-264); default all rows."""
-    q_lo, q_n = local_q if local_q is not None else (0, q_vectors.shape[0])
-    c_lo, c_n = local_ctx if local_ctx is not None else (0, ctx_vectors.shape[0])
-    loss, allv = _NllFn.apply(q_vectors, ctx_vectors, positive_idx_per_question, loss_scale, q_lo, q_n, c_lo, c_n)
+    loss, allv = _ScoresFn.apply(q_vectors, ctx_vectors, positive_idx_per_question, loss_scale,
+                                 *_slots(q_vectors, ctx_vectors, local_q, local_ctx), None)
     return loss, allv[3]
-
-
-class _KdFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, c, tq, tc, pos_idx, T, ce_w, kd_w, loss_scale, q_lo, q_n, c_lo, c_n, kd, alpha, beta):
-        q, c, tq, tc = _f32c(q), _f32c(c), _f32c(tq.detach()), _f32c(tc.detach())
-        Q, H = q.shape
-        Cn, HT = c.shape[0], tq.shape[1]
-        bi = kd == L.KD_BI_LOGIT
-        if bi and (tq.shape != q.shape or tc.shape != c.shape):
-            raise ValueError("Bi_logit compares embeddings: teacher shapes %s / %s differ from the student's %s / %s"
-                             % (tuple(tq.shape), tuple(tc.shape), tuple(q.shape), tuple(c.shape)))
-        pos = torch.as_tensor(pos_idx, dtype=torch.int32, device=q.device).contiguous()
-        scores = torch.empty(Q, Cn, dtype=torch.float32, device=q.device)
-        tscores = None if bi else torch.empty(Q, Cn, dtype=torch.float32, device=q.device)
-        losses = torch.empty(4, dtype=torch.float32, device=q.device)
-        dq, dc = torch.zeros_like(q), torch.zeros_like(c)
-        ws, wsb = _scores_ws(Q, Cn, H, q_n, c_n, q.device)
-        L.call("simx_scores_kd_type_fwd_bwd", L.stream_ptr(), kd, Q, Cn, H, HT, L.ptr(q), L.ptr(c), L.ptr(tq), L.ptr(tc), L.ptr(pos),
-               float(T), float(ce_w), float(kd_w), float(alpha), float(beta), float(loss_scale or 1.0), q_lo, q_n, c_lo, c_n,
-               L.ptr(scores), L.ptr(tscores), L.ptr(losses), C.c_void_p(dq.data_ptr() + q_lo * H * 4),
-               C.c_void_p(dc.data_ptr() + c_lo * H * 4), L.ptr(ws) if wsb else None, wsb)
-        ctx.save_for_backward(dq, dc)
-        return losses[0], losses.detach()
-
-    @staticmethod
-    def backward(ctx, g, g_all):
-        dq, dc = ctx.saved_tensors
-        return (dq * g, dc * g) + (None,) * 14
 
 
 def bi_kd_loss(q_vectors, ctx_vectors, teacher_q_vector, teacher_ctxs_vector, positive_idx_per_question, temperature=4.0,
@@ -207,10 +201,9 @@ def bi_kd_loss(q_vectors, ctx_vectors, teacher_q_vector, teacher_ctxs_vector, po
     teacher embeddings, soft term chosen by ``kd_type`` (KD_softmax, KD_logit, DKD with ``dkd_alpha`` / ``dkd_beta``), or
     Bi_logit: an MSE between student and teacher embeddings of the same width.  -> (loss, hard, soft, correct_count)."""
     kd, alpha, beta = _kd_kind(BI_KD_TYPES, kd_type, dkd_alpha, dkd_beta)
-    q_lo, q_n = local_q if local_q is not None else (0, q_vectors.shape[0])
-    c_lo, c_n = local_ctx if local_ctx is not None else (0, ctx_vectors.shape[0])
-    loss, allv = _KdFn.apply(q_vectors, ctx_vectors, teacher_q_vector, teacher_ctxs_vector, positive_idx_per_question,
-                             temperature, ce_weight, kd_weight, loss_scale, q_lo, q_n, c_lo, c_n, kd, alpha, beta)
+    loss, allv = _ScoresFn.apply(q_vectors, ctx_vectors, positive_idx_per_question, loss_scale,
+                                 *_slots(q_vectors, ctx_vectors, local_q, local_ctx),
+                                 (kd, teacher_q_vector, teacher_ctxs_vector, temperature, ce_weight, kd_weight, alpha, beta))
     return loss, allv[1], allv[2], allv[3]
 
 

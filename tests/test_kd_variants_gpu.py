@@ -187,12 +187,13 @@ def test_unknown_kind_is_unsupported(dev):
     assert float(dq.abs().max()) == 0.0 and float(dc.abs().max()) == 0.0
 
 
-# ------------------------------------------------------------------------------------------ KD_softmax is untouched
+# ------------------------------------------------------------------------------------------ one call, one row body
 @pytest.mark.parametrize("rows", [2, 9])
-def test_kd_softmax_through_new_arguments_is_bit_identical(dev, rows):
-    """KD_softmax with the new arguments spelled out == the call without them, bit for bit.  The loss scalars are f32 atomic
-    sums over the rows, whose order is only fixed for two rows (a + b == b + a), so they are compared there; the gradients
-    and the per-row work carry no atomics and are compared at both sizes."""
+def test_kd_softmax_defaulted_and_spelled_out_are_the_same_call(dev, rows):
+    """KD_softmax with kd_type and the DKD weights spelled out == the call that leaves them at their defaults, bit for bit: both
+    are the same launch, and alpha / beta reach no KD_softmax arithmetic.  The loss scalars are f32 atomic sums over the rows,
+    whose order is only fixed for two rows (a + b == b + a), so they are compared there; the gradients and the per-row work
+    carry no atomics and are compared at both sizes."""
     from simxns_amd import ops
     rs = np.random.RandomState(rows)
     D, H, C = 16, 64, 24
@@ -218,6 +219,25 @@ def test_kd_softmax_through_new_arguments_is_bit_identical(dev, rows):
                 assert torch.equal(a, b)
             else:
                 assert abs(a.item() - b.item()) <= 1e-6 * max(1.0, abs(a.item()))
+
+
+@pytest.mark.parametrize("C", [24, 130])
+def test_all_pairs_forms_agree_on_the_hard_term(dev, C):
+    """What every objective of the all-pairs row kernel shares -- lse = m + log(s1), hard = (lse - S[pos]) / Q, the arg-max
+    count -- is the same bits whichever objective runs: the NLL loss (loss_scale 1) == the hard term of each kd_type.  Two rows,
+    so that the atomic sum of the rows has one order; C below one lane stride and with a tail after two."""
+    from simxns_amd import ops
+    Q, H = 2, 64
+    rs = np.random.RandomState(C)
+    q, c, tq_, tc_ = _emb(rs, Q, H), _emb(rs, C, H), _emb(rs, Q, H), _emb(rs, C, H)
+    pos = [0, C - 1]
+    nll, nll_correct = ops.inbatch_nll_loss(_t(q, dev), _t(c, dev), pos, 1.0)
+    for kd_type in BI_TYPES:
+        _, hard, _, correct = ops.bi_kd_loss(_t(q, dev), _t(c, dev), _t(tq_, dev), _t(tc_, dev), pos, HP["T"], HP["ce_w"], HP["kd_w"],
+                                             1.0, None, None, kd_type, HP["alpha"], HP["beta"])
+        print("%s C%d: nll %s hard %s" % (kd_type, C, float(nll.item()).hex(), float(hard.item()).hex()))
+        assert torch.equal(nll, hard), kd_type
+        assert torch.equal(nll_correct, correct), kd_type
 
 
 # ------------------------------------------------------------------------------------------ SIMX_DETERMINISTIC=1

@@ -198,6 +198,43 @@ def test_inbatch_nll_config3_full_shape_each_local_slot(dev):
         assert np.abs(gq).max() == 0.0 and np.abs(gc).max() == 0.0, "remote rows must not receive gradient"
 
 
+def _nll_abi(dev, q, c, pos, with_stats):
+    """simx_scores_nll_fwd_bwd itself, every row local, unsplit products -> (row_stats [Q,2] or None, losses, dq, dc)."""
+    from simxns_amd import _lib as L
+    tq, tc = _t(q, dev), _t(c, dev)
+    (Q, H), Cn = tq.shape, tc.shape[0]
+    tpos = torch.tensor(pos, dtype=torch.int32, device=dev)
+    scores, losses = torch.empty(Q, Cn, device=dev), torch.empty(4, device=dev)
+    stats = torch.full((Q, 2), float("nan"), device=dev) if with_stats else None
+    dq, dc = torch.zeros_like(tq), torch.zeros_like(tc)
+    L.call("simx_scores_nll_fwd_bwd", L.stream_ptr(), Q, Cn, H, L.ptr(tq), L.ptr(tc), L.ptr(tpos), 1.0, 0, Q, 0, Cn, L.ptr(scores),
+           L.ptr(stats), L.ptr(losses), L.ptr(dq), L.ptr(dc), None, 0)
+    torch.cuda.synchronize()
+    return stats, losses, dq, dc
+
+
+@pytest.mark.parametrize("C", [24, 130])
+def test_inbatch_nll_row_stats(dev, C):
+    """row_stats of the C interface: [2i] the row maximum of the scores (the same GEMM call as dot_product_scores, so the same
+    bits), [2i+1] its logsumexp (against float64 on those scores).  Q = 5: a partial four-row block; C below one lane stride
+    and with a tail after two; positives in the first and the last column.  Passing NULL changes nothing else: the same bits
+    at two rows, and the same gradients at five (the loss scalars are unordered atomic sums beyond two rows)."""
+    from simxns_amd import ops
+    rs = np.random.RandomState(40 + C)
+    q, c = rs.randn(5, 64) * 0.4, rs.randn(C, 64) * 0.4
+    pos = [0, C - 1, C // 3, 64 % C, C // 2]
+    stats, losses, dq, dc = _nll_abi(dev, q, c, pos, True)
+    S = ops.dot_product_scores(_t(q, dev), _t(c, dev))
+    assert torch.equal(stats[:, 0], S.max(1).values)
+    S64 = S.cpu().numpy().astype(np.float64)
+    m = S64.max(1)
+    _close(stats[:, 1].cpu().numpy(), m + np.log(np.exp(S64 - m[:, None]).sum(1)), what="row_stats lse")
+    _, _, dq0, dc0 = _nll_abi(dev, q, c, pos, False)
+    assert torch.equal(dq, dq0) and torch.equal(dc, dc0)
+    a, b = _nll_abi(dev, q[:2], c, pos[:2], True), _nll_abi(dev, q[:2], c, pos[:2], False)
+    assert all(torch.equal(x, y) for x, y in zip(a[1:], b[1:]))
+
+
 # ------------------------------------------------------------------------------------------ sampler
 def test_sampler_bit_exact_vs_oracle_scheme(dev, golden_dir):
     from simxns_amd import ops
