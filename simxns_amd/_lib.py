@@ -15,6 +15,7 @@ SIMX_F32, SIMX_BF16, SIMX_F16, SIMX_F32_SPLIT_H, SIMX_F32_SPLIT_B = 0, 1, 2, 3, 
 EPI_NONE, EPI_GELU, EPI_DGELU = 0, 1, 2
 LOSS_KL, LOSS_WIKI, LOSS_CEKD, LOSS_CE, LOSS_CE_LOGIT, LOSS_CE_DKD, LOSS_CE_PROB = 0, 1, 2, 3, 4, 5, 6
 KD_SOFTMAX, KD_LOGIT, KD_DKD, KD_BI_LOGIT = 0, 1, 2, 3
+SIMX_SQNORM_WS_FLOATS = 2048       # floats of scratch simx_sqnorm_accum_det takes (include/simx.h)
 (P_WORD, P_POS, P_TYPE, P_EMB_LN_G, P_EMB_LN_B, P_WQKV, P_BQKV, P_WO, P_BO, P_LN1_G, P_LN1_B,
  P_W1, P_B1, P_W2, P_B2, P_LN2_G, P_LN2_B, P_POOL_W, P_POOL_B) = range(19)
 

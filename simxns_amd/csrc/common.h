@@ -253,6 +253,23 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false));   // row_bcast31 -> rows 2,3
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+// Sums of a 256-thread block: the four wave totals combined pairwise, (w0 + w1) + (w2 + w3), a fixed order.  s[e] is the block's
+// total in THREAD 0 ONLY afterwards (the other threads keep their wave's).  One call per kernel (the LDS slots are not fenced again).
+template <int N>
+__device__ __forceinline__ void block_sum256(float (&s)[N]) {
+  __shared__ float part[N][4];
+#pragma unroll
+  for (int e = 0; e < N; ++e) s[e] = wave_sum(s[e]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) part[e][threadIdx.x >> 6] = s[e];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) s[e] = (part[e][0] + part[e][1]) + (part[e][2] + part[e][3]);
+  }
+}
 __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, dpp_mov<0xB1, 0xF>(v));
   v = fmaxf(v, dpp_mov<0x4E, 0xF>(v));

@@ -6,46 +6,59 @@
 #include "common.h"
 #include "prof.h"
 
-__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, size_t n, float* __restrict__ out) {
-  __shared__ float part[4];
-  float s = 0.f;
-  const size_t n4 = n / 4;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const float4 v = reinterpret_cast<const float4*>(g)[i];
-    s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+// ---- the pieces every kernel below shares, each stated once ------------------------------------------------------------------
+// gradient multiplier: 1/W of the data-parallel mean times clip_grad_norm_'s min(1, max_norm / (norm + 1e-6)) from the device scalar
+__device__ __forceinline__ float clip_coef(const float* sqnorm, float max_norm, float grad_scale) {
+  float coef = grad_scale;
+  if (sqnorm && max_norm > 0.f) {
+    const float total = sqrtf(*sqnorm) * grad_scale;
+    coef *= fminf(1.0f, max_norm / (total + 1e-6f));
   }
-  if (blockIdx.x == 0) for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) s += g[i] * g[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
+  return coef;
+}
+// the loss scaler (state below; NULL: none) found an overflow: this step leaves parameters and moments alone
+__device__ __forceinline__ bool scaler_skips(const float* scaler) { return scaler && scaler[3] != 0.f; }
+// g[0, n) = 0 over the grid-stride walk of adamw_kernel (float4 i to thread i mod 256 of block i / 256 mod grid, the n % 4 tail
+// elements to block 0): what a step the loss scaler skips still does
+__device__ __forceinline__ void zero_grads(float* __restrict__ g, size_t n) {
+  const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) st4(g + 4 * i, zero);
+  if (blockIdx.x == 0) for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) g[i] = 0.f;
+}
+// 256-thread blocks, one float4 per thread and pass, at most `cap` blocks (the kernels stride over the rest)
+static unsigned grid_for(size_t n, size_t cap) {
+  const size_t blocks = (n / 4 + 255) / 256;
+  return (unsigned)(blocks > cap ? cap : blocks < 1 ? 1 : blocks);
 }
 
-// deterministic variant: pass 1 leaves one partial per block (fixed element -> thread assignment, fixed in-block order), pass 2
-// (one block) adds the partials in index order.  No float atomics: every rank of a data-parallel job gets the SAME bits
-// from the same all-reduced gradients, so the clip coefficient -- and with it the replicas -- cannot drift apart.
-__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, size_t n, float* __restrict__ partials) {
-  __shared__ float part[4];
-  float s = 0.f;
+// Squared L2 norm: ONE body; the block's sum leaves either as a float atomic into `out` or, deterministic variant, as partial
+// blockIdx.x for sqnorm_final_kernel (one block) to add in index order.  No float atomics there: every rank of a data-parallel job
+// gets the SAME bits from the same all-reduced gradients, so the clip coefficient -- and with it the replicas -- cannot drift apart.
+template <bool ATOMIC>
+__device__ __forceinline__ void sqnorm_body(const float* __restrict__ g, size_t n, float* __restrict__ out) {
+  float s[1] = {0.f}, v[4];
   const size_t n4 = n / 4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const float4 v = reinterpret_cast<const float4*>(g)[i];
-    s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    ld4(g + 4 * i, v);
+    s[0] += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
   }
-  if (blockIdx.x == 0) for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) s += g[i] * g[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+  if (blockIdx.x == 0) for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) s[0] += g[i] * g[i];
+  block_sum256(s);
+  if (threadIdx.x != 0) return;
+  if constexpr (ATOMIC) atomicAdd(out, s[0]); else out[blockIdx.x] = s[0];
+}
+__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, size_t n, float* __restrict__ out) {
+  sqnorm_body<true>(g, n, out);
+}
+__global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, size_t n, float* __restrict__ partials) {
+  sqnorm_body<false>(g, n, partials);
 }
 __global__ __launch_bounds__(256) void sqnorm_final_kernel(const float* __restrict__ partials, int nparts, float* __restrict__ out) {
-  __shared__ float part[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nparts; i += 256) s += partials[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out += (part[0] + part[1]) + (part[2] + part[3]);
+  float s[1] = {0.f};
+  for (int i = threadIdx.x; i < nparts; i += 256) s[0] += partials[i];
+  block_sum256(s);
+  if (threadIdx.x == 0) *out += s[0];
 }
 
 // Dynamic loss scaler of the fp16 engine (apex.amp's dynamic loss scaling, which the reference's --fp16 mode runs under:
@@ -76,54 +89,48 @@ __global__ void scaler_update_kernel(float* __restrict__ st, const float* __rest
   st[1] = 1.0f / S;
 }
 
+// m = b1 m + (1 - b1) g and v = b2 v + (1 - b2) g g, the ONE statement for AdamW and LAMB.  Left to contraction the compiler fuses
+// one product in a float4 body and another (or none) in a scalar head or tail, which round differently; spelled out, in the form
+// the float4 bodies have always had, an element gets the same bits wherever it sits in a buffer.
+__device__ __forceinline__ void moments(float& m, float& v, float gg, float beta1, float beta2, float omb1, float omb2) {
+  m = __fmaf_rn(beta1, m, omb1 * gg);
+  v = __fmaf_rn(omb2 * gg, gg, beta2 * v);
+}
+// transformers.AdamW on one element: moments, bias-corrected step, then the decoupled decay of the UPDATED parameter
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float coef, float step_size, float beta1, float beta2,
+                                           float eps, float decay) {
+  const float gg = g * coef;
+  moments(m, v, gg, beta1, beta2, 1.0f - beta1, 1.0f - beta2);
+  p = p - step_size * m / (sqrtf(v) + eps);
+  p = __fmaf_rn(-decay, p, p);
+}
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, size_t n, float step_size, float beta1, float beta2,
                                                     float eps, float decay, const float* __restrict__ sqnorm, float max_norm,
                                                     float grad_scale, int zero_grad, const float* __restrict__ scaler, float lr) {
-  float coef = grad_scale;
-  if (sqnorm && max_norm > 0.f) {
-    const float total = sqrtf(*sqnorm) * grad_scale;
-    coef *= fminf(1.0f, max_norm / (total + 1e-6f));
-  }
+  const float coef = clip_coef(sqnorm, max_norm, grad_scale);
   if (scaler) {
     // the step count that enters the bias correction is the number of steps APPLIED (skipped ones do not age the moments)
     const double t = (double)scaler[4];
     step_size = (float)((double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
-    if (scaler[3] != 0.f) {                        // overflow: parameters and moments keep their values, gradients are dropped
-      if (zero_grad) {
-        const size_t n4z = n / 4;
-        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4z; i += (size_t)gridDim.x * 256)
-          reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (blockIdx.x == 0) for (size_t i = n4z * 4 + threadIdx.x; i < n; i += 256) g[i] = 0.f;
-      }
+    if (scaler_skips(scaler)) {                    // overflow: parameters and moments keep their values, gradients are dropped
+      if (zero_grad) zero_grads(g, n);
       return;
     }
   }
+  const float zero[4] = {0.f, 0.f, 0.f, 0.f};
   const size_t n4 = n / 4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i];
-    float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-    float* pp = &pv.x; float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+    float pv[4], gv[4], mv[4], vv[4];
+    ld4(p + 4 * i, pv); ld4(g + 4 * i, gv); ld4(m + 4 * i, mv); ld4(v + 4 * i, vv);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gp[e] * coef;
-      mp[e] = beta1 * mp[e] + (1.0f - beta1) * gg;
-      vp[e] = beta2 * vp[e] + (1.0f - beta2) * gg * gg;
-      pp[e] = pp[e] - step_size * mp[e] / (sqrtf(vp[e]) + eps);
-      pp[e] = pp[e] - decay * pp[e];
-    }
-    reinterpret_cast<float4*>(p)[i] = pv;
-    reinterpret_cast<float4*>(m)[i] = mv;
-    reinterpret_cast<float4*>(v)[i] = vv;
-    if (zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = 0; e < 4; ++e) adamw_elem(pv[e], gv[e], mv[e], vv[e], coef, step_size, beta1, beta2, eps, decay);
+    st4(p + 4 * i, pv); st4(m + 4 * i, mv); st4(v + 4 * i, vv);
+    if (zero_grad) st4(g + 4 * i, zero);
   }
   if (blockIdx.x == 0)
     for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) {
-      const float gg = g[i] * coef;
-      m[i] = beta1 * m[i] + (1.0f - beta1) * gg;
-      v[i] = beta2 * v[i] + (1.0f - beta2) * gg * gg;
-      float pn = p[i] - step_size * m[i] / (sqrtf(v[i]) + eps);
-      p[i] = pn - decay * pn;
+      adamw_elem(p[i], g[i], m[i], v[i], coef, step_size, beta1, beta2, eps, decay);
       if (zero_grad) g[i] = 0.f;
     }
 }
@@ -132,10 +139,7 @@ extern "C" int simx_sqnorm_accum(simx_stream_t stream, const float* g, size_t n,
   SIMX_PROF(SIMX_K_ADAMW, stream, 4.0 * n);
   SIMX_REQUIRE(g && sqnorm && n > 0, SIMX_ERR_BAD_SHAPE, "sqnorm_accum: bad arguments");
   SIMX_REQUIRE(simx_al16(g), SIMX_ERR_BAD_SHAPE, "sqnorm_accum: g not 16-B aligned");
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sqnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, sqnorm);
+  hipLaunchKernelGGL(sqnorm_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, g, n, sqnorm);
   SIMX_CHECK_LAUNCH("sqnorm");
   return SIMX_OK;
 }
@@ -144,10 +148,8 @@ extern "C" int simx_sqnorm_accum_det(simx_stream_t stream, const float* g, size_
   SIMX_PROF(SIMX_K_ADAMW, stream, 4.0 * n);
   SIMX_REQUIRE(g && sqnorm && ws && n > 0, SIMX_ERR_BAD_SHAPE, "sqnorm_accum_det: bad arguments");
   SIMX_REQUIRE(simx_al16(g), SIMX_ERR_BAD_SHAPE, "sqnorm_accum_det: g not 16-B aligned");
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks > SIMX_SQNORM_WS_FLOATS) blocks = SIMX_SQNORM_WS_FLOATS;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, ws);
+  const unsigned blocks = grid_for(n, SIMX_SQNORM_WS_FLOATS);
+  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, ws);
   SIMX_CHECK_LAUNCH("sqnorm_partial");
   hipLaunchKernelGGL(sqnorm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, (int)blocks, sqnorm);
   SIMX_CHECK_LAUNCH("sqnorm_final");
@@ -213,62 +215,47 @@ __device__ __forceinline__ void lamb_split(const simx_lamb_chunk_t& c, int& head
   body4 = (c.len - head) / 4;
 }
 
+// the head and tail elements of a chunk, one per thread each (head < 4, tail < 4)
+template <typename F>
+__device__ __forceinline__ void lamb_edges(const simx_lamb_chunk_t& c, int head, int body4, F one) {
+  if ((int)threadIdx.x < head) one(threadIdx.x);
+  const int t0 = head + body4 * 4;
+  if (t0 + (int)threadIdx.x < c.len) one(t0 + threadIdx.x);
+}
+
 __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, size_t n, const simx_lamb_chunk_t* __restrict__ chunks,
                                                            const float* __restrict__ seg_wd, int nseg, float* __restrict__ partials,
                                                            float beta1, float beta2, float omb1, float omb2, float eps,
                                                            const float* __restrict__ sqnorm, float max_norm, float grad_scale, const float* __restrict__ scaler) {
-  __shared__ float part[8];
-  if (scaler && scaler[3] != 0.f) return;
+  if (scaler_skips(scaler)) return;
   const simx_lamb_chunk_t c = chunks[blockIdx.x];
   if (!lamb_chunk_ok(c, n, nseg)) return;
-  float coef = grad_scale;
-  if (sqnorm && max_norm > 0.f) {
-    const float total = sqrtf(*sqnorm) * grad_scale;
-    coef *= fminf(1.0f, max_norm / (total + 1e-6f));
-  }
-  const float wd = seg_wd[c.seg];
+  const float coef = clip_coef(sqnorm, max_norm, grad_scale), wd = seg_wd[c.seg];
   int head, body4;
   lamb_split(c, head, body4);
   p += c.off; g += c.off; m += c.off; v += c.off;
-  float sp = 0.f, su = 0.f;
-  auto one = [&](int i) {
-    const float gg = g[i] * coef, pv = p[i];
-    const float mn = beta1 * m[i] + omb1 * gg, vn = beta2 * v[i] + omb2 * gg * gg;
-    m[i] = mn; v[i] = vn;
-    const float u = lamb_u(pv, mn, vn, eps, wd);
-    sp += pv * pv; su += u * u;
+  float s[2] = {0.f, 0.f};                                   // sum p^2, sum u^2 of the chunk
+  auto elem = [&](float pe, float ge, float& me, float& ve) {      // the moments of one element, and its share of the two sums
+    moments(me, ve, ge * coef, beta1, beta2, omb1, omb2);
+    const float u = lamb_u(pe, me, ve, eps, wd);
+    s[0] += pe * pe; s[1] += u * u;
   };
   for (int i = threadIdx.x; i < body4; i += 256) {
-    const float4 pv = reinterpret_cast<const float4*>(p + head)[i], gv = reinterpret_cast<const float4*>(g + head)[i];
-    float4 mv = reinterpret_cast<float4*>(m + head)[i], vv = reinterpret_cast<float4*>(v + head)[i];
-    const float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+    float pv[4], gv[4], mv[4], vv[4];
+    ld4(p + head + 4 * i, pv); ld4(g + head + 4 * i, gv); ld4(m + head + 4 * i, mv); ld4(v + head + 4 * i, vv);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gp[e] * coef;
-      mp[e] = beta1 * mp[e] + omb1 * gg;
-      vp[e] = beta2 * vp[e] + omb2 * gg * gg;
-      const float u = lamb_u(pp[e], mp[e], vp[e], eps, wd);
-      sp += pp[e] * pp[e]; su += u * u;
-    }
-    reinterpret_cast<float4*>(m + head)[i] = mv;
-    reinterpret_cast<float4*>(v + head)[i] = vv;
+    for (int e = 0; e < 4; ++e) elem(pv[e], gv[e], mv[e], vv[e]);
+    st4(m + head + 4 * i, mv); st4(v + head + 4 * i, vv);
   }
-  if ((int)threadIdx.x < head) one(threadIdx.x);
-  const int t0 = head + body4 * 4;
-  if (t0 + (int)threadIdx.x < c.len) one(t0 + threadIdx.x);
-  sp = wave_sum(sp); su = wave_sum(su);
-  if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = sp; part[4 + (threadIdx.x >> 6)] = su; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partials[2 * (size_t)blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
-    partials[2 * (size_t)blockIdx.x + 1] = (part[4] + part[5]) + (part[6] + part[7]);
-  }
+  lamb_edges(c, head, body4, [&](int i) { elem(p[i], g[i], m[i], v[i]); });
+  block_sum256(s);
+  if (threadIdx.x == 0) { partials[2 * (size_t)blockIdx.x] = s[0]; partials[2 * (size_t)blockIdx.x + 1] = s[1]; }
 }
 
 __global__ __launch_bounds__(64) void lamb_ratio_kernel(const float* __restrict__ partials, const int* __restrict__ seg_chunks, int nchunk,
                                                         float* __restrict__ stats, const float* __restrict__ scaler) {
-  if (scaler && scaler[3] != 0.f) return;
+  if (scaler_skips(scaler)) return;
   const int first = seg_chunks[2 * blockIdx.x], count = seg_chunks[2 * blockIdx.x + 1];
   if (first < 0 || count < 1 || first > nchunk - count) return;
   float sp = 0.f, su = 0.f;
@@ -290,31 +277,29 @@ __global__ __launch_bounds__(256) void lamb_update_kernel(float* __restrict__ p,
                                                           float lr, float eps, int zero_grad, const float* __restrict__ scaler) {
   const simx_lamb_chunk_t c = chunks[blockIdx.x];
   if (!lamb_chunk_ok(c, n, nseg)) return;
-  const bool skip = scaler && scaler[3] != 0.f;              // overflow: parameters, moments and stats keep their bits
+  const bool skip = scaler_skips(scaler);                    // overflow: parameters, moments and stats keep their bits
   if (skip && !zero_grad) return;
   int head, body4;
   lamb_split(c, head, body4);
   p += c.off; g += c.off; m += c.off; v += c.off;
   const float wd = seg_wd[c.seg];
   const float ns = skip ? 0.f : -(lr * stats[3 * (size_t)c.seg + 2]);
-  auto one = [&](int i) {
-    if (!skip) p[i] = __fmaf_rn(ns, lamb_u(p[i], m[i], v[i], eps, wd), p[i]);
-    if (zero_grad) g[i] = 0.f;
-  };
+  const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+  auto elem = [&](float& pe, float me, float ve) { pe = __fmaf_rn(ns, lamb_u(pe, me, ve, eps, wd), pe); };
   for (int i = threadIdx.x; i < body4; i += 256) {
     if (!skip) {
-      float4 pv = reinterpret_cast<float4*>(p + head)[i];
-      const float4 mv = reinterpret_cast<const float4*>(m + head)[i], vv = reinterpret_cast<const float4*>(v + head)[i];
-      float* pp = &pv.x; const float* mp = &mv.x; const float* vp = &vv.x;
+      float pv[4], mv[4], vv[4];
+      ld4(p + head + 4 * i, pv); ld4(m + head + 4 * i, mv); ld4(v + head + 4 * i, vv);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) pp[e] = __fmaf_rn(ns, lamb_u(pp[e], mp[e], vp[e], eps, wd), pp[e]);
-      reinterpret_cast<float4*>(p + head)[i] = pv;
+      for (int e = 0; e < 4; ++e) elem(pv[e], mv[e], vv[e]);
+      st4(p + head + 4 * i, pv);
     }
-    if (zero_grad) reinterpret_cast<float4*>(g + head)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (zero_grad) st4(g + head + 4 * i, zero);
   }
-  if ((int)threadIdx.x < head) one(threadIdx.x);
-  const int t0 = head + body4 * 4;
-  if (t0 + (int)threadIdx.x < c.len) one(t0 + threadIdx.x);
+  lamb_edges(c, head, body4, [&](int i) {
+    if (!skip) elem(p[i], m[i], v[i]);
+    if (zero_grad) g[i] = 0.f;
+  });
 }
 
 extern "C" int simx_lamb_chunk(void) { return SIMX_LAMB_CHUNK; }

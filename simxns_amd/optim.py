@@ -6,18 +6,25 @@ host sync) -> AdamW update of every tower with the clip coefficient computed on 
 zeroed in the same pass.  Non-engine parameters (the Reranker's Linear(H,1)) are packed into a small
 extra flat buffer so that one code path serves all.
 """
+import contextlib
+import os
+
 import torch
 
 from . import _lib as L
 from .engine import LossScaler
 
+_NO_DECAY = ("bias", "LayerNorm.weight")
 
-class _NullCtx(object):
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *a):
-        return False
+def _no_decay(name):
+    """The reference's grouping rule (co_training_marco_train.py:59-65): these parameters take no weight decay."""
+    return any(k in name for k in _NO_DECAY)
+
+
+def _saved_state(sd, i):
+    """Entry i of a torch Optimizer state_dict's 'state' (the keys are ints, or strings after a trip through JSON), or None."""
+    return sd["state"].get(i, sd["state"].get(str(i)))
 
 
 def _engines_of(model):
@@ -51,7 +58,6 @@ class FusedAdamW(object):
         # scaler per optimizer too, co_training_marco_train.py:97-104); engines read it in backward, step() updates it
         self.scaler = None
         if any(e.dtype_code == L.SIMX_F16 for m, e in self.towers):
-            import os
             self.scaler = LossScaler(init_scale=float(os.environ.get("SIMX_LOSS_SCALE_INIT", 2.0 ** 16)))
             for m, e in self.towers:
                 if e.dtype_code == L.SIMX_F16:
@@ -68,6 +74,25 @@ class FusedAdamW(object):
         self._reduced = {}                               # id(engine) -> backward serial whose slices were launched
         self._synced = False
         self._comm_log = []
+
+    def _device(self):
+        """Where the flat buffers live: the towers' device, without towers the extra parameters'."""
+        return self.towers[0][1].flat.device if self.towers else self.extra[0].device
+
+    def _on_gpu(self):
+        return bool(self.towers) and self._device().type == "cuda"
+
+    def _join_tower_streams(self, cur):
+        """A tower's backward may have run on a side stream (BiBertEncoder): nothing queued on `cur` reads its buffers before."""
+        for m, e in self.towers:
+            st = getattr(e, "last_stream", None)
+            if st is not None and st != cur:
+                cur.wait_stream(st)
+
+    def _comm_ctx(self):
+        """-> (the communication stream, None on the host; the context that makes it the current stream)"""
+        comm = self._comm if self._on_gpu() else None
+        return comm, (torch.cuda.stream(comm) if comm is not None else contextlib.nullcontext())
 
     # ---- DDP's role: gradient averaging over the ranks (co_training_marco_train.py:107-114) ------------------------
     def enable_overlap(self, world_size, parts=2, process_group=None, payload=None, force=False):
@@ -87,7 +112,6 @@ class FusedAdamW(object):
             # north_star's 1e-3) all-reduce f32 like the reference's DDP (co_training_marco_train.py:107-114); only when EVERY
             # tower computes in 16 bits do the slices cross the links as bf16 (438 MB instead of 876 MB per step and
             # rank; the sum is taken in bf16 by RCCL, the master gradients stay f32).  SIMX_GRAD_PAYLOAD=bf16|fp32 overrides.
-            import os
             all16 = bool(self.towers) and all(getattr(e, "dtype_code", None) in (L.SIMX_BF16, L.SIMX_F16) for _, e in self.towers)
             payload = os.environ.get("SIMX_GRAD_PAYLOAD") or ("bf16" if self.world_size > 1 and all16 else "fp32")
         if payload not in ("fp32", "bf16"):
@@ -95,8 +119,7 @@ class FusedAdamW(object):
         self.payload = payload
         if self.world_size <= 1 and not force:
             return self
-        dev = self.towers[0][1].flat.device if self.towers else None
-        self._comm = torch.cuda.Stream(device=dev) if dev is not None and dev.type == "cuda" else None
+        self._comm = torch.cuda.Stream(device=self._device()) if self._on_gpu() else None
         self._hooks_on = True
         for m, e in self.towers:
             e.grad_ready_hook = self._on_grad_ready
@@ -110,19 +133,17 @@ class FusedAdamW(object):
         self._reduced[id(e)] = e._bwd_serial
         e._reduced_this_step = True                      # a further backward into this buffer before step() raises
         sl = e.flat_grad[lo:hi]
+        ev, ctx = None, contextlib.nullcontext()         # (host tensors: the gloo control-flow tests)
         if e.flat_grad.is_cuda:
             cur = torch.cuda.current_stream()
             comm = self._comm or cur
             comm.wait_stream(cur)                        # the slice is final once the backward kernels queued so far are done
-            with torch.cuda.stream(comm):
-                ev = None
-                if self.profile_comm:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record(comm)
-                buf = sl.to(torch.bfloat16) if self.payload == "bf16" else None
-                w = dist.all_reduce(buf if buf is not None else sl, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        else:                                            # (host tensors: the gloo control-flow tests)
-            ev = None
+            ctx = torch.cuda.stream(comm)
+            if self.profile_comm:
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        with ctx:
+            if ev is not None:
+                ev[0].record(comm)
             buf = sl.to(torch.bfloat16) if self.payload == "bf16" else None
             w = dist.all_reduce(buf if buf is not None else sl, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
         self._pending.append((w, e, lo, hi, buf, ev))
@@ -138,17 +159,12 @@ class FusedAdamW(object):
         if self._synced:
             return 1.0 / W
         import torch.distributed as dist
-        on_gpu = bool(self.towers) and self.towers[0][1].flat.is_cuda
-        cur = torch.cuda.current_stream() if on_gpu else None
-        if on_gpu:
-            for m, e in self.towers:                   # a tower's backward may have run on a side stream (BiBertEncoder):
-                st = getattr(e, "last_stream", None)   # no collective may read its buffer before that stream is done
-                if st is not None and st != cur:
-                    cur.wait_stream(st)
+        cur = torch.cuda.current_stream() if self._on_gpu() else None
+        if cur is not None:
+            self._join_tower_streams(cur)
         launched = set()
-        comm = self._comm if on_gpu else None
         nbytes, evs = 0, []
-        ctx = torch.cuda.stream(comm) if comm is not None else _NullCtx()
+        comm, ctx = self._comm_ctx()
         with ctx:
             for w, e, lo, hi, buf, ev in self._pending:
                 w.wait()                                  # RCCL: the communication stream waits for the collective, not the host
@@ -180,7 +196,7 @@ class FusedAdamW(object):
                 nbytes += g.numel() * (2 if self.payload == "bf16" else 4)
             e._open_graphs = 0
         if self.extra:
-            st = self._extra_state(self.extra[0].device)
+            st = self._extra_state(self._device())
             self._gather_extra(st)
             dist.all_reduce(st["g"], op=dist.ReduceOp.SUM, group=self.group)
             st["g_ready"] = True
@@ -205,14 +221,18 @@ class FusedAdamW(object):
                 "allreduce_ms_on_comm_stream_per_step": round(ar / n, 3), "exposed_wait_ms_per_step": round(ex / n, 3),
                 "overlapped_slices_per_step": sum(k for _, evs, _, k in self._comm_log) / float(n)}
 
-    def _gather_extra(self, st):
+    def _extra_slices(self):
+        """(index, parameter, element offset, elements) of every extra parameter in the packed buffer."""
         o = 0
-        for p in self.extra:
-            n = p.numel()
+        for j, p in enumerate(self.extra):
+            yield j, p, o, p.numel()
+            o += p.numel()
+
+    def _gather_extra(self, st):
+        for j, p, o, n in self._extra_slices():
             st["p"][o:o + n].copy_(p.reshape(-1))
             if p.grad is not None:
                 st["g"][o:o + n].copy_(p.grad.reshape(-1))
-            o += n
 
     def _tower_state(self, e):
         st = self.state.get(id(e))
@@ -238,9 +258,7 @@ class FusedAdamW(object):
         joins it -- nothing may zero a buffer RCCL is still reading or writing -- and the per-step bookkeeping is reset so
         that the next backward may arm its slices again."""
         if self._pending:
-            on_gpu = bool(self.towers) and self.towers[0][1].flat.is_cuda
-            comm = self._comm if on_gpu else None
-            ctx = torch.cuda.stream(comm) if comm is not None else _NullCtx()
+            comm, ctx = self._comm_ctx()
             with ctx:
                 for w, e, lo, hi, buf, ev in self._pending:
                     w.wait()
@@ -279,12 +297,8 @@ class FusedAdamW(object):
         """Everything of a step that is not the update rule: joins the towers' streams, completes the gradient reduction,
         collects the flat buffers, takes the deterministic squared norm and lets the loss scaler judge it.
         -> ([(p, g, state, engine or None)], squared norm, clip?, 1/W, scaler state or None)"""
-        dev = self.towers[0][1].flat.device if self.towers else self.extra[0].device
-        cur = torch.cuda.current_stream()
-        for m, e in self.towers:                       # a tower's backward may have run on a side stream (BiBertEncoder)
-            st = getattr(e, "last_stream", None)
-            if st is not None and st != cur:
-                cur.wait_stream(st)
+        dev = self._device()
+        self._join_tower_streams(torch.cuda.current_stream())
         s = L.stream_ptr()
         grad_scale = self.sync_grads(max(int(world_size), self.world_size))
         self._synced = False
@@ -303,7 +317,7 @@ class FusedAdamW(object):
         sq = torch.zeros(1, dtype=torch.float32, device=dev)
         clip = bool(max_grad_norm and max_grad_norm > 0)
         if clip or self.scaler is not None:       # (the fp16 overflow check is the same norm: inf / nan in any gradient)
-            ws = torch.empty(2048, dtype=torch.float32, device=dev)
+            ws = torch.empty(L.SIMX_SQNORM_WS_FLOATS, dtype=torch.float32, device=dev)
             for p_, g_, st_, e_ in bufs:          # (no float atomics: every data-parallel replica gets the same bits)
                 L.call("simx_sqnorm_accum_det", s, L.ptr(g_), g_.numel(), L.ptr(sq), L.ptr(ws))
         sc = None
@@ -321,42 +335,34 @@ class FusedAdamW(object):
                    L.ptr(sq), max_norm, grad_scale, 1, L.ptr(sc))
             if e_ is not None:
                 e_.mark_weights_dirty()
-        # (on an overflow-skipped fp16 step the decay factor below is 1: the device flag, no host read)
+        # decoupled decay p -= lr*wd*p on everything except 'bias' / 'LayerNorm.weight' (co_training_marco_train.py:59-65; default
+        # weight_decay is 0.0); on an overflow-skipped fp16 step the factor is 1: the device flag, no host read
         keep = None if sc is None else 1.0 - sc[3]
+        f = 1.0 - lr * self.wd * (1.0 if keep is None else keep) if self.wd > 0.0 or self.extra else None
         if self.wd > 0.0:
-            self._decay_towers(lr, keep)
+            self._decay_towers(f)
         if self.extra:
-            nodecay = self._extra_no_decay()
-            f = 1.0 - lr * self.wd if keep is None else 1.0 - lr * self.wd * keep
+            names = {id(p): n for n, p in self.model.named_parameters()}
 
             def decay(p):
-                if self.wd > 0.0 and id(p) not in nodecay:      # same grouping rule as the towers (:59-65)
+                if self.wd > 0.0 and not _no_decay(names[id(p)]):
                     p.mul_(f)
             self._scatter_extra(decay)
 
     def _scatter_extra(self, after=None):
         """The packed extra parameters back into their tensors (`after(p)`: what the update still owes each), gradients zeroed."""
         st = self.state["extra"]
-        o = 0
-        for p in self.extra:
-            n = p.numel()
+        for j, p, o, n in self._extra_slices():
             p.copy_(st["p"][o:o + n].view_as(p))
             if after is not None:
                 after(p)
             if p.grad is not None:
                 p.grad.zero_()
-            o += n
 
-    def _extra_no_decay(self):
-        return {id(p) for n, p in self.model.named_parameters() if any(nd in n for nd in ("bias", "LayerNorm.weight"))}
-
-    def _decay_towers(self, lr, keep=None):
-        # decoupled decay p -= lr*wd*p on everything except 'bias' / 'LayerNorm.weight'
-        # (co_training_marco_train.py:59-65); default weight_decay is 0.0 so this is normally skipped.
-        f = 1.0 - lr * self.wd if keep is None else 1.0 - lr * self.wd * keep
+    def _decay_towers(self, f):
         for m, e in self.towers:
             for name, p in m.named_parameters():
-                if not any(nd in name for nd in ("bias", "LayerNorm.weight")):
+                if not _no_decay(name):
                     p.mul_(f)
             e.mark_weights_dirty()
 
@@ -366,8 +372,7 @@ class FusedAdamW(object):
         then the 'bias' / 'LayerNorm.weight' ones (co_training_marco_train.py:57-65) -- and torch numbers optimizer state by
         position in that concatenation.  -> [(name, param, group)]"""
         named = list(self.model.named_parameters())
-        nd = lambda n: any(k in n for k in ("bias", "LayerNorm.weight"))
-        return [(n, p, 0) for n, p in named if not nd(n)] + [(n, p, 1) for n, p in named if nd(n)]
+        return [(n, p, 0) for n, p in named if not _no_decay(n)] + [(n, p, 1) for n, p in named if _no_decay(n)]
 
     def _moment_views(self):
         """{id(param): (m_view, v_view)} into the flat Adam-state buffers."""
@@ -378,12 +383,9 @@ class FusedAdamW(object):
             for name, p in m.named_parameters():
                 out[id(p)] = (mv[name], vv[name])
         if self.extra:
-            st = self._extra_state(self.extra[0].device)
-            o = 0
-            for p in self.extra:
-                n = p.numel()
+            st = self._extra_state(self._device())
+            for j, p, o, n in self._extra_slices():
                 out[id(p)] = (st["m"][o:o + n].view_as(p), st["v"][o:o + n].view_as(p))
-                o += n
         return out
 
     _group_defaults = {"correct_bias": True}         # what the reference's optimizer class adds to every param group
@@ -430,7 +432,7 @@ class FusedAdamW(object):
                 st["m"].copy_(t["m"])
                 st["v"].copy_(t["v"])
             if "extra" in sd and self.extra:
-                st = self._extra_state(self.extra[0].device)
+                st = self._extra_state(self._device())
                 for k in ("p", "g", "m", "v"):
                     st[k].copy_(sd["extra"][k])
             return
@@ -446,7 +448,7 @@ class FusedAdamW(object):
         steps = set()
         with torch.no_grad():
             for i, (n, p, g) in enumerate(order):
-                st = sd["state"].get(i, sd["state"].get(str(i)))
+                st = _saved_state(sd, i)
                 if st is None:
                     continue
                 if tuple(st["exp_avg"].shape) != tuple(p.shape):
@@ -459,16 +461,14 @@ class FusedAdamW(object):
             raise ValueError("per-parameter step counts differ (%s): the fused update keeps one step count" % sorted(steps))
         self.step_count = steps.pop() if steps else 0
         if self.scaler is not None:
-            dev = self.towers[0][1].flat.device if self.towers else self.extra[0].device
             ls = dict(sd.get("loss_scaler") or {"scale": self.scaler.init_scale})
             ls["applied_steps"] = self.step_count
-            self.scaler.load_state_dict(ls, dev)
+            self.scaler.load_state_dict(ls, self._device())
         g0 = sd["param_groups"][0]
         self.param_groups[0]["lr"] = float(g0.get("lr", self.lr))
         self.base_lr = float(g0.get("initial_lr", self.base_lr))
 
 
-_NO_DECAY = ("bias", "LayerNorm.weight")
 _LAMB_CHUNK_T = [("seg", "<i4"), ("len", "<i4"), ("off", "<i8")]      # simx_lamb_chunk_t (include/simx.h)
 _LAMB_SCALARS = ("weight_norm", "adam_norm", "trust_ratio")
 
@@ -519,7 +519,7 @@ class FusedLamb(FusedAdamW):
         names = {}
         for n, p in self.model.named_parameters():
             names.setdefault(id(p), n)
-        wd = lambda n: 0.0 if any(k in n for k in _NO_DECAY) else self.wd
+        wd = lambda n: 0.0 if _no_decay(n) else self.wd
         out = []
         for b, (m, e) in enumerate(self.towers):
             own = dict(m.named_parameters())
@@ -528,11 +528,9 @@ class FusedLamb(FusedAdamW):
                     continue
                 p = own[key]
                 out.append((names[id(p)], b, int(off), p.numel(), wd(names[id(p)]), p))
-        o = 0
-        for j, p in enumerate(self.extra):
+        for j, p, o, n in self._extra_slices():
             if live_extra is None or live_extra[j]:
-                out.append((names[id(p)], len(self.towers), o, p.numel(), wd(names[id(p)]), p))
-            o += p.numel()
+                out.append((names[id(p)], len(self.towers), o, n, wd(names[id(p)]), p))
         return out
 
     def _plan_for(self, dev):
@@ -621,7 +619,7 @@ class FusedLamb(FusedAdamW):
         self._plan, self._carry = None, {}
         stepping = {id(sg[5]) for sg in self.segments()}       # (an AdamW state has entries for the pooler slots as well)
         for i, (n, p, g) in enumerate(self._ref_param_order()):
-            st = sd["state"].get(i, sd["state"].get(str(i)))
+            st = _saved_state(sd, i)
             if st is not None and id(p) in stepping:
                 self._carry[id(p)] = tuple(float(st[k]) if k in st else nan for k in _LAMB_SCALARS)
 

@@ -33,6 +33,8 @@ def test_library_exports_every_header_symbol():
         assert name in L.SIGNATURES, "ctypes stub has no signature for %s" % name
     assert set(L.SIGNATURES) <= declared
     assert lib.simx_version() >= 100
+    # (the one header constant the ctypes stub restates: FusedAdamW sizes simx_sqnorm_accum_det's scratch by it)
+    assert L.SIMX_SQNORM_WS_FLOATS == int(re.search(r"#define\s+SIMX_SQNORM_WS_FLOATS\s+(\d+)", hdr).group(1))
 
 
 def test_param_layout_matches_bert_base():
