@@ -577,7 +577,14 @@ int simx_assemble_batch(simx_stream_t stream, int B, int D, int QL, int PL, int 
  *                      skip) or, when ids == NULL, implicit ids id_base + column -- into the running result
  *                      run_scores / run_ids [nq,k] (initialise to -inf / -1; k <= 1024).  Also the cross-shard merge.
  * simx_flat_ip_search  = index.search: walks the shard in `chunk`-passage pieces (scores chunk -> top-k update);
- *                      workspace >= simx_flat_ip_workspace_bytes(nq, chunk); ids returned are id_base + row. */
+ *                      workspace >= simx_flat_ip_workspace_bytes(nq, chunk); ids returned are id_base + row.
+ *
+ * float16 storage (faiss useFloat16): q16 / c16 / corpus16 hold IEEE binary16 (the caller rounds, to nearest even; values
+ * beyond the binary16 range are +-inf and score as such -- nothing checks for them).  A score is the float32 sum of the
+ * exact products of the rounded operands, accumulated on the matrix cores in one K loop of fixed order: it depends on
+ * neither chunk nor nq nor the row's position.  H % 8 == 0 and 16-byte aligned pointers (rows are 16-byte aligned).
+ * simx_ip_scores_f16       scores[nq, ld] (first nc columns, float32) = q16[nq,H] . c16[nc,H]^T
+ * simx_flat_ip_search_f16  simx_flat_ip_search over a binary16 shard: same workspace size, top-k, tie order and padding. */
 int simx_ip_scores(simx_stream_t stream, int nq, int nc, int H, const float* q, const float* c, float* scores, long ld);
 int simx_topk_update(simx_stream_t stream, int nq, int m, const float* scores, long ld, const int64_t* ids, long ld_ids,
                      int64_t id_base, int k, float* run_scores, int64_t* run_ids);
@@ -585,6 +592,10 @@ size_t simx_flat_ip_workspace_bytes(int nq, int chunk);
 int simx_flat_ip_search(simx_stream_t stream, int nq, long nc, int H, const float* q, const float* corpus,
                         int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
                         float* out_scores, int64_t* out_ids);
+int simx_ip_scores_f16(simx_stream_t stream, int nq, int nc, int H, const void* q16, const void* c16, float* scores, long ld);
+int simx_flat_ip_search_f16(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
+                            int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
+                            float* out_scores, int64_t* out_ids);
 
 /* -------------------------------------------------------------- SimANS sampler
  * S1+S2 (SimANS/utils/MARCO_until_new.py:174-202, util_wiki.py:609-639, MARCO_until_Doc.py:110-148).

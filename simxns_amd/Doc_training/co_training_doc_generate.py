@@ -37,14 +37,24 @@ def get_new_dataset(args, model, global_step, renew_tools):
     return out
 
 
-def main(argv=None):
+def get_arguments(argv=None):
+    """the train job's flags plus --max_doc_character N and --index_float16 (binary16 index storage, the reference's
+    co.useFloat16; default off)."""
     argv = list(sys.argv[1:] if argv is None else argv)
     max_doc_character = 10000
     if "--max_doc_character" in argv:
         i = argv.index("--max_doc_character")
         max_doc_character = int(argv[i + 1])
         del argv[i:i + 2]
-    args = M.get_arguments(argv)
+    index_float16 = "--index_float16" in argv
+    args = M.get_arguments([a for a in argv if a != "--index_float16"])
+    args.max_doc_character, args.index_float16 = max_doc_character, index_float16
+    return args
+
+
+def main(argv=None):
+    args = get_arguments(argv)
+    max_doc_character = args.max_doc_character
     M.set_env(args)
     if not args.teacher_model_type:
         args.teacher_model_type = args.model_type        # (the generate job has no teacher; load_model wants a config path)
@@ -54,7 +64,7 @@ def main(argv=None):
     model.to(args.device)
     renew_tools = RenewTools(os.path.join(args.passage_path, 'msmarco-docs.tsv'), tokenizer, args.ann_dir,
                              temp_dir=os.path.join(args.ann_dir, 'temp'), max_doc_character=max_doc_character, rank=args.rank,
-                             world=args.world_size)
+                             world=args.world_size, index_float16=args.index_float16)
     if args.world_size > 1:
         dist.barrier()
     out = get_new_dataset(args, model, args.global_step, renew_tools) if args.global_step <= args.max_steps else {}

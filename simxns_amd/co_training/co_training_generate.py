@@ -118,10 +118,12 @@ def write_to_file(qids_to_ranked_candidate_passages, qids_to_ranked_candidate_sc
 class RenewTools(object):
     """The reference's driver object (:269-460) reduced to what the job needs."""
 
-    def __init__(self, passages_path, tokenizer, output_dir, passage_title_path=None, max_passage_length=128, rank=0, world=1):
+    def __init__(self, passages_path, tokenizer, output_dir, passage_title_path=None, max_passage_length=128, rank=0, world=1,
+                 index_float16=False):
         """Reads the corpus file once (ids of every row: the search returns global corpus rows), but TOKENISES only this
-        rank's contiguous slice [rank*n/world, (rank+1)*n/world) -- the only rows this rank embeds."""
-        self.tokenizer, self.output_dir = tokenizer, output_dir
+        rank's contiguous slice [rank*n/world, (rank+1)*n/world) -- the only rows this rank embeds.  ``index_float16``: the
+        reference's (commented-out) ``co.useFloat16 = True``, FlatIPIndex(storage="fp16")."""
+        self.tokenizer, self.output_dir, self.index_float16 = tokenizer, output_dir, bool(index_float16)
         titles = load_id_text(passage_title_path) if passage_title_path and os.path.exists(passage_title_path) else {}
         rows = []
         with open(passages_path) as inp:
@@ -140,7 +142,7 @@ class RenewTools(object):
         if (lo, hi) != self.slice:
             raise ValueError("RenewTools was built for corpus rows %s, build_index asked for %s" % (self.slice, (lo, hi)))
         emb = embed_table(get_model_obj(model).body_emb, self.passage_table, device)
-        index = FlatIPIndex(emb.shape[1] if emb.numel() else 768, id_base=lo)
+        index = FlatIPIndex(emb.shape[1] if emb.numel() else 768, id_base=lo, storage="fp16" if self.index_float16 else "fp32")
         if emb.numel():
             index.add(emb)
         return index
@@ -186,10 +188,10 @@ def load_pos_examples(path, q_type="train", data_dir=None):
     return pos_qp, pos_qp_add
 
 
-def main():
+def get_arguments(argv=None):
     """Flags of the reference's generate jobs (co_training_marco_generate.py:222-252, 327-362): --passage_path is the data
     DIRECTORY (para.txt, para.title.txt, qrels.{train,dev}.tsv inside), the model is output_dir/checkpoint-<global_step>,
-    the mined file goes to --ann_dir."""
+    the mined file goes to --ann_dir.  --index_float16: binary16 index storage (the reference's co.useFloat16, off there too)."""
     ap = argparse.ArgumentParser()
     A = ap.add_argument
     A("--model_type", required=True); A("--model_name_or_path", default=None); A("--output_dir", required=True)
@@ -201,7 +203,12 @@ def main():
     for ignored in ("--max_seq_length", "--max_steps", "--adv_step", "--iteration_step", "--iteration_reranker_step"):
         A(ignored, type=int, default=0)
     A("--log_dir", default=None); A("--gradient_checkpointing", action="store_true")
-    args = ap.parse_args()
+    A("--index_float16", action="store_true")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = get_arguments()
     logging.basicConfig(level=logging.INFO)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", max(args.local_rank, 0)))
@@ -225,7 +232,8 @@ def main():
         from transformers import BertTokenizer
         tok = BertTokenizer.from_pretrained(args.tokenizer_name or "bert-base-uncased", do_lower_case=True)
     data_dir = args.passage_path
-    tools = RenewTools(os.path.join(data_dir, "para.txt"), tok, ann_dir, os.path.join(data_dir, "para.title.txt"), rank=rank, world=world)
+    tools = RenewTools(os.path.join(data_dir, "para.txt"), tok, ann_dir, os.path.join(data_dir, "para.title.txt"), rank=rank, world=world,
+                       index_float16=args.index_float16)
     index = tools.build_index(model, device, rank, world)
     for mode, qa in (("train", args.train_qa_path), ("dev", args.dev_qa_path)):
         if qa:

@@ -5,6 +5,12 @@
 //                      (bit-reproducible: oracle/topk_ref.c restates exactly this), 128x128x16 register-tiled
 //                      VALU kernel (the f32 MFMA has the same peak as packed f32 FMA on gfx950 and no defined
 //                      accumulation order).  Bound: f32 FMA, 2*nq*nc*H FLOP.
+//   ip_scores_f16_kernel  the same contraction for the float16 storage mode (faiss useFloat16): both operands binary16, products
+//                      exact in float32, float32 accumulation by v_mfma_f32_16x16x32_f16 in ONE K loop of fixed order per
+//                      score (no split-K, no atomics), so a score depends on neither the chunk, the query block nor the
+//                      position of its row in a tile.  128x128x64 tiles, LDS-DMA staging into the swizzled image of the
+//                      NT GEMMs, K tail zero-filled in LDS.  Bounds: 16-bit MFMA rate and, for a whole search, the 8 B
+//                      of HBM traffic per score of the write-then-top-k design.
 //   topk_stream_kernel per query: streaming exact top-k over [running best (k) U new candidates] with 64-bit
 //                      composite keys (orderable score << 32 | ~id): candidates below the running k-th key are
 //                      dropped while scanning, survivors are collected in LDS and folded in by a bitonic sort of
@@ -12,6 +18,7 @@
 //                      score row once (4 B per candidate).
 #include <math.h>
 #include "common.h"
+#include "p3.h"
 #include "prof.h"
 
 #define IP_BM 128
@@ -69,6 +76,112 @@ __global__ __launch_bounds__(256) void ip_scores_kernel(int nq, int nc, int H, c
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (n + j < nc) dst[j] = acc[i][jh * 4 + j];
+      }
+    }
+  }
+}
+
+// ---- float16 storage: scores on the matrix cores ----------------------------------------------------------------------
+#define IPH_BM 128
+#define IPH_BN 128
+#define IPH_BK 64
+#define IPH_TILE (128 * 64 * 2)            // one operand tile; a stage = Q tile + C tile
+
+// stage rows [row0, row0 + 128) x k [k0, k0 + 64) of G [nrows, H] (binary16, K contiguous).  LDS image as in the NT GEMMs:
+// row r at r * 128 B, the 16-B chunk c of the row at chunk position c ^ ((r >> 1) & 7).  Rows past the end re-read the last
+// row (their scores are never stored).  A full stage goes by LDS-DMA; the ragged last stage (H % 64 != 0; H % 8 == 0, so a
+// chunk is inside the row or wholly outside it) through registers, with zeros for the chunks at k >= H: no byte past a row
+// is ever read.
+__device__ __forceinline__ void iph_stage_tile(const f16_t* __restrict__ G, int H, int row0, int nrows, int k0, char* tile,
+                                               int wave, int lane) {
+  const bool full = k0 + IPH_BK <= H;          // uniform
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = wave * 4 + j;                // wave-instruction index: 8 rows each
+    const int r = i * 8 + (lane >> 3);
+    const int c = (lane & 7) ^ ((r >> 1) & 7);
+    int gr = row0 + r;
+    gr = gr < nrows ? gr : nrows - 1;
+    const f16_t* src = G + (long)gr * H + k0 + c * 8;
+    if (full) {
+      glds16(src, tile + i * 1024);
+    } else {
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (k0 + c * 8 < H) v = *reinterpret_cast<const uint4*>(src);
+      *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
+                                                               const f16_t* __restrict__ Cp, float* __restrict__ S, long ldS,
+                                                               int tiles_m, int nwg) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // queries fastest: the workgroups of one XCD walk all query tiles of a few corpus tiles, so a corpus row leaves HBM once
+  const int tile = xcd_remap(blockIdx.x, nwg);
+  const int m0 = (tile % tiles_m) * IPH_BM, n0 = (tile / tiles_m) * IPH_BN;
+  const int wr = wave >> 1, wc = wave & 1;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int nt = (H + IPH_BK - 1) / IPH_BK;
+  iph_stage_tile(Q, H, m0, nq, 0, smem, wave, lane);
+  iph_stage_tile(Cp, H, n0, nc, 0, smem + IPH_TILE, wave, lane);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  const int fr = lane & 15, fg = lane >> 4;
+  int cur = 0;
+  for (int t = 0; t < nt; ++t) {
+    char* sa = smem + cur * 2 * IPH_TILE;
+    char* sb = sa + IPH_TILE;
+    if (t + 1 < nt) {
+      char* na = smem + (cur ^ 1) * 2 * IPH_TILE;
+      iph_stage_tile(Q, H, m0, nq, (t + 1) * IPH_BK, na, wave, lane);
+      iph_stage_tile(Cp, H, n0, nc, (t + 1) * IPH_BK, na + IPH_TILE, wave, lane);
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {           // ascending k: the one accumulation order of a score
+      bf16x8 af[4], bfr[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int ra = wr * 64 + i * 16 + fr;
+        af[i] = *reinterpret_cast<const bf16x8*>(sa + ra * 128 + (((ks * 4 + fg) ^ ((ra >> 1) & 7)) << 4));
+        const int rb = wc * 64 + i * 16 + fr;
+        bfr[i] = *reinterpret_cast<const bf16x8*>(sb + rb * 128 + (((ks * 4 + fg) ^ ((rb >> 1) & 7)) << 4));
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = H16<f16_t>::mfma(bfr[j], af[i], acc[i][j]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // lane holds query m = .. + fr, passages n = .. + fg * 4 .. + 3 of each 16 x 16 tile
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + wr * 64 + i * 16 + fr;
+    if (m >= nq) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = n0 + wc * 64 + j * 16 + fg * 4;
+      float* dst = S + (long)m * ldS + n;
+      if (n + 4 <= nc && (ldS & 3) == 0) {
+        *reinterpret_cast<float4*>(dst) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (n + e < nc) dst[e] = acc[i][j][e];
       }
     }
   }
@@ -162,6 +275,20 @@ extern "C" int simx_ip_scores(simx_stream_t stream, int nq, int nc, int H, const
   return SIMX_OK;
 }
 
+extern "C" int simx_ip_scores_f16(simx_stream_t stream, int nq, int nc, int H, const void* q16, const void* c16, float* scores, long ld) {
+  hipStream_t s = (hipStream_t)stream;
+  SIMX_PROF(SIMX_K_TOPK, s, 2.0 * nq * nc * H);
+  SIMX_REQUIRE(nq > 0 && nc > 0 && H > 0 && H % 8 == 0 && ld >= nc, SIMX_ERR_BAD_SHAPE, "ip_scores_f16: bad shape nq=%d nc=%d H=%d ld=%ld", nq, nc, H, ld);
+  SIMX_REQUIRE(q16 && c16 && scores && simx_al16(q16) && simx_al16(c16) && simx_al16(scores), SIMX_ERR_BAD_SHAPE,
+               "ip_scores_f16: pointers must be non-NULL and 16-byte aligned");
+  const int tiles_m = cdiv(nq, IPH_BM), tiles_n = cdiv(nc, IPH_BN);
+  SIMX_REQUIRE((long)tiles_m * tiles_n <= 0x7FFFFFFFl, SIMX_ERR_BAD_SHAPE, "ip_scores_f16: too many tiles (nq=%d nc=%d)", nq, nc);
+  const int nwg = tiles_m * tiles_n;
+  hipLaunchKernelGGL(ip_scores_f16_kernel, dim3(nwg), dim3(256), 0, s, nq, nc, H, (const f16_t*)q16, (const f16_t*)c16, scores, ld, tiles_m, nwg);
+  SIMX_CHECK_LAUNCH("ip_scores_f16");
+  return SIMX_OK;
+}
+
 extern "C" int simx_topk_update(simx_stream_t stream, int nq, int m, const float* scores, long ld, const int64_t* ids, long ld_ids,
                                 int64_t id_base, int k, float* run_scores, int64_t* run_ids) {
   hipStream_t s = (hipStream_t)stream;
@@ -181,21 +308,35 @@ __global__ void topk_init_kernel(long n, float* s, long long* i) {
 
 extern "C" size_t simx_flat_ip_workspace_bytes(int nq, int chunk) { return (size_t)nq * (size_t)((chunk + 3) & ~3) * sizeof(float); }
 
-extern "C" int simx_flat_ip_search(simx_stream_t stream, int nq, long nc, int H, const float* q, const float* corpus,
-                                   int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
-                                   float* out_scores, int64_t* out_ids) {
+// index.search over a float32 (f16 == false) or binary16 shard: the chunk walk is the same, the score kernel differs
+static int flat_ip_search(const char* what, bool f16, simx_stream_t stream, int nq, long nc, int H, const void* q, const void* corpus,
+                          int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_ids) {
   hipStream_t s = (hipStream_t)stream;
-  SIMX_REQUIRE(nq > 0 && nc >= 0 && chunk > 0, SIMX_ERR_BAD_SHAPE, "flat_ip_search: bad shape");
-  SIMX_REQUIRE(workspace_bytes >= simx_flat_ip_workspace_bytes(nq, chunk), SIMX_ERR_WORKSPACE, "flat_ip_search: workspace too small");
+  SIMX_REQUIRE(nq > 0 && nc >= 0 && chunk > 0, SIMX_ERR_BAD_SHAPE, "%s: bad shape", what);
+  SIMX_REQUIRE(workspace_bytes >= simx_flat_ip_workspace_bytes(nq, chunk), SIMX_ERR_WORKSPACE, "%s: workspace too small", what);
   const long ld = (chunk + 3) & ~3;
   hipLaunchKernelGGL(topk_init_kernel, dim3(cdiv((int)((long)nq * k), 256)), dim3(256), 0, s, (long)nq * k, out_scores, (long long*)out_ids);
   SIMX_CHECK_LAUNCH("topk_init");
   for (long c0 = 0; c0 < nc; c0 += chunk) {
     const int m = (int)((nc - c0) < chunk ? (nc - c0) : chunk);
-    int rc = simx_ip_scores(stream, nq, m, H, q, corpus + c0 * H, (float*)workspace, ld);
+    int rc = f16 ? simx_ip_scores_f16(stream, nq, m, H, q, (const f16_t*)corpus + c0 * H, (float*)workspace, ld)
+                 : simx_ip_scores(stream, nq, m, H, (const float*)q, (const float*)corpus + c0 * H, (float*)workspace, ld);
     if (rc) return rc;
     rc = simx_topk_update(stream, nq, m, (const float*)workspace, ld, nullptr, 0, id_base + c0, k, out_scores, out_ids);
     if (rc) return rc;
   }
   return SIMX_OK;
+}
+
+extern "C" int simx_flat_ip_search(simx_stream_t stream, int nq, long nc, int H, const float* q, const float* corpus,
+                                   int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
+                                   float* out_scores, int64_t* out_ids) {
+  return flat_ip_search("flat_ip_search", false, stream, nq, nc, H, q, corpus, id_base, k, chunk, workspace, workspace_bytes, out_scores, out_ids);
+}
+
+extern "C" int simx_flat_ip_search_f16(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
+                                       int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
+                                       float* out_scores, int64_t* out_ids) {
+  return flat_ip_search("flat_ip_search_f16", true, stream, nq, nc, H, q16, corpus16, id_base, k, chunk, workspace, workspace_bytes, out_scores,
+                        out_ids);
 }

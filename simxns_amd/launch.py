@@ -104,6 +104,9 @@ def main(argv=None):
                          "32).  The recipes split the step for 32-40 GB GPUs; their losses are per-query (no in-batch negatives), so the "
                          "summed gradient is the same up to rounding and dropout draws, and 65536 passage tokens fill the 256 CUs in "
                          "whole waves of GEMM tiles where 32768 leave the last wave half empty.  Off by default: the recipe to the letter")
+    ap.add_argument("--index_float16", "--index-float16", dest="index_float16", action="store_true",
+                    help="pass --index_float16 to the generate jobs: binary16 index storage scored on the matrix cores (the reference's "
+                         "co.useFloat16, which its NQ / TQ generate job sets).  Off by default in every recipe")
     args, extra = ap.parse_known_args(argv)
     extra = [e for e in extra if e != "--"]
     r = RECIPES[args.recipe]()
@@ -120,7 +123,8 @@ def main(argv=None):
         jobs = [job_argv(script, dict(flags, global_step=global_step, **loop), args.nproc, args.port) + extra]
         if r["generate"] is not None:
             script, flags = r["generate"]
-            jobs.append(job_argv(script, dict(flags, global_step=global_step + step, **loop), args.nproc, args.port))
+            jobs.append(job_argv(script, dict(flags, global_step=global_step + step, index_float16=args.index_float16, **loop),
+                                 args.nproc, args.port))
         elif os.environ.get("SIMX_GENERATE_CMD"):
             jobs.append(os.environ["SIMX_GENERATE_CMD"].split() + ["--global_step=%d" % (global_step + step)])
         for j in jobs:

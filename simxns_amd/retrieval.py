@@ -4,7 +4,11 @@ in the reference's generate job (SimANS/co_training/co_training_generate.py:359-
 One process per GPU holds a contiguous shard of the corpus embeddings in HBM (8.8 M x 768 f32 = 27 GB: the whole
 MS-MARCO corpus fits one 288 GB GPU; with W ranks each holds 1/W).  search() = local top-k by the HIP kernels, then --
 when a process group is given -- an all_gather of the W x [nq,k] candidates over RCCL and the same top-k kernel as the
-merge.  No CPU path: without the HIP library every call raises."""
+merge.  No CPU path: without the HIP library every call raises.
+
+storage="fp16" is faiss's ``useFloat16``: rows and queries are rounded to IEEE binary16 (round to nearest even; values
+beyond the binary16 range become +-inf, as in FAISS, and nothing checks for them), the shard takes 2 B per element and the
+scores are accumulated in float32 on the matrix cores (ip_scores_f16_kernel)."""
 import ctypes as C
 
 import torch
@@ -15,12 +19,20 @@ from . import _lib as L
 class FlatIPIndex(object):
     """index = FlatIPIndex(dim); index.add(emb); D, I = index.search(q, k)   (faiss.IndexFlatIP surface)."""
 
-    def __init__(self, dim, id_base=0, chunk=65536, query_block=8192):
+    def __init__(self, dim, id_base=0, chunk=65536, query_block=8192, storage="fp32"):
         """``chunk``: corpus rows scored per pass; ``query_block``: queries per pass -- the score workspace is
         query_block x chunk x 4 B (2 GB by default) whatever the number of queries (the 503 k MS-MARCO train queries in one
-        call would otherwise ask for 132 GB)."""
+        call would otherwise ask for 132 GB).  ``storage``: "fp32" (the default: float32 rows, one fmaf chain per score) or
+        "fp16" (binary16 rows and queries, float32 scores from the matrix cores; needs dim % 8 == 0)."""
+        if storage not in ("fp32", "fp16"):
+            raise ValueError("FlatIPIndex: storage must be 'fp32' or 'fp16', not %r" % (storage,))
+        if storage == "fp16" and dim % 8 != 0:
+            raise ValueError("FlatIPIndex: storage='fp16' needs an embedding size that is a multiple of 8, not %d" % dim)
         assert dim % 4 == 0, "embedding size must be a multiple of 4"
         self.d, self.id_base, self.chunk, self.query_block = int(dim), int(id_base), int(chunk), int(query_block)
+        self.storage = storage
+        self._dtype = torch.float16 if storage == "fp16" else torch.float32
+        self._search = "simx_flat_ip_search_f16" if storage == "fp16" else "simx_flat_ip_search"
         self._parts, self._emb = [], None
 
     @property
@@ -32,7 +44,7 @@ class FlatIPIndex(object):
         if not emb.is_cuda:
             raise L.SimxError("FlatIPIndex.add: embeddings must live on the GPU (there is no CPU path)")
         assert emb.dim() == 2 and emb.shape[1] == self.d
-        self._parts.append(emb.detach().to(torch.float32).contiguous())
+        self._parts.append(emb.detach().to(self._dtype).contiguous())
 
     def _corpus(self):
         if self._parts:
@@ -46,7 +58,7 @@ class FlatIPIndex(object):
         q = torch.as_tensor(q)
         if not q.is_cuda:
             raise L.SimxError("FlatIPIndex.search: queries must live on the GPU (there is no CPU path)")
-        q = q.detach().to(torch.float32).contiguous()
+        q = q.detach().to(self._dtype).contiguous()
         nq = q.shape[0]
         corpus = self._corpus()
         nc = 0 if corpus is None else corpus.shape[0]
@@ -58,7 +70,7 @@ class FlatIPIndex(object):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
         for lo in range(0, nq, qb):                     # query blocks reuse ONE workspace
             n = min(qb, nq - lo)
-            L.call("simx_flat_ip_search", L.stream_ptr(), n, nc, self.d, L.ptr(q[lo:lo + n]), L.ptr(corpus) if nc else None,
+            L.call(self._search, L.stream_ptr(), n, nc, self.d, L.ptr(q[lo:lo + n]), L.ptr(corpus) if nc else None,
                    self.id_base, k, chunk, L.ptr(ws), ws_bytes, L.ptr(D[lo:lo + n]), L.ptr(I[lo:lo + n]))
         if group is None:
             return D, I

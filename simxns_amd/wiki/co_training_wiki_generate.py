@@ -50,15 +50,24 @@ def get_new_dataset(args, model, global_step, renew_tools):
         renew_tools.get_question_topk(q, a, emb, gold, index, mode=mode, step_num=global_step, group=group)
 
 
+def get_arguments(argv=None):
+    """the train job's flags plus --index_float16 (binary16 index storage, the reference's co.useFloat16; default off)."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    index_float16 = "--index_float16" in argv
+    args = M.get_arguments([a for a in argv if a != "--index_float16"])
+    args.index_float16 = index_float16
+    return args
+
+
 def main(argv=None):
-    args = M.get_arguments(argv)
+    args = get_arguments(argv)
     M.set_env(args)
     if args.output_dir and is_first_worker():
         os.makedirs(args.output_dir, exist_ok=True)
     tokenizer, model = load_model(args)
     renew_tools = RenewTools(passages_path=args.passage_path, tokenizer=tokenizer, output_dir=args.ann_dir,
                              temp_dir=os.path.join(args.ann_dir, 'temp'), max_seq_length=args.max_seq_length, rank=args.rank,
-                             world=args.world_size)
+                             world=args.world_size, index_float16=args.index_float16)
     if args.world_size > 1:
         dist.barrier()
     if args.global_step <= args.max_steps:
