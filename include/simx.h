@@ -584,7 +584,33 @@ int simx_assemble_batch(simx_stream_t stream, int B, int D, int QL, int PL, int 
  * exact products of the rounded operands, accumulated on the matrix cores in one K loop of fixed order: it depends on
  * neither chunk nor nq nor the row's position.  H % 8 == 0 and 16-byte aligned pointers (rows are 16-byte aligned).
  * simx_ip_scores_f16       scores[nq, ld] (first nc columns, float32) = q16[nq,H] . c16[nc,H]^T
- * simx_flat_ip_search_f16  simx_flat_ip_search over a binary16 shard: same workspace size, top-k, tie order and padding. */
+ * simx_flat_ip_search_f16  simx_flat_ip_search over a binary16 shard: same workspace size, top-k, tie order and padding.
+ *
+ * One-pass float16 search (opt-in; the entry points above are unchanged): the score tile is compared with each query's running
+ * k-th entry while still in the accumulators, and only the survivors reach HBM, as a short per-query candidate list that is then
+ * folded into the running top-k.  Scores have the bits of simx_ip_scores_f16 and the top-k is exact, so the result equals
+ * simx_flat_ip_search_f16's bit for bit unless a list overflowed, which is reported.
+ * simx_ip_filter_f16       the kernel alone.  For query q the threshold is the running set's last entry, run_scores / run_ids
+ *                          [q*k + k-1] (run_ids < 0: the set is not full, every score survives).  A score of column j survives if
+ *                          !(score <= threshold) -- NaN survives, a tie does not -- and is appended to the list of q:
+ *                          slot = cand_count[q]++ (atomic); if slot < cand_cap, cand_scores[q*cand_cap + slot] = score and
+ *                          cand_ids[q*cand_cap + slot] = id0 + j, else nothing is written: cand_count keeps the true number.
+ *                          List order is not defined.  The caller zeroes cand_count.  PRECONDITION: id0 is larger than every id
+ *                          in the running set (the rows of a later chunk of the same shard); a row that ties the k-th score then
+ *                          loses on the id rule and dropping it is exact.  The filter may pass a score the fold rejects, never
+ *                          the reverse.  Shapes and alignment as simx_ip_scores_f16; 0 < k <= 1024; id0 + nc < 2^32.
+ * simx_topk_fold_lists     folds those lists into run_scores / run_ids [nq,k] (the top-k kernel of simx_topk_update, its sort sized
+ *                          to k + the list length): query q contributes its first min(cand_count[q], cand_cap) entries; a count
+ *                          above cand_cap adds 1 to *overflow (device memory, accumulated); every cand_count is reset to 0.
+ * simx_flat_ip_search_f16_fused  = simx_flat_ip_search_f16 in one pass.  The first min(seed_rows, nc) rows take the unfused
+ *                          pass (an empty running set filters nothing); each later chunk takes min(chunk, rows seen so far,
+ *                          rows left) rows through filter + fold, so on rows in random order a query lists about k survivors
+ *                          per chunk or fewer.  workspace >= simx_flat_ip_fused_workspace_bytes(nq, seed_rows, cand_cap): the
+ *                          seed score block, the two candidate arrays, the counts and an overflow word; 16-byte aligned.
+ *                          Asynchronous on the stream.  *overflow (device memory) is written, not accumulated: non-zero = the
+ *                          number of (query, chunk) lists that exceeded cand_cap, and out_scores / out_ids of THIS call are not
+ *                          to be used (search again with simx_flat_ip_search_f16 or a larger cand_cap).  Neither chunk, seed_rows
+ *                          nor cand_cap changes a result bit. */
 int simx_ip_scores(simx_stream_t stream, int nq, int nc, int H, const float* q, const float* c, float* scores, long ld);
 int simx_topk_update(simx_stream_t stream, int nq, int m, const float* scores, long ld, const int64_t* ids, long ld_ids,
                      int64_t id_base, int k, float* run_scores, int64_t* run_ids);
@@ -596,6 +622,15 @@ int simx_ip_scores_f16(simx_stream_t stream, int nq, int nc, int H, const void* 
 int simx_flat_ip_search_f16(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
                             int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
                             float* out_scores, int64_t* out_ids);
+size_t simx_flat_ip_fused_workspace_bytes(int nq, int seed_rows, int cand_cap);
+int simx_ip_filter_f16(simx_stream_t stream, int nq, int nc, int H, const void* q16, const void* c16, int64_t id0, int k,
+                       const float* run_scores, const int64_t* run_ids, float* cand_scores, int64_t* cand_ids, int cand_cap,
+                       int* cand_count);
+int simx_topk_fold_lists(simx_stream_t stream, int nq, const float* cand_scores, const int64_t* cand_ids, int cand_cap,
+                         int* cand_count, int k, float* run_scores, int64_t* run_ids, int* overflow);
+int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
+                                  int64_t id_base, int k, int chunk, int seed_rows, int cand_cap, void* workspace,
+                                  size_t workspace_bytes, float* out_scores, int64_t* out_ids, int* overflow);
 
 /* -------------------------------------------------------------- SimANS sampler
  * S1+S2 (SimANS/utils/MARCO_until_new.py:174-202, util_wiki.py:609-639, MARCO_until_Doc.py:110-148).

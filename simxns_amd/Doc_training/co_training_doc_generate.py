@@ -39,16 +39,18 @@ def get_new_dataset(args, model, global_step, renew_tools):
 
 def get_arguments(argv=None):
     """the train job's flags plus --max_doc_character N and --index_float16 (binary16 index storage, the reference's
-    co.useFloat16; default off)."""
+    co.useFloat16; default off) and, with it, --index_fused (its one-pass search; experimental, default off)."""
     argv = list(sys.argv[1:] if argv is None else argv)
     max_doc_character = 10000
     if "--max_doc_character" in argv:
         i = argv.index("--max_doc_character")
         max_doc_character = int(argv[i + 1])
         del argv[i:i + 2]
-    index_float16 = "--index_float16" in argv
-    args = M.get_arguments([a for a in argv if a != "--index_float16"])
-    args.max_doc_character, args.index_float16 = max_doc_character, index_float16
+    index_float16, index_fused = "--index_float16" in argv, "--index_fused" in argv
+    if index_fused and not index_float16:
+        raise SystemExit("--index_fused needs --index_float16: the one-pass search exists for the binary16 index only")
+    args = M.get_arguments([a for a in argv if a not in ("--index_float16", "--index_fused")])
+    args.max_doc_character, args.index_float16, args.index_fused = max_doc_character, index_float16, index_fused
     return args
 
 
@@ -64,7 +66,8 @@ def main(argv=None):
     model.to(args.device)
     renew_tools = RenewTools(os.path.join(args.passage_path, 'msmarco-docs.tsv'), tokenizer, args.ann_dir,
                              temp_dir=os.path.join(args.ann_dir, 'temp'), max_doc_character=max_doc_character, rank=args.rank,
-                             world=args.world_size, index_float16=args.index_float16)
+                             world=args.world_size, index_float16=args.index_float16,
+                             index_fused=args.index_fused)
     if args.world_size > 1:
         dist.barrier()
     out = get_new_dataset(args, model, args.global_step, renew_tools) if args.global_step <= args.max_steps else {}

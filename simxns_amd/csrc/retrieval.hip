@@ -11,11 +11,26 @@
 //                      position of its row in a tile.  128x128x64 tiles, LDS-DMA staging into the swizzled image of the
 //                      NT GEMMs, K tail zero-filled in LDS.  Bounds: 16-bit MFMA rate and, for a whole search, the 8 B
 //                      of HBM traffic per score of the write-then-top-k design.
+//   ip_filter_f16_kernel  the same main loop (iph_main_loop: ONE copy, so a score has the same bits in both kernels) with a
+//                      filter epilogue instead of the store: each score is compared, still in the accumulators, with the running
+//                      k-th entry of its query (run_scores / run_ids [q*k + k-1]; id < 0 = the set is not full and everything
+//                      survives); it survives if !(score <= thr), which keeps NaN and is strict on ties.  A survivor takes a slot
+//                      with a device-scope atomicAdd on cand_count[q] and, if slot < cand_cap, writes (score, id0 + column) to the
+//                      query's candidate list; the count keeps the true number, so an overflow is visible.
+//                      PRECONDITION of the strict test: every row scored here has a LARGER id than every entry of the running set
+//                      (inside one search over one shard: the rows of a later chunk).  A row that ties the k-th score then loses
+//                      on the id rule (ties: ascending id) exactly as in topk_stream_kernel.  The filter may pass a score the fold
+//                      rejects; it never drops one whose key exceeds the running k-th key (a threshold of -0.0 is lowered to
+//                      -FLT_MIN, since +0.0 <= -0.0 but key(+0.0) > key(-0.0)).
 //   topk_stream_kernel per query: streaming exact top-k over [running best (k) U new candidates] with 64-bit
 //                      composite keys (orderable score << 32 | ~id): candidates below the running k-th key are
 //                      dropped while scanning, survivors are collected in LDS and folded in by a bitonic sort of
 //                      4096 keys whenever the buffer could overflow.  Ties: lower id first.  HBM-bound: reads the
-//                      score row once (4 B per candidate).
+//                      score row once (4 B per candidate).  With a per-query count (the fold of ip_filter_f16_kernel's
+//                      lists) the rows of query q are its first min(cand_count[q], cand_cap) list entries, the sort is sized
+//                      to the next power of two >= k + that number, a count above cand_cap adds 1 to the overflow word and
+//                      the count is reset to 0 for the next chunk.
+#include <float.h>
 #include <math.h>
 #include "common.h"
 #include "p3.h"
@@ -113,19 +128,11 @@ __device__ __forceinline__ void iph_stage_tile(const f16_t* __restrict__ G, int 
   }
 }
 
-__global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
-                                                               const f16_t* __restrict__ Cp, float* __restrict__ S, long ldS,
-                                                               int tiles_m, int nwg) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // queries fastest: the workgroups of one XCD walk all query tiles of a few corpus tiles, so a corpus row leaves HBM once
-  const int tile = xcd_remap(blockIdx.x, nwg);
-  const int m0 = (tile % tiles_m) * IPH_BM, n0 = (tile / tiles_m) * IPH_BN;
+// the ONE main loop of the binary16 score kernels: acc[i][j] = the 16 x 16 tiles (query rows wr * 64 + i * 16 .., passages
+// wc * 64 + j * 16 ..) of the 128 x 128 tile at (m0, n0), accumulated over all of H in ascending k
+__device__ __forceinline__ void iph_main_loop(int nq, int nc, int H, const f16_t* Q, const f16_t* Cp, int m0,
+                                              int n0, char* smem, int wave, int lane, f32x4 (&acc)[4][4]) {
   const int wr = wave >> 1, wc = wave & 1;
-
-  f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -166,7 +173,24 @@ __global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, i
     __syncthreads();
     cur ^= 1;
   }
+}
 
+__global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
+                                                               const f16_t* __restrict__ Cp, float* __restrict__ S, long ldS,
+                                                               int tiles_m, int nwg) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // queries fastest: the workgroups of one XCD walk all query tiles of a few corpus tiles, so a corpus row leaves HBM once
+  const int tile = xcd_remap(blockIdx.x, nwg);
+  const int m0 = (tile % tiles_m) * IPH_BM, n0 = (tile / tiles_m) * IPH_BN;
+  const int wr = wave >> 1, wc = wave & 1;
+
+  f32x4 acc[4][4];
+  iph_main_loop(nq, nc, H, Q, Cp, m0, n0, smem, wave, lane, acc);
+
+  const int fr = lane & 15, fg = lane >> 4;
   // lane holds query m = .. + fr, passages n = .. + fg * 4 .. + 3 of each 16 x 16 tile
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -182,6 +206,70 @@ __global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, i
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           if (n + e < nc) dst[e] = acc[i][j][e];
+      }
+    }
+  }
+}
+
+// filter epilogue (see the header of this file for the rule and its precondition).  Survivors are rare once the running set is
+// warm -- about k * nc / rows_seen per query and chunk -- so a 16 x 16 tile is first tested with one wave-wide ballot.
+__global__ __launch_bounds__(256, 2) void ip_filter_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
+                                                               const f16_t* __restrict__ Cp, long long id0, int k,
+                                                               const float* __restrict__ run_s, const long long* __restrict__ run_i,
+                                                               float* __restrict__ cand_s, long long* __restrict__ cand_i, int cand_cap,
+                                                               int* __restrict__ cand_count, int tiles_m, int nwg) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = xcd_remap(blockIdx.x, nwg);
+  const int m0 = (tile % tiles_m) * IPH_BM, n0 = (tile / tiles_m) * IPH_BN;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fg = lane >> 4;
+
+  // the running k-th entry of the lane's four query rows, loaded ahead of the main loop
+  float thr[4];
+  bool open[4];                                  // the row takes every score: its set is not full
+  bool live[4];                                  // the row exists
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + wr * 64 + i * 16 + fr;
+    live[i] = m < nq;
+    thr[i] = 0.f;
+    open[i] = false;
+    if (live[i]) {
+      const long at = (long)m * k + (k - 1);
+      open[i] = run_i[at] < 0;
+      const float t = run_s[at];
+      thr[i] = __float_as_uint(t) == 0x80000000u ? -FLT_MIN : t;
+    }
+  }
+
+  f32x4 acc[4][4];
+  iph_main_loop(nq, nc, H, Q, Cp, m0, n0, smem, wave, lane, acc);
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + wr * 64 + i * 16 + fr;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = n0 + wc * 64 + j * 16 + fg * 4;
+      bool pass[4];
+      bool any = false;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        pass[e] = live[i] && n + e < nc && (open[i] || !(acc[i][j][e] <= thr[i]));
+        any = any || pass[e];
+      }
+      if (__ballot(any) == 0ull) continue;       // wave-uniform: no survivor in this 16 x 16 tile
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (!pass[e]) continue;
+        const int slot = atomicAdd(cand_count + m, 1);          // device scope: one query's workgroups sit on different XCDs
+        if (slot < cand_cap) {
+          cand_s[(long)m * cand_cap + slot] = acc[i][j][e];
+          cand_i[(long)m * cand_cap + slot] = id0 + n + e;
+        }
       }
     }
   }
@@ -205,11 +293,11 @@ __device__ __forceinline__ void tk_unkey(uint64_t key, float* s, long long* id) 
   *id = (long long)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu));
 }
 
-// descending bitonic sort of arr[0..TK_N) (256 threads)
-__device__ void tk_sort(uint64_t* arr) {
-  for (int k = 2; k <= TK_N; k <<= 1) {
+// descending bitonic sort of arr[0..n), n a power of two <= TK_N (256 threads)
+__device__ void tk_sort(uint64_t* arr, int n) {
+  for (int k = 2; k <= n; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < TK_N / 2; t += 256) {
+      for (int t = threadIdx.x; t < n / 2; t += 256) {
         const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));      // lower index of the pair
         const int p = i | j;
         const bool desc = (i & k) == 0;
@@ -221,33 +309,50 @@ __device__ void tk_sort(uint64_t* arr) {
   }
 }
 
+// cand_count == nullptr: m candidates per query, scores[q * ld + j] with ids[q * ld_ids + j] or id_base + j.
+// cand_count != nullptr: the lists of ip_filter_f16_kernel (ids explicit, ld = ld_ids = cand_cap = m): query q has
+// min(cand_count[q], m) entries; a count above m adds 1 to *overflow; the count is reset to 0.
 __global__ __launch_bounds__(256) void topk_stream_kernel(int m, const float* __restrict__ scores, long ld,
                                                           const long long* __restrict__ ids, long ld_ids, long long id_base,
-                                                          int k, float* __restrict__ run_s, long long* __restrict__ run_i) {
+                                                          int k, float* __restrict__ run_s, long long* __restrict__ run_i,
+                                                          int* __restrict__ cand_count, int* __restrict__ overflow) {
   __shared__ uint64_t arr[TK_N];
-  __shared__ int cnt;
+  __shared__ int cnt, listed;
   const int q = blockIdx.x, tid = threadIdx.x;
+  int n = TK_N;                                    // keys sorted per flush
+  if (cand_count) {
+    if (tid == 0) listed = cand_count[q];
+    __syncthreads();
+    const int c = listed;
+    if (c == 0) return;                            // uniform: nothing survived, the running set stands
+    if (tid == 0) {
+      cand_count[q] = 0;
+      if (c > m) atomicAdd(overflow, 1);
+    }
+    m = min(c, m);
+    while ((n >> 1) >= k + m) n >>= 1;             // the next power of two >= k + m (TK_N when the list needs flushes)
+  }
   const float* row = scores + (long)q * ld;
   const long long* idr = ids ? ids + (long)q * ld_ids : nullptr;
-  for (int t = tid; t < TK_N; t += 256) {
+  for (int t = tid; t < n; t += 256) {
     uint64_t key = 0;
     if (t < k) { const long long id = run_i[(long)q * k + t]; if (id >= 0) key = tk_key(run_s[(long)q * k + t], id); }
     arr[t] = key;
   }
   if (tid == 0) cnt = 0;
   __syncthreads();
-  const int cap = TK_N - k;
+  const int cap = n - k;
   for (int s0 = 0; s0 < m; s0 += TK_SEG) {
-    if (cnt + TK_SEG > cap) {                      // uniform: fold the buffer into the best-k first
+    const int s1 = min(m, s0 + TK_SEG);
+    if (cnt + (s1 - s0) > cap) {                   // uniform: fold the buffer into the best-k first
       __syncthreads();
-      tk_sort(arr);
-      for (int t = k + tid; t < TK_N; t += 256) arr[t] = 0;
+      tk_sort(arr, n);
+      for (int t = k + tid; t < n; t += 256) arr[t] = 0;
       if (tid == 0) cnt = 0;
       __syncthreads();
     }
     const uint64_t tau = arr[k - 1];               // running k-th key (0 while fewer than k are known)
     __syncthreads();
-    const int s1 = min(m, s0 + TK_SEG);
     for (int j = s0 + tid; j < s1; j += 256) {
       const long long id = idr ? idr[j] : id_base + j;
       if (id < 0) continue;
@@ -256,7 +361,7 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(int m, const float* __
     }
     __syncthreads();
   }
-  tk_sort(arr);
+  tk_sort(arr, n);
   for (int t = tid; t < k; t += 256) {
     float s; long long id;
     tk_unkey(arr[t], &s, &id);
@@ -289,6 +394,25 @@ extern "C" int simx_ip_scores_f16(simx_stream_t stream, int nq, int nc, int H, c
   return SIMX_OK;
 }
 
+extern "C" int simx_ip_filter_f16(simx_stream_t stream, int nq, int nc, int H, const void* q16, const void* c16, int64_t id0, int k,
+                                  const float* run_scores, const int64_t* run_ids, float* cand_scores, int64_t* cand_ids, int cand_cap,
+                                  int* cand_count) {
+  hipStream_t s = (hipStream_t)stream;
+  SIMX_PROF(SIMX_K_TOPK, s, 2.0 * nq * nc * H);
+  SIMX_REQUIRE(nq > 0 && nc > 0 && H > 0 && H % 8 == 0, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: bad shape nq=%d nc=%d H=%d", nq, nc, H);
+  SIMX_REQUIRE(k > 0 && k <= TK_KMAX && cand_cap > 0, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: need 0 < k=%d <= %d and cand_cap=%d > 0", k, TK_KMAX, cand_cap);
+  SIMX_REQUIRE(q16 && c16 && simx_al16(q16) && simx_al16(c16), SIMX_ERR_BAD_SHAPE, "ip_filter_f16: q16 / c16 must be non-NULL and 16-byte aligned");
+  SIMX_REQUIRE(run_scores && run_ids && cand_scores && cand_ids && cand_count, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: NULL argument");
+  SIMX_REQUIRE(id0 >= 0 && id0 + nc < 0xFFFFFFFFll, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: ids must fit 32 bits");
+  const int tiles_m = cdiv(nq, IPH_BM), tiles_n = cdiv(nc, IPH_BN);
+  SIMX_REQUIRE((long)tiles_m * tiles_n <= 0x7FFFFFFFl, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: too many tiles (nq=%d nc=%d)", nq, nc);
+  const int nwg = tiles_m * tiles_n;
+  hipLaunchKernelGGL(ip_filter_f16_kernel, dim3(nwg), dim3(256), 0, s, nq, nc, H, (const f16_t*)q16, (const f16_t*)c16, (long long)id0, k,
+                     run_scores, (const long long*)run_ids, cand_scores, (long long*)cand_ids, cand_cap, cand_count, tiles_m, nwg);
+  SIMX_CHECK_LAUNCH("ip_filter_f16");
+  return SIMX_OK;
+}
+
 extern "C" int simx_topk_update(simx_stream_t stream, int nq, int m, const float* scores, long ld, const int64_t* ids, long ld_ids,
                                 int64_t id_base, int k, float* run_scores, int64_t* run_ids) {
   hipStream_t s = (hipStream_t)stream;
@@ -296,8 +420,20 @@ extern "C" int simx_topk_update(simx_stream_t stream, int nq, int m, const float
   SIMX_REQUIRE(scores && run_scores && run_ids && ld >= m, SIMX_ERR_BAD_SHAPE, "topk_update: NULL argument / ld < m");
   SIMX_REQUIRE(ids != nullptr || (id_base >= 0 && id_base + m < 0xFFFFFFFFll), SIMX_ERR_BAD_SHAPE, "topk_update: ids must fit 32 bits");
   hipLaunchKernelGGL(topk_stream_kernel, dim3(nq), dim3(256), 0, s, m, scores, ld, (const long long*)ids, ld_ids, (long long)id_base, k,
-                     run_scores, (long long*)run_ids);
+                     run_scores, (long long*)run_ids, (int*)nullptr, (int*)nullptr);
   SIMX_CHECK_LAUNCH("topk_update");
+  return SIMX_OK;
+}
+
+extern "C" int simx_topk_fold_lists(simx_stream_t stream, int nq, const float* cand_scores, const int64_t* cand_ids, int cand_cap,
+                                    int* cand_count, int k, float* run_scores, int64_t* run_ids, int* overflow) {
+  hipStream_t s = (hipStream_t)stream;
+  SIMX_REQUIRE(nq > 0 && cand_cap > 0 && k > 0 && k <= TK_KMAX, SIMX_ERR_BAD_SHAPE, "topk_fold_lists: need nq=%d > 0, cand_cap=%d > 0, 0 < k=%d <= %d", nq,
+               cand_cap, k, TK_KMAX);
+  SIMX_REQUIRE(cand_scores && cand_ids && cand_count && run_scores && run_ids && overflow, SIMX_ERR_BAD_SHAPE, "topk_fold_lists: NULL argument");
+  hipLaunchKernelGGL(topk_stream_kernel, dim3(nq), dim3(256), 0, s, cand_cap, cand_scores, (long)cand_cap, (const long long*)cand_ids, (long)cand_cap,
+                     0ll, k, run_scores, (long long*)run_ids, cand_count, overflow);
+  SIMX_CHECK_LAUNCH("topk_fold_lists");
   return SIMX_OK;
 }
 
@@ -339,4 +475,78 @@ extern "C" int simx_flat_ip_search_f16(simx_stream_t stream, int nq, long nc, in
                                        float* out_scores, int64_t* out_ids) {
   return flat_ip_search("flat_ip_search_f16", true, stream, nq, nc, H, q16, corpus16, id_base, k, chunk, workspace, workspace_bytes, out_scores,
                         out_ids);
+}
+
+// ---- one-pass float16 search: seed pass unfused, then filter + fold per chunk -------------------------------------------
+// workspace: [seed scores nq x ld][cand_scores nq x cap][cand_ids nq x cap][cand_count nq][overflow word], each part 16-byte aligned
+struct FusedWs { size_t ld, cand_s, cand_i, count, ovf, total; };
+static FusedWs fused_ws(int nq, int seed_rows, int cand_cap) {
+  auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  FusedWs w;
+  w.ld = ((size_t)seed_rows + 3) & ~(size_t)3;
+  w.cand_s = up((size_t)nq * w.ld * sizeof(float));
+  w.cand_i = w.cand_s + up((size_t)nq * cand_cap * sizeof(float));
+  w.count = w.cand_i + up((size_t)nq * cand_cap * sizeof(int64_t));
+  w.ovf = w.count + up((size_t)nq * sizeof(int));
+  w.total = w.ovf + 16;
+  return w;
+}
+
+extern "C" size_t simx_flat_ip_fused_workspace_bytes(int nq, int seed_rows, int cand_cap) {
+  if (nq <= 0 || seed_rows <= 0 || cand_cap <= 0) return 0;
+  return fused_ws(nq, seed_rows, cand_cap).total;
+}
+
+__global__ void fused_overflow_out_kernel(const int* __restrict__ word, int* __restrict__ out) { *out = *word; }
+
+extern "C" int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
+                                             int64_t id_base, int k, int chunk, int seed_rows, int cand_cap, void* workspace,
+                                             size_t workspace_bytes, float* out_scores, int64_t* out_ids, int* overflow) {
+  hipStream_t s = (hipStream_t)stream;
+  SIMX_REQUIRE(nq > 0 && nc >= 0 && chunk > 0 && seed_rows > 0 && cand_cap > 0, SIMX_ERR_BAD_SHAPE,
+               "flat_ip_search_f16_fused: bad shape nq=%d nc=%ld chunk=%d seed_rows=%d cand_cap=%d", nq, nc, chunk, seed_rows, cand_cap);
+  SIMX_REQUIRE(H > 0 && H % 8 == 0 && k > 0 && k <= TK_KMAX, SIMX_ERR_BAD_SHAPE, "flat_ip_search_f16_fused: need H=%d %% 8 == 0 and 0 < k=%d <= %d", H, k,
+               TK_KMAX);
+  SIMX_REQUIRE(q16 && simx_al16(q16) && (nc == 0 || (corpus16 && simx_al16(corpus16))) && workspace && simx_al16(workspace), SIMX_ERR_BAD_SHAPE,
+               "flat_ip_search_f16_fused: q16 / corpus16 / workspace must be non-NULL and 16-byte aligned");
+  SIMX_REQUIRE(out_scores && out_ids && overflow, SIMX_ERR_BAD_SHAPE, "flat_ip_search_f16_fused: NULL output");
+  SIMX_REQUIRE(id_base >= 0 && id_base + nc < 0xFFFFFFFFll, SIMX_ERR_BAD_SHAPE, "flat_ip_search_f16_fused: ids must fit 32 bits");
+  SIMX_REQUIRE(workspace_bytes >= simx_flat_ip_fused_workspace_bytes(nq, seed_rows, cand_cap), SIMX_ERR_WORKSPACE,
+               "flat_ip_search_f16_fused: workspace too small");
+  const FusedWs w = fused_ws(nq, seed_rows, cand_cap);
+  char* base = (char*)workspace;
+  float* seed_s = (float*)base;
+  float* cand_s = (float*)(base + w.cand_s);
+  int64_t* cand_i = (int64_t*)(base + w.cand_i);
+  int* count = (int*)(base + w.count);
+  int* ovf = (int*)(base + w.ovf);
+  const f16_t* corpus = (const f16_t*)corpus16;
+  hipLaunchKernelGGL(topk_init_kernel, dim3(cdiv((int)((long)nq * k), 256)), dim3(256), 0, s, (long)nq * k, out_scores, (long long*)out_ids);
+  SIMX_CHECK_LAUNCH("topk_init");
+  if (hipMemsetAsync(count, 0, w.total - w.count, s) != hipSuccess) {          // the counts and the overflow word
+    simx_set_error("flat_ip_search_f16_fused: hipMemsetAsync failed");
+    return SIMX_ERR_HIP;
+  }
+  // with an empty running set every score survives: the first seed_rows rows take the unfused pass
+  long seen = nc < seed_rows ? nc : seed_rows;
+  if (seen > 0) {
+    int rc = simx_ip_scores_f16(stream, nq, (int)seen, H, q16, corpus, seed_s, (long)w.ld);
+    if (rc) return rc;
+    rc = simx_topk_update(stream, nq, (int)seen, seed_s, (long)w.ld, nullptr, 0, id_base, k, out_scores, out_ids);
+    if (rc) return rc;
+  }
+  // then chunks that grow with what has been seen: about k * m / seen <= k survivors per query on rows in random order
+  while (seen < nc) {
+    long m = nc - seen;
+    if (m > seen) m = seen;
+    if (m > chunk) m = chunk;
+    int rc = simx_ip_filter_f16(stream, nq, (int)m, H, q16, corpus + seen * H, id_base + seen, k, out_scores, out_ids, cand_s, cand_i, cand_cap, count);
+    if (rc) return rc;
+    rc = simx_topk_fold_lists(stream, nq, cand_s, cand_i, cand_cap, count, k, out_scores, out_ids, ovf);
+    if (rc) return rc;
+    seen += m;
+  }
+  hipLaunchKernelGGL(fused_overflow_out_kernel, dim3(1), dim3(1), 0, s, ovf, overflow);
+  SIMX_CHECK_LAUNCH("fused_overflow_out");
+  return SIMX_OK;
 }

@@ -8,7 +8,12 @@ merge.  No CPU path: without the HIP library every call raises.
 
 storage="fp16" is faiss's ``useFloat16``: rows and queries are rounded to IEEE binary16 (round to nearest even; values
 beyond the binary16 range become +-inf, as in FAISS, and nothing checks for them), the shard takes 2 B per element and the
-scores are accumulated in float32 on the matrix cores (ip_scores_f16_kernel)."""
+scores are accumulated in float32 on the matrix cores (ip_scores_f16_kernel).
+
+fused=True (storage="fp16" only, opt-in) searches in one pass: after a short unfused seed pass the score tile is compared with
+each query's running k-th entry inside the score kernel (ip_filter_f16_kernel) and only the survivors are written, to a
+per-query candidate list of ``cand_cap`` entries that the top-k kernel folds in.  The result is bit for bit the unfused one; a
+query block whose list overflowed (rows in adversarial order) is searched again by the unfused path."""
 import ctypes as C
 
 import torch
@@ -19,11 +24,14 @@ from . import _lib as L
 class FlatIPIndex(object):
     """index = FlatIPIndex(dim); index.add(emb); D, I = index.search(q, k)   (faiss.IndexFlatIP surface)."""
 
-    def __init__(self, dim, id_base=0, chunk=65536, query_block=8192, storage="fp32"):
+    def __init__(self, dim, id_base=0, chunk=65536, query_block=8192, storage="fp32", fused=False, seed_rows=None, cand_cap=4096):
         """``chunk``: corpus rows scored per pass; ``query_block``: queries per pass -- the score workspace is
         query_block x chunk x 4 B (2 GB by default) whatever the number of queries (the 503 k MS-MARCO train queries in one
         call would otherwise ask for 132 GB).  ``storage``: "fp32" (the default: float32 rows, one fmaf chain per score) or
-        "fp16" (binary16 rows and queries, float32 scores from the matrix cores; needs dim % 8 == 0)."""
+        "fp16" (binary16 rows and queries, float32 scores from the matrix cores; needs dim % 8 == 0).  ``fused``: the one-pass
+        float16 search (experimental, off by default); its workspace is query_block x (seed_rows x 4 + cand_cap x 12) B.
+        ``seed_rows``: rows of the unfused first pass, max(8192, 4 k) when None; ``cand_cap``: entries per candidate list.
+        ``last_search_fallbacks``: query blocks of the last search() that overflowed a list and were searched again unfused."""
         if storage not in ("fp32", "fp16"):
             raise ValueError("FlatIPIndex: storage must be 'fp32' or 'fp16', not %r" % (storage,))
         if storage == "fp16" and dim % 8 != 0:
@@ -33,6 +41,16 @@ class FlatIPIndex(object):
         self.storage = storage
         self._dtype = torch.float16 if storage == "fp16" else torch.float32
         self._search = "simx_flat_ip_search_f16" if storage == "fp16" else "simx_flat_ip_search"
+        if fused and storage != "fp16":
+            raise ValueError("FlatIPIndex: fused=True needs storage='fp16' (the float32 score kernel is bound by its FMA rate, not by "
+                             "the score round trip)")
+        if int(cand_cap) < 1:
+            raise ValueError("FlatIPIndex: cand_cap must be at least 1, not %r" % (cand_cap,))
+        if seed_rows is not None and int(seed_rows) < 1:
+            raise ValueError("FlatIPIndex: seed_rows must be at least 1, not %r" % (seed_rows,))
+        self.fused, self.cand_cap = bool(fused), int(cand_cap)
+        self.seed_rows = None if seed_rows is None else int(seed_rows)
+        self.last_search_fallbacks = 0
         self._parts, self._emb = [], None
 
     @property
@@ -66,15 +84,38 @@ class FlatIPIndex(object):
         I = torch.empty(nq, k, dtype=torch.int64, device=q.device)
         chunk = max(4, min(self.chunk, max(nc, 4)))
         qb = max(1, min(self.query_block, nq))
-        ws_bytes = int(L.load().simx_flat_ip_workspace_bytes(qb, chunk))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-        for lo in range(0, nq, qb):                     # query blocks reuse ONE workspace
+        blocks = list(range(0, nq, qb))
+        self.last_search_fallbacks = 0
+        if self.fused:
+            blocks = self._search_fused(q, corpus, nc, k, chunk, qb, blocks, D, I)
+            self.last_search_fallbacks = len(blocks)
+        if blocks:
+            ws_bytes = int(L.load().simx_flat_ip_workspace_bytes(qb, chunk))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        for lo in blocks:                               # query blocks reuse ONE workspace
             n = min(qb, nq - lo)
             L.call(self._search, L.stream_ptr(), n, nc, self.d, L.ptr(q[lo:lo + n]), L.ptr(corpus) if nc else None,
                    self.id_base, k, chunk, L.ptr(ws), ws_bytes, L.ptr(D[lo:lo + n]), L.ptr(I[lo:lo + n]))
         if group is None:
             return D, I
         return merge_topk(D, I, k, group)
+
+
+    def _search_fused(self, q, corpus, nc, k, chunk, qb, blocks, D, I):
+        """the one-pass search of every query block; -> the blocks whose candidate lists overflowed (one host read after the loop)"""
+        nq = q.shape[0]
+        seed = max(8192, 4 * k) if self.seed_rows is None else self.seed_rows
+        seed = max(1, min(seed, nc))                    # no workspace for seed rows the shard does not have
+        ws_bytes = int(L.load().simx_flat_ip_fused_workspace_bytes(qb, seed, self.cand_cap))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        overflow = torch.empty(len(blocks), dtype=torch.int32, device=q.device)
+        for b, lo in enumerate(blocks):
+            n = min(qb, nq - lo)
+            L.call("simx_flat_ip_search_f16_fused", L.stream_ptr(), n, nc, self.d, L.ptr(q[lo:lo + n]), L.ptr(corpus) if nc else None,
+                   self.id_base, k, chunk, seed, self.cand_cap, L.ptr(ws), ws_bytes, L.ptr(D[lo:lo + n]), L.ptr(I[lo:lo + n]),
+                   L.ptr(overflow[b:b + 1]))
+        flags = overflow.cpu().tolist()                 # the one synchronisation of a fused search
+        return [lo for lo, f in zip(blocks, flags) if f != 0]
 
 
 def merge_topk(D, I, k, group):

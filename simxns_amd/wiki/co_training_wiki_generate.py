@@ -51,11 +51,14 @@ def get_new_dataset(args, model, global_step, renew_tools):
 
 
 def get_arguments(argv=None):
-    """the train job's flags plus --index_float16 (binary16 index storage, the reference's co.useFloat16; default off)."""
+    """the train job's flags plus --index_float16 (binary16 index storage, the reference's co.useFloat16; default off) and,
+    with it, --index_fused (its one-pass search; experimental, default off)."""
     argv = list(sys.argv[1:] if argv is None else argv)
-    index_float16 = "--index_float16" in argv
-    args = M.get_arguments([a for a in argv if a != "--index_float16"])
-    args.index_float16 = index_float16
+    index_float16, index_fused = "--index_float16" in argv, "--index_fused" in argv
+    if index_fused and not index_float16:
+        raise SystemExit("--index_fused needs --index_float16: the one-pass search exists for the binary16 index only")
+    args = M.get_arguments([a for a in argv if a not in ("--index_float16", "--index_fused")])
+    args.index_float16, args.index_fused = index_float16, index_fused
     return args
 
 
@@ -67,7 +70,8 @@ def main(argv=None):
     tokenizer, model = load_model(args)
     renew_tools = RenewTools(passages_path=args.passage_path, tokenizer=tokenizer, output_dir=args.ann_dir,
                              temp_dir=os.path.join(args.ann_dir, 'temp'), max_seq_length=args.max_seq_length, rank=args.rank,
-                             world=args.world_size, index_float16=args.index_float16)
+                             world=args.world_size, index_float16=args.index_float16,
+                             index_fused=args.index_fused)
     if args.world_size > 1:
         dist.barrier()
     if args.global_step <= args.max_steps:

@@ -1,7 +1,8 @@
 """Micro-benchmark of the generate job's search on one GPU (not part of bench.py's metric): inner-product scores + exact
-top-k over a corpus shard resident in HBM, timed for BOTH index storages on the same corpus in one process -- float32 (one
-fmaf chain per score, VALU) and float16 (binary16 rows, matrix cores) -- one JSON record each, then their ratio, then the kernels of one
-default-size chunk (all queries x 65536 rows) timed apart by device events.
+top-k over a corpus shard resident in HBM, timed for the index storages on the same corpus in one process -- float32 (one
+fmaf chain per score, VALU), float16 (binary16 rows, matrix cores) and float16 fused (the one-pass search; its searches alternate with
+the unfused float16 ones) -- one JSON record each, then their ratios, then the kernels of one default-size chunk (all queries x 65536
+rows) timed apart by device events: the unfused pair, and the fused pair at the warm running set of a search's last chunk.
 usage: python tools/search_bench.py [nq nc k] [--out FILE]"""
 import json
 import subprocess
@@ -28,25 +29,40 @@ parts = [torch.randn(min(250000, nc - lo), H, device=dev) for lo in range(0, nc,
 q = torch.randn(nq, H, device=dev)
 
 
-def run(storage, repeats=3):
-    index = FlatIPIndex(H, storage=storage)
+def make_index(storage, fused=False):
+    index = FlatIPIndex(H, storage=storage, fused=fused)
     for p in parts:
         index.add(p)
-    index.search(q[:64], k)
+    return index
+
+
+def run(indexes, repeats=3):
+    """one record per index; the timed searches of several indexes alternate, so that they see the same clock and neighbours"""
+    times, fallbacks = [[] for _ in indexes], [0] * len(indexes)
+    for index in indexes:
+        index.search(q[:64], k)
     torch.cuda.synchronize()
-    times = []
     for _ in range(repeats):
-        t0 = time.perf_counter()
-        index.search(q, k)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-    dt = min(times)
-    rate = 2.0 * nq * nc * H / dt
-    return {"storage": storage, "nq": nq, "nc": nc, "k": k, "H": H, "seconds": round(dt, 4), "seconds_all": [round(t, 4) for t in times],
-            "queries_per_s": round(nq / dt, 1), "tflops": round(rate / 1e12, 2),
-            "score_bytes_per_s_tb": round(8.0 * nq * nc / dt / 1e12, 3),          # the score chunk is written, then read by the top-k
-            "index_gb": round(nc * H * (2 if storage == "fp16" else 4) / 1e9, 3),
-            "full_msmarco_train_job_s_per_gpu_of_8": round(502939 * 8841823 / 8 * H * 2 / rate, 1)}
+        for i, index in enumerate(indexes):
+            t0 = time.perf_counter()
+            index.search(q, k)
+            torch.cuda.synchronize()
+            times[i].append(time.perf_counter() - t0)
+            fallbacks[i] += index.last_search_fallbacks
+    out = []
+    for index, ts, fb in zip(indexes, times, fallbacks):
+        dt = min(ts)
+        rate = 2.0 * nq * nc * H / dt
+        rec = {"storage": index.storage, "fused": index.fused, "nq": nq, "nc": nc, "k": k, "H": H, "seconds": round(dt, 4),
+               "seconds_all": [round(t, 4) for t in ts], "queries_per_s": round(nq / dt, 1), "tflops": round(rate / 1e12, 2),
+               "index_gb": round(nc * H * (2 if index.storage == "fp16" else 4) / 1e9, 3),
+               "full_msmarco_train_job_s_per_gpu_of_8": round(502939 * 8841823 / 8 * H * 2 / rate, 1)}
+        if index.fused:
+            rec["last_search_fallbacks"] = fb                                   # summed over the timed searches
+        else:
+            rec["score_bytes_per_s_tb"] = round(8.0 * nq * nc / dt / 1e12, 3)   # the score chunk is written, then read by the top-k
+        out.append(rec)
+    return out
 
 
 def clock_mhz():
@@ -62,7 +78,10 @@ def clock_mhz():
 
 
 def split(chunk=65536):
-    """the three kernels of one chunk pass, each alone: float16 scores, float32 scores, top-k update of a warm running set"""
+    """the kernels of one chunk pass, each alone: float16 scores, float32 scores, top-k update of a warm running set; then the
+    fused pair on the LAST `chunk` rows of the corpus against the running set of all rows before them (the state a search is in
+    there): the filter kernel, and the fold of the lists it wrote (the running set and the counts are restored before every fold;
+    the restore is timed alone and subtracted)"""
     m = min(chunk, nc)
     c = parts[0][:m] if parts[0].shape[0] >= m else torch.cat(parts, 0)[:m]
     m = c.shape[0]
@@ -87,17 +106,67 @@ def split(chunk=65536):
     t16 = ms(lambda: L.call("simx_ip_scores_f16", sp, nq, m, H, L.ptr(q16), L.ptr(c16), L.ptr(S), m), 10)
     ttk = ms(lambda: L.call("simx_topk_update", sp, nq, m, L.ptr(S), m, None, 0, 0, k, L.ptr(D), L.ptr(I)), 10)
     fl = 2.0 * nq * m * H
-    return {"chunk": [nq, m, H], "ip_scores_f16_ms": round(t16, 3), "ip_scores_f16_tflops": round(fl / t16 / 1e9, 1),
+    fused = {}
+    if nc > m:
+        head = FlatIPIndex(H, storage="fp16")
+        allrows = torch.cat(parts, 0)
+        head.add(allrows[:nc - m])
+        D0, I0 = head.search(q, k)
+        c16 = allrows[nc - m:].half()
+        del head, allrows
+        cap = 4096
+        cs = torch.empty(nq, cap, device=dev)
+        ci = torch.empty(nq, cap, dtype=torch.int64, device=dev)
+        cnt = torch.zeros(nq, dtype=torch.int32, device=dev)
+        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+        D, I = D0.clone(), I0.clone()
+
+        def filt():
+            cnt.zero_()
+            L.call("simx_ip_filter_f16", sp, nq, m, H, L.ptr(q16), L.ptr(c16), nc - m, k, L.ptr(D0), L.ptr(I0), L.ptr(cs), L.ptr(ci), cap, L.ptr(cnt))
+
+        def restore():
+            D.copy_(D0); I.copy_(I0); cnt.copy_(cnt0)
+
+        def fold():
+            restore()
+            L.call("simx_topk_fold_lists", sp, nq, L.ptr(cs), L.ptr(ci), cap, L.ptr(cnt), k, L.ptr(D), L.ptr(I), L.ptr(ovf))
+
+        tfi = ms(filt, 10)
+        cnt0 = cnt.clone()
+        tz = ms(cnt.zero_, 10)
+        tfo = ms(fold, 10)
+        tre = ms(restore, 10)
+        fused = {"fused_chunk_rows_seen_before": nc - m, "ip_filter_f16_ms": round(tfi - tz, 3), "ip_filter_f16_tflops": round(fl / (tfi - tz) / 1e9, 1),
+                 "count_zero_ms_subtracted": round(tz, 4), "topk_fold_lists_ms": round(tfo - tre, 3), "restore_ms_subtracted": round(tre, 4),
+                 "survivors_per_query_mean": round(cnt0.float().mean().item(), 2), "survivors_per_query_max": int(cnt0.max().item()),
+                 "fold_overflows": int(ovf.item())}
+    return {"chunk": [nq, m, H], **fused, "ip_scores_f16_ms": round(t16, 3), "ip_scores_f16_tflops": round(fl / t16 / 1e9, 1),
             "ip_scores_f16_store_tb_s": round(nq * m * 4 / t16 / 1e9, 3), "ip_scores_f32_ms": round(t32, 3),
             "ip_scores_f32_tflops": round(fl / t32 / 1e9, 1), "topk_update_ms": round(ttk, 3), "topk_read_tb_s": round(nq * m * 4 / ttk / 1e9, 3)}
 
 
-records = [run("fp32"), run("fp16")]
+def commit():
+    try:
+        return subprocess.run(["git", "rev-parse", "--short", "HEAD"], capture_output=True, text=True, timeout=30).stdout.strip() or None
+    except Exception:
+        return None
+
+
+f16, fus = make_index("fp16"), make_index("fp16", fused=True)
+D16, I16 = f16.search(q, k)
+Dfu, Ifu = fus.search(q, k)
+same = bool((I16 == Ifu).all().item() and (D16.view(torch.int32) == Dfu.view(torch.int32)).all().item())
+del D16, I16, Dfu, Ifu
+records = run([make_index("fp32")]) + run([f16, fus])
+del f16, fus
 for r in records:
     print(json.dumps(r))
-summary = {"fp32_seconds": records[0]["seconds"], "fp16_seconds": records[1]["seconds"],
-           "fp16_speedup": round(records[0]["seconds"] / records[1]["seconds"], 2), "sclk": clock_mhz(),
-           "device": torch.cuda.get_device_name(0)}
+summary = {"fp32_seconds": records[0]["seconds"], "fp16_seconds": records[1]["seconds"], "fp16_fused_seconds": records[2]["seconds"],
+           "fp16_speedup": round(records[0]["seconds"] / records[1]["seconds"], 2),
+           "fused_speedup_over_fp16": round(records[1]["seconds"] / records[2]["seconds"], 2),
+           "fused_result_equals_fp16_bit_for_bit": same, "last_search_fallbacks": records[2]["last_search_fallbacks"],
+           "sclk": clock_mhz(), "commit": commit(), "device": torch.cuda.get_device_name(0)}
 print(json.dumps(summary))
 per_chunk = split()
 print(json.dumps(per_chunk))
