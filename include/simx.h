@@ -610,7 +610,23 @@ int simx_assemble_batch(simx_stream_t stream, int B, int D, int QL, int PL, int 
  *                          Asynchronous on the stream.  *overflow (device memory) is written, not accumulated: non-zero = the
  *                          number of (query, chunk) lists that exceeded cand_cap, and out_scores / out_ids of THIS call are not
  *                          to be used (search again with simx_flat_ip_search_f16 or a larger cand_cap).  Neither chunk, seed_rows
- *                          nor cand_cap changes a result bit. */
+ *                          nor cand_cap changes a result bit.
+ *
+ * Plane-pair storage (opt-in; float32-grade scores on the 16-bit matrix cores): rows and queries arrive as float32 and are held as
+ * two binary16 planes, hi = rnd16(x) and lo = rnd16(x - hi), rounding to nearest even -- the split rule of the fp32 engine, taken
+ * by simx_planes_from(SIMX_F32 -> SIMX_F16).  Per element |x - hi - lo| <= max(2^-22 |x|, 2^-25).  A score is the float32 MFMA
+ * accumulation of Qhi.Clo + Qlo.Chi + Qhi.Chi; the lo.lo term is dropped by definition.  The accumulation runs in ONE K loop of
+ * fixed order -- per 64-wide k block hi.lo, lo.hi, then hi.hi -- with no split-K and no atomics, so a score's bits depend on neither
+ * the chunk, the query block nor the position of its row in a tile.  Top-k, tie order (lower id first), padding (-inf, -1) and
+ * id_base are those of the other two modes.  Values beyond the binary16 range are not supported: hi becomes +-inf and nothing
+ * checks.  H % 8 == 0; every plane pointer 16-byte aligned.  The index holds 4 B per element (the two planes are separate buffers;
+ * no float32 copy is kept).  The argument lists are those of the _f16 namesakes with each 16-bit operand replaced by its (hi, lo)
+ * pair; the workspaces are simx_flat_ip_workspace_bytes / simx_flat_ip_fused_workspace_bytes.
+ * simx_ip_scores_planes            simx_ip_scores_f16 on plane pairs
+ * simx_ip_filter_planes            simx_ip_filter_f16 on plane pairs: the same filter rule, list format and precondition
+ * simx_flat_ip_search_planes       simx_flat_ip_search over a plane-pair shard
+ * simx_flat_ip_search_planes_fused simx_flat_ip_search_f16_fused over a plane-pair shard: the same schedule and overflow word; the
+ *                                  result equals simx_flat_ip_search_planes's bit for bit unless a list overflowed */
 int simx_ip_scores(simx_stream_t stream, int nq, int nc, int H, const float* q, const float* c, float* scores, long ld);
 int simx_topk_update(simx_stream_t stream, int nq, int m, const float* scores, long ld, const int64_t* ids, long ld_ids,
                      int64_t id_base, int k, float* run_scores, int64_t* run_ids);
@@ -631,6 +647,18 @@ int simx_topk_fold_lists(simx_stream_t stream, int nq, const float* cand_scores,
 int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
                                   int64_t id_base, int k, int chunk, int seed_rows, int cand_cap, void* workspace,
                                   size_t workspace_bytes, float* out_scores, int64_t* out_ids, int* overflow);
+int simx_ip_scores_planes(simx_stream_t stream, int nq, int nc, int H, const void* q_hi, const void* q_lo, const void* c_hi, const void* c_lo,
+                          float* scores, long ld);
+int simx_ip_filter_planes(simx_stream_t stream, int nq, int nc, int H, const void* q_hi, const void* q_lo, const void* c_hi, const void* c_lo,
+                          int64_t id0, int k, const float* run_scores, const int64_t* run_ids, float* cand_scores, int64_t* cand_ids,
+                          int cand_cap, int* cand_count);
+int simx_flat_ip_search_planes(simx_stream_t stream, int nq, long nc, int H, const void* q_hi, const void* q_lo, const void* corpus_hi,
+                               const void* corpus_lo, int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
+                               float* out_scores, int64_t* out_ids);
+int simx_flat_ip_search_planes_fused(simx_stream_t stream, int nq, long nc, int H, const void* q_hi, const void* q_lo,
+                                     const void* corpus_hi, const void* corpus_lo, int64_t id_base, int k, int chunk, int seed_rows,
+                                     int cand_cap, void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_ids,
+                                     int* overflow);
 
 /* -------------------------------------------------------------- SimANS sampler
  * S1+S2 (SimANS/utils/MARCO_until_new.py:174-202, util_wiki.py:609-639, MARCO_until_Doc.py:110-148).

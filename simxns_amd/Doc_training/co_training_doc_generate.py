@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from simxns_amd.Doc_training import co_training_doc_train as T                                 # noqa: E402
 from simxns_amd.Doc_training.co_training_generate_new_train import RenewTools                  # noqa: E402
 from simxns_amd.co_training import co_training_marco_train as M                                # noqa: E402
+from simxns_amd.retrieval import index_storage                                                 # noqa: E402
 from simxns_amd.utils.dpr_utils import get_model_obj, load_states_from_checkpoint              # noqa: E402
 from simxns_amd.utils.util import is_first_worker                                              # noqa: E402
 
@@ -39,18 +40,21 @@ def get_new_dataset(args, model, global_step, renew_tools):
 
 def get_arguments(argv=None):
     """the train job's flags plus --max_doc_character N and --index_float16 (binary16 index storage, the reference's
-    co.useFloat16; default off) and, with it, --index_fused (its one-pass search; experimental, default off)."""
+    co.useFloat16; default off), --index_planes (binary16 plane pairs of the float32 rows, float32-grade scores from the matrix
+    cores; default off, not with --index_float16) and, with either, --index_fused (the one-pass search; experimental, default off)."""
     argv = list(sys.argv[1:] if argv is None else argv)
     max_doc_character = 10000
     if "--max_doc_character" in argv:
         i = argv.index("--max_doc_character")
         max_doc_character = int(argv[i + 1])
         del argv[i:i + 2]
-    index_float16, index_fused = "--index_float16" in argv, "--index_fused" in argv
-    if index_fused and not index_float16:
-        raise SystemExit("--index_fused needs --index_float16: the one-pass search exists for the binary16 index only")
-    args = M.get_arguments([a for a in argv if a not in ("--index_float16", "--index_fused")])
-    args.max_doc_character, args.index_float16, args.index_fused = max_doc_character, index_float16, index_fused
+    index_float16, index_planes, index_fused = "--index_float16" in argv, "--index_planes" in argv, "--index_fused" in argv
+    try:
+        index_storage(index_float16, index_planes, index_fused)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    args = M.get_arguments([a for a in argv if a not in ("--index_float16", "--index_planes", "--index_fused")])
+    args.max_doc_character, args.index_float16, args.index_planes, args.index_fused = max_doc_character, index_float16, index_planes, index_fused
     return args
 
 
@@ -67,7 +71,7 @@ def main(argv=None):
     renew_tools = RenewTools(os.path.join(args.passage_path, 'msmarco-docs.tsv'), tokenizer, args.ann_dir,
                              temp_dir=os.path.join(args.ann_dir, 'temp'), max_doc_character=max_doc_character, rank=args.rank,
                              world=args.world_size, index_float16=args.index_float16,
-                             index_fused=args.index_fused)
+                             index_fused=args.index_fused, index_planes=args.index_planes)
     if args.world_size > 1:
         dist.barrier()
     out = get_new_dataset(args, model, args.global_step, renew_tools) if args.global_step <= args.max_steps else {}

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from ..co_training.co_training_generate import compute_metrics, embed_table, tokenize_table
-from ..retrieval import FlatIPIndex
+from ..retrieval import FlatIPIndex, index_storage
 from ..utils.MARCO_until_Doc import load_docs
 from ..utils.dpr_utils import get_model_obj
 from ..utils.util import is_first_worker
@@ -58,11 +58,10 @@ def write_to_file(cand, scores, q_text, pos_qp, pos_qp_add, q_type, save_path, g
 
 class RenewTools(object):
     def __init__(self, passages_ctx_path, tokenizer, output_dir, temp_dir=None, max_doc_character=10000, max_doc_length=512,
-                 max_query_length=128, rank=0, world=1, index_float16=False, index_fused=False):
+                 max_query_length=128, rank=0, world=1, index_float16=False, index_fused=False, index_planes=False):
         """``index_float16``: the reference's (commented-out) ``co.useFloat16 = True``, FlatIPIndex(storage="fp16")."""
-        if index_fused and not index_float16:
-            raise ValueError("index_fused (FlatIPIndex(fused=True), the one-pass float16 search) needs index_float16")
-        self.index_float16, self.index_fused = bool(index_float16), bool(index_fused)
+        self.index_storage = index_storage(index_float16, index_planes, index_fused)     # refuses both modes, or fused with neither
+        self.index_float16, self.index_planes, self.index_fused = bool(index_float16), bool(index_planes), bool(index_fused)
         docs = load_docs(passages_ctx_path)                      # id -> url<sep>title<sep>body[:10000]
         if max_doc_character != 10000:
             docs = {k: v[:max_doc_character] for k, v in docs.items()}
@@ -79,7 +78,7 @@ class RenewTools(object):
     def get_new_faiss_index(self, model, device, batch_size=256):
         emb = embed_table(get_model_obj(model).body_emb, self.passage_table, device, batch_size=batch_size, pad_id=PAD)
         index = FlatIPIndex(emb.shape[1] if emb.numel() else 768, id_base=self.slice[0],
-                            storage="fp16" if self.index_float16 else "fp32", fused=self.index_fused)
+                            storage=self.index_storage, fused=self.index_fused)
         if emb.numel():
             index.add(emb)
         return index

@@ -21,7 +21,7 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from simxns_amd.model.models import BiBertEncoder                                     # noqa: E402
-from simxns_amd.retrieval import FlatIPIndex                                          # noqa: E402
+from simxns_amd.retrieval import FlatIPIndex, index_storage                           # noqa: E402
 from simxns_amd.utils.MARCO_until_new import HashTokenizer, load_id_text              # noqa: E402
 from simxns_amd.utils.dpr_utils import get_model_obj, load_states_from_checkpoint     # noqa: E402
 from simxns_amd.utils.util import is_first_worker                                     # noqa: E402
@@ -119,15 +119,14 @@ class RenewTools(object):
     """The reference's driver object (:269-460) reduced to what the job needs."""
 
     def __init__(self, passages_path, tokenizer, output_dir, passage_title_path=None, max_passage_length=128, rank=0, world=1,
-                 index_float16=False, index_fused=False):
+                 index_float16=False, index_fused=False, index_planes=False):
         """Reads the corpus file once (ids of every row: the search returns global corpus rows), but TOKENISES only this
         rank's contiguous slice [rank*n/world, (rank+1)*n/world) -- the only rows this rank embeds.  ``index_float16``: the
-        reference's (commented-out) ``co.useFloat16 = True``, FlatIPIndex(storage="fp16"); ``index_fused``: its one-pass search
-        (FlatIPIndex(fused=True), needs index_float16)."""
-        if index_fused and not index_float16:
-            raise ValueError("index_fused needs index_float16")
+        reference's (commented-out) ``co.useFloat16 = True``, FlatIPIndex(storage="fp16"); ``index_planes``: float32-grade scores on
+        the matrix cores, FlatIPIndex(storage="planes"); ``index_fused``: the one-pass search of either (FlatIPIndex(fused=True))."""
+        self.index_storage = index_storage(index_float16, index_planes, index_fused)
         self.tokenizer, self.output_dir, self.index_float16 = tokenizer, output_dir, bool(index_float16)
-        self.index_fused = bool(index_fused)
+        self.index_planes, self.index_fused = bool(index_planes), bool(index_fused)
         titles = load_id_text(passage_title_path) if passage_title_path and os.path.exists(passage_title_path) else {}
         rows = []
         with open(passages_path) as inp:
@@ -146,8 +145,7 @@ class RenewTools(object):
         if (lo, hi) != self.slice:
             raise ValueError("RenewTools was built for corpus rows %s, build_index asked for %s" % (self.slice, (lo, hi)))
         emb = embed_table(get_model_obj(model).body_emb, self.passage_table, device)
-        index = FlatIPIndex(emb.shape[1] if emb.numel() else 768, id_base=lo, storage="fp16" if self.index_float16 else "fp32",
-                            fused=self.index_fused)
+        index = FlatIPIndex(emb.shape[1] if emb.numel() else 768, id_base=lo, storage=self.index_storage, fused=self.index_fused)
         if emb.numel():
             index.add(emb)
         return index
@@ -197,7 +195,9 @@ def get_arguments(argv=None):
     """Flags of the reference's generate jobs (co_training_marco_generate.py:222-252, 327-362): --passage_path is the data
     DIRECTORY (para.txt, para.title.txt, qrels.{train,dev}.tsv inside), the model is output_dir/checkpoint-<global_step>,
     the mined file goes to --ann_dir.  --index_float16: binary16 index storage (the reference's co.useFloat16, off there too);
-    --index_fused: with it, the one-pass search that filters the scores in the score kernel (experimental, off by default)."""
+    --index_planes: float32 rows as binary16 plane pairs, float32-grade scores from the matrix cores (off by default; not with
+    --index_float16); --index_fused: with either, the one-pass search that filters the scores in the score kernel (experimental,
+    off by default)."""
     ap = argparse.ArgumentParser()
     A = ap.add_argument
     A("--model_type", required=True); A("--model_name_or_path", default=None); A("--output_dir", required=True)
@@ -209,10 +209,12 @@ def get_arguments(argv=None):
     for ignored in ("--max_seq_length", "--max_steps", "--adv_step", "--iteration_step", "--iteration_reranker_step"):
         A(ignored, type=int, default=0)
     A("--log_dir", default=None); A("--gradient_checkpointing", action="store_true")
-    A("--index_float16", action="store_true"); A("--index_fused", action="store_true")
+    A("--index_float16", action="store_true"); A("--index_planes", action="store_true"); A("--index_fused", action="store_true")
     args = ap.parse_args(argv)
-    if args.index_fused and not args.index_float16:
-        ap.error("--index_fused needs --index_float16: the one-pass search exists for the binary16 index only")
+    try:
+        index_storage(args.index_float16, args.index_planes, args.index_fused)
+    except ValueError as e:
+        ap.error(str(e))
     return args
 
 
@@ -242,7 +244,7 @@ def main():
         tok = BertTokenizer.from_pretrained(args.tokenizer_name or "bert-base-uncased", do_lower_case=True)
     data_dir = args.passage_path
     tools = RenewTools(os.path.join(data_dir, "para.txt"), tok, ann_dir, os.path.join(data_dir, "para.title.txt"), rank=rank, world=world,
-                       index_float16=args.index_float16, index_fused=args.index_fused)
+                       index_float16=args.index_float16, index_fused=args.index_fused, index_planes=args.index_planes)
     index = tools.build_index(model, device, rank, world)
     for mode, qa in (("train", args.train_qa_path), ("dev", args.dev_qa_path)):
         if qa:

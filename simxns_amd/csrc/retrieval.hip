@@ -11,6 +11,18 @@
 //                      position of its row in a tile.  128x128x64 tiles, LDS-DMA staging into the swizzled image of the
 //                      NT GEMMs, K tail zero-filled in LDS.  Bounds: 16-bit MFMA rate and, for a whole search, the 8 B
 //                      of HBM traffic per score of the write-then-top-k design.
+//   ip_scores_planes_kernel / ip_filter_planes_kernel  the plane-pair storage mode: every float32 row and query is held as two binary16
+//                      planes, hi = rnd16(x), lo = rnd16(x - hi) (the xp_split2 rule of gemm_xp.hip, taken by simx_planes_from), and a
+//                      score is the float32 MFMA accumulation of Qhi.Clo + Qlo.Chi + Qhi.Chi (lo.lo dropped by definition): 22
+//                      significand bits per operand element on the 16-bit matrix cores.  The loop is iph_main_loop<true>: the same
+//                      staging, LDS image, fragment reads and K order as the binary16 kernels, with four operand tiles per stage and
+//                      three products per 64-wide k block in the fixed order hi.lo, lo.hi, hi.hi; the epilogues are the ones of the
+//                      binary16 kernels.  Tile choice: BK stays 64, so the two stages take 128 KB of LDS and ONE workgroup runs per CU.
+//                      A k block is 96 MFMAs per wave against 64 KB of LDS-DMA, so the next stage lands well inside the matrix
+//                      work of the current one and a second workgroup has little latency left to hide; BK = 32 would keep two
+//                      workgroups but needs a second LDS image (64-B rows, another swizzle) and a barrier plus a fragment-read
+//                      restart every 32-deep step, which is the slower form of this loop.  Bounds: 3 x the 16-bit MFMA work of the
+//                      binary16 kernels for 2 x their operand bytes.
 //   ip_filter_f16_kernel  the same main loop (iph_main_loop: ONE copy, so a score has the same bits in both kernels) with a
 //                      filter epilogue instead of the store: each score is compared, still in the accumulators, with the running
 //                      k-th entry of its query (run_scores / run_ids [q*k + k-1]; id < 0 = the set is not full and everything
@@ -26,7 +38,7 @@
 //                      composite keys (orderable score << 32 | ~id): candidates below the running k-th key are
 //                      dropped while scanning, survivors are collected in LDS and folded in by a bitonic sort of
 //                      4096 keys whenever the buffer could overflow.  Ties: lower id first.  HBM-bound: reads the
-//                      score row once (4 B per candidate).  With a per-query count (the fold of ip_filter_f16_kernel's
+//                      score row once (4 B per candidate).  With a per-query count (the fold of the filter kernels'
 //                      lists) the rows of query q are its first min(cand_count[q], cand_cap) list entries, the sort is sized
 //                      to the next power of two >= k + that number, a count above cand_cap adds 1 to the overflow word and
 //                      the count is reset to 0 for the next chunk.
@@ -128,10 +140,28 @@ __device__ __forceinline__ void iph_stage_tile(const f16_t* __restrict__ G, int 
   }
 }
 
-// the ONE main loop of the binary16 score kernels: acc[i][j] = the 16 x 16 tiles (query rows wr * 64 + i * 16 .., passages
-// wc * 64 + j * 16 ..) of the 128 x 128 tile at (m0, n0), accumulated over all of H in ascending k
-__device__ __forceinline__ void iph_main_loop(int nq, int nc, int H, const f16_t* Q, const f16_t* Cp, int m0,
-                                              int n0, char* smem, int wave, int lane, f32x4 (&acc)[4][4]) {
+// one stage = the operand tiles of one k block: [Q][C] for binary16 operands, [Q hi][C hi][Q lo][C lo] for plane pairs
+template <bool PLANES>
+__device__ __forceinline__ void iph_stage(int nq, int nc, int H, const f16_t* Q, const f16_t* Ql, const f16_t* Cp, const f16_t* Cl, int m0,
+                                          int n0, int k0, char* st, int wave, int lane) {
+  iph_stage_tile(Q, H, m0, nq, k0, st, wave, lane);
+  iph_stage_tile(Cp, H, n0, nc, k0, st + IPH_TILE, wave, lane);
+  if constexpr (PLANES) {
+    iph_stage_tile(Ql, H, m0, nq, k0, st + 2 * IPH_TILE, wave, lane);
+    iph_stage_tile(Cl, H, n0, nc, k0, st + 3 * IPH_TILE, wave, lane);
+  }
+}
+
+// the ONE main loop of the matrix-core score kernels: acc[i][j] = the 16 x 16 tiles (query rows wr * 64 + i * 16 .., passages
+// wc * 64 + j * 16 ..) of the 128 x 128 tile at (m0, n0), accumulated over all of H in ascending k.
+//   PLANES == false: binary16 operands Q, Cp (Ql, Cl unused), one product per k block.
+//   PLANES == true : plane pairs (Q, Ql) and (Cp, Cl), three products per k block into the same accumulators, in the fixed order
+//                    hi.lo, lo.hi, hi.hi (corrections first, as gemm_xp.hip; lo.lo is dropped by definition).
+template <bool PLANES>
+__device__ __forceinline__ void iph_main_loop(int nq, int nc, int H, const f16_t* Q, const f16_t* Ql, const f16_t* Cp, const f16_t* Cl,
+                                              int m0, int n0, char* smem, int wave, int lane, f32x4 (&acc)[4][4]) {
+  constexpr int STAGE = (PLANES ? 4 : 2) * IPH_TILE;
+  constexpr int TERMS = PLANES ? 3 : 1;
   const int wr = wave >> 1, wc = wave & 1;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -139,35 +169,34 @@ __device__ __forceinline__ void iph_main_loop(int nq, int nc, int H, const f16_t
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int nt = (H + IPH_BK - 1) / IPH_BK;
-  iph_stage_tile(Q, H, m0, nq, 0, smem, wave, lane);
-  iph_stage_tile(Cp, H, n0, nc, 0, smem + IPH_TILE, wave, lane);
+  iph_stage<PLANES>(nq, nc, H, Q, Ql, Cp, Cl, m0, n0, 0, smem, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   const int fr = lane & 15, fg = lane >> 4;
   int cur = 0;
   for (int t = 0; t < nt; ++t) {
-    char* sa = smem + cur * 2 * IPH_TILE;
-    char* sb = sa + IPH_TILE;
-    if (t + 1 < nt) {
-      char* na = smem + (cur ^ 1) * 2 * IPH_TILE;
-      iph_stage_tile(Q, H, m0, nq, (t + 1) * IPH_BK, na, wave, lane);
-      iph_stage_tile(Cp, H, n0, nc, (t + 1) * IPH_BK, na + IPH_TILE, wave, lane);
-    }
+    const char* st = smem + cur * STAGE;
+    if (t + 1 < nt) iph_stage<PLANES>(nq, nc, H, Q, Ql, Cp, Cl, m0, n0, (t + 1) * IPH_BK, smem + (cur ^ 1) * STAGE, wave, lane);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {           // ascending k: the one accumulation order of a score
-      bf16x8 af[4], bfr[4];
+    for (int term = 0; term < TERMS; ++term) {   // plane pairs: Q hi . C lo, Q lo . C hi, Q hi . C hi
+      const char* sa = st + (PLANES && term == 1 ? 2 * IPH_TILE : 0);
+      const char* sb = st + IPH_TILE + (PLANES && term == 0 ? 2 * IPH_TILE : 0);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ra = wr * 64 + i * 16 + fr;
-        af[i] = *reinterpret_cast<const bf16x8*>(sa + ra * 128 + (((ks * 4 + fg) ^ ((ra >> 1) & 7)) << 4));
-        const int rb = wc * 64 + i * 16 + fr;
-        bfr[i] = *reinterpret_cast<const bf16x8*>(sb + rb * 128 + (((ks * 4 + fg) ^ ((rb >> 1) & 7)) << 4));
+      for (int ks = 0; ks < 2; ++ks) {           // ascending k: the one accumulation order of a score
+        bf16x8 af[4], bfr[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int ra = wr * 64 + i * 16 + fr;
+          af[i] = *reinterpret_cast<const bf16x8*>(sa + ra * 128 + (((ks * 4 + fg) ^ ((ra >> 1) & 7)) << 4));
+          const int rb = wc * 64 + i * 16 + fr;
+          bfr[i] = *reinterpret_cast<const bf16x8*>(sb + rb * 128 + (((ks * 4 + fg) ^ ((rb >> 1) & 7)) << 4));
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = H16<f16_t>::mfma(bfr[j], af[i], acc[i][j]);
       }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = H16<f16_t>::mfma(bfr[j], af[i], acc[i][j]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -175,30 +204,29 @@ __device__ __forceinline__ void iph_main_loop(int nq, int nc, int H, const f16_t
   }
 }
 
-__global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
-                                                               const f16_t* __restrict__ Cp, float* __restrict__ S, long ldS,
-                                                               int tiles_m, int nwg) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // queries fastest: the workgroups of one XCD walk all query tiles of a few corpus tiles, so a corpus row leaves HBM once
+// the tile a workgroup scores.  Queries fastest: the workgroups of one XCD walk all query tiles of a few corpus tiles, so a corpus
+// row leaves HBM once
+struct IphTile { int m0, n0, lane, wave; };
+__device__ __forceinline__ IphTile iph_tile(int tiles_m, int nwg) {
+  IphTile t;
+  t.lane = threadIdx.x & 63;
+  t.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tile = xcd_remap(blockIdx.x, nwg);
-  const int m0 = (tile % tiles_m) * IPH_BM, n0 = (tile / tiles_m) * IPH_BN;
-  const int wr = wave >> 1, wc = wave & 1;
+  t.m0 = (tile % tiles_m) * IPH_BM;
+  t.n0 = (tile / tiles_m) * IPH_BN;
+  return t;
+}
 
-  f32x4 acc[4][4];
-  iph_main_loop(nq, nc, H, Q, Cp, m0, n0, smem, wave, lane, acc);
-
-  const int fr = lane & 15, fg = lane >> 4;
-  // lane holds query m = .. + fr, passages n = .. + fg * 4 .. + 3 of each 16 x 16 tile
+// store epilogue: lane holds query m = .. + fr, passages n = .. + fg * 4 .. + 3 of each 16 x 16 tile
+__device__ __forceinline__ void iph_store(const IphTile& t, int nq, int nc, const f32x4 (&acc)[4][4], float* __restrict__ S, long ldS) {
+  const int wr = t.wave >> 1, wc = t.wave & 1, fr = t.lane & 15, fg = t.lane >> 4;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wr * 64 + i * 16 + fr;
+    const int m = t.m0 + wr * 64 + i * 16 + fr;
     if (m >= nq) continue;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wc * 64 + j * 16 + fg * 4;
+      const int n = t.n0 + wc * 64 + j * 16 + fg * 4;
       float* dst = S + (long)m * ldS + n;
       if (n + 4 <= nc && (ldS & 3) == 0) {
         *reinterpret_cast<float4*>(dst) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
@@ -213,52 +241,46 @@ __global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, i
 
 // filter epilogue (see the header of this file for the rule and its precondition).  Survivors are rare once the running set is
 // warm -- about k * nc / rows_seen per query and chunk -- so a 16 x 16 tile is first tested with one wave-wide ballot.
-__global__ __launch_bounds__(256, 2) void ip_filter_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
-                                                               const f16_t* __restrict__ Cp, long long id0, int k,
-                                                               const float* __restrict__ run_s, const long long* __restrict__ run_i,
-                                                               float* __restrict__ cand_s, long long* __restrict__ cand_i, int cand_cap,
-                                                               int* __restrict__ cand_count, int tiles_m, int nwg) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile = xcd_remap(blockIdx.x, nwg);
-  const int m0 = (tile % tiles_m) * IPH_BM, n0 = (tile / tiles_m) * IPH_BN;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int fr = lane & 15, fg = lane >> 4;
-
-  // the running k-th entry of the lane's four query rows, loaded ahead of the main loop
+struct IphFilter {
   float thr[4];
   bool open[4];                                  // the row takes every score: its set is not full
   bool live[4];                                  // the row exists
+};
+// the running k-th entry of the lane's four query rows, loaded ahead of the main loop
+__device__ __forceinline__ IphFilter iph_filter_load(const IphTile& t, int nq, int k, const float* __restrict__ run_s,
+                                                     const long long* __restrict__ run_i) {
+  const int wr = t.wave >> 1, fr = t.lane & 15;
+  IphFilter f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wr * 64 + i * 16 + fr;
-    live[i] = m < nq;
-    thr[i] = 0.f;
-    open[i] = false;
-    if (live[i]) {
+    const int m = t.m0 + wr * 64 + i * 16 + fr;
+    f.live[i] = m < nq;
+    f.thr[i] = 0.f;
+    f.open[i] = false;
+    if (f.live[i]) {
       const long at = (long)m * k + (k - 1);
-      open[i] = run_i[at] < 0;
-      const float t = run_s[at];
-      thr[i] = __float_as_uint(t) == 0x80000000u ? -FLT_MIN : t;
+      f.open[i] = run_i[at] < 0;
+      const float v = run_s[at];
+      f.thr[i] = __float_as_uint(v) == 0x80000000u ? -FLT_MIN : v;
     }
   }
-
-  f32x4 acc[4][4];
-  iph_main_loop(nq, nc, H, Q, Cp, m0, n0, smem, wave, lane, acc);
-
+  return f;
+}
+__device__ __forceinline__ void iph_filter(const IphTile& t, const IphFilter& f, int nc, const f32x4 (&acc)[4][4], long long id0,
+                                           float* __restrict__ cand_s, long long* __restrict__ cand_i, int cand_cap,
+                                           int* __restrict__ cand_count) {
+  const int wr = t.wave >> 1, wc = t.wave & 1, fr = t.lane & 15, fg = t.lane >> 4;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wr * 64 + i * 16 + fr;
+    const int m = t.m0 + wr * 64 + i * 16 + fr;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wc * 64 + j * 16 + fg * 4;
+      const int n = t.n0 + wc * 64 + j * 16 + fg * 4;
       bool pass[4];
       bool any = false;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        pass[e] = live[i] && n + e < nc && (open[i] || !(acc[i][j][e] <= thr[i]));
+        pass[e] = f.live[i] && n + e < nc && (f.open[i] || !(acc[i][j][e] <= f.thr[i]));
         any = any || pass[e];
       }
       if (__ballot(any) == 0ull) continue;       // wave-uniform: no survivor in this 16 x 16 tile
@@ -273,6 +295,57 @@ __global__ __launch_bounds__(256, 2) void ip_filter_f16_kernel(int nq, int nc, i
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256, 2) void ip_scores_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
+                                                               const f16_t* __restrict__ Cp, float* __restrict__ S, long ldS,
+                                                               int tiles_m, int nwg) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
+  const IphTile t = iph_tile(tiles_m, nwg);
+  f32x4 acc[4][4];
+  iph_main_loop<false>(nq, nc, H, Q, nullptr, Cp, nullptr, t.m0, t.n0, smem, t.wave, t.lane, acc);
+  iph_store(t, nq, nc, acc, S, ldS);
+}
+
+__global__ __launch_bounds__(256, 2) void ip_filter_f16_kernel(int nq, int nc, int H, const f16_t* __restrict__ Q,
+                                                               const f16_t* __restrict__ Cp, long long id0, int k,
+                                                               const float* __restrict__ run_s, const long long* __restrict__ run_i,
+                                                               float* __restrict__ cand_s, long long* __restrict__ cand_i, int cand_cap,
+                                                               int* __restrict__ cand_count, int tiles_m, int nwg) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * IPH_TILE];
+  const IphTile t = iph_tile(tiles_m, nwg);
+  const IphFilter f = iph_filter_load(t, nq, k, run_s, run_i);
+  f32x4 acc[4][4];
+  iph_main_loop<false>(nq, nc, H, Q, nullptr, Cp, nullptr, t.m0, t.n0, smem, t.wave, t.lane, acc);
+  iph_filter(t, f, nc, acc, id0, cand_s, cand_i, cand_cap, cand_count);
+}
+
+// plane-pair storage: the same two kernels on the three-term loop.  Two stages of four tiles are 128 KB of (dynamic) LDS: one
+// workgroup per CU.
+#define IPP_LDS (8 * IPH_TILE)
+__global__ __launch_bounds__(256, 1) void ip_scores_planes_kernel(int nq, int nc, int H, const f16_t* __restrict__ Qh,
+                                                                  const f16_t* __restrict__ Ql, const f16_t* __restrict__ Ch,
+                                                                  const f16_t* __restrict__ Cl, float* __restrict__ S, long ldS,
+                                                                  int tiles_m, int nwg) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const IphTile t = iph_tile(tiles_m, nwg);
+  f32x4 acc[4][4];
+  iph_main_loop<true>(nq, nc, H, Qh, Ql, Ch, Cl, t.m0, t.n0, smem, t.wave, t.lane, acc);
+  iph_store(t, nq, nc, acc, S, ldS);
+}
+
+__global__ __launch_bounds__(256, 1) void ip_filter_planes_kernel(int nq, int nc, int H, const f16_t* __restrict__ Qh,
+                                                                  const f16_t* __restrict__ Ql, const f16_t* __restrict__ Ch,
+                                                                  const f16_t* __restrict__ Cl, long long id0, int k,
+                                                                  const float* __restrict__ run_s, const long long* __restrict__ run_i,
+                                                                  float* __restrict__ cand_s, long long* __restrict__ cand_i, int cand_cap,
+                                                                  int* __restrict__ cand_count, int tiles_m, int nwg) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const IphTile t = iph_tile(tiles_m, nwg);
+  const IphFilter f = iph_filter_load(t, nq, k, run_s, run_i);
+  f32x4 acc[4][4];
+  iph_main_loop<true>(nq, nc, H, Qh, Ql, Ch, Cl, t.m0, t.n0, smem, t.wave, t.lane, acc);
+  iph_filter(t, f, nc, acc, id0, cand_s, cand_i, cand_cap, cand_count);
 }
 
 // ---- top-k ------------------------------------------------------------------------------------------------------
@@ -310,7 +383,7 @@ __device__ void tk_sort(uint64_t* arr, int n) {
 }
 
 // cand_count == nullptr: m candidates per query, scores[q * ld + j] with ids[q * ld_ids + j] or id_base + j.
-// cand_count != nullptr: the lists of ip_filter_f16_kernel (ids explicit, ld = ld_ids = cand_cap = m): query q has
+// cand_count != nullptr: the lists of the filter kernels (ids explicit, ld = ld_ids = cand_cap = m): query q has
 // min(cand_count[q], m) entries; a count above m adds 1 to *overflow; the count is reset to 0.
 __global__ __launch_bounds__(256) void topk_stream_kernel(int m, const float* __restrict__ scores, long ld,
                                                           const long long* __restrict__ ids, long ld_ids, long long id_base,
@@ -380,37 +453,82 @@ extern "C" int simx_ip_scores(simx_stream_t stream, int nq, int nc, int H, const
   return SIMX_OK;
 }
 
-extern "C" int simx_ip_scores_f16(simx_stream_t stream, int nq, int nc, int H, const void* q16, const void* c16, float* scores, long ld) {
+// operands of the matrix-core kernels: binary16 matrices (lo == nullptr) or binary16 plane pairs (hi, lo)
+struct IphOperand { const f16_t *hi, *lo; };
+static bool iph_ok(const IphOperand& x, bool planes) { return x.hi && simx_al16(x.hi) && (!planes || (x.lo && simx_al16(x.lo))); }
+static IphOperand iph_rows(const IphOperand& x, long row0, int H) { return IphOperand{x.hi + row0 * H, x.lo ? x.lo + row0 * H : nullptr}; }
+
+// the dynamic-LDS limit of the plane-pair kernels (more than 64 KB), set once per device; false: it could not be set
+static bool ip_planes_device() {
+  static SimxLdsAttrs st;
+  static const SimxLdsAttr lds[] = {simx_lds(ip_scores_planes_kernel, IPP_LDS), simx_lds(ip_filter_planes_kernel, IPP_LDS)};
+  return simx_set_lds_attrs(st, lds, sizeof(lds) / sizeof(lds[0]));
+}
+
+// the score launcher of both matrix-core modes (`what` names the entry point in messages)
+static int ip_scores_h16(const char* what, bool planes, simx_stream_t stream, int nq, int nc, int H, IphOperand q, IphOperand c, float* scores,
+                         long ld) {
   hipStream_t s = (hipStream_t)stream;
-  SIMX_PROF(SIMX_K_TOPK, s, 2.0 * nq * nc * H);
-  SIMX_REQUIRE(nq > 0 && nc > 0 && H > 0 && H % 8 == 0 && ld >= nc, SIMX_ERR_BAD_SHAPE, "ip_scores_f16: bad shape nq=%d nc=%d H=%d ld=%ld", nq, nc, H, ld);
-  SIMX_REQUIRE(q16 && c16 && scores && simx_al16(q16) && simx_al16(c16) && simx_al16(scores), SIMX_ERR_BAD_SHAPE,
-               "ip_scores_f16: pointers must be non-NULL and 16-byte aligned");
+  SIMX_PROF(SIMX_K_TOPK, s, (planes ? 6.0 : 2.0) * nq * nc * H);
+  SIMX_REQUIRE(nq > 0 && nc > 0 && H > 0 && H % 8 == 0 && ld >= nc, SIMX_ERR_BAD_SHAPE, "%s: bad shape nq=%d nc=%d H=%d ld=%ld", what, nq, nc, H, ld);
+  SIMX_REQUIRE(iph_ok(q, planes) && iph_ok(c, planes) && scores && simx_al16(scores), SIMX_ERR_BAD_SHAPE,
+               "%s: pointers must be non-NULL and 16-byte aligned", what);
   const int tiles_m = cdiv(nq, IPH_BM), tiles_n = cdiv(nc, IPH_BN);
-  SIMX_REQUIRE((long)tiles_m * tiles_n <= 0x7FFFFFFFl, SIMX_ERR_BAD_SHAPE, "ip_scores_f16: too many tiles (nq=%d nc=%d)", nq, nc);
+  SIMX_REQUIRE((long)tiles_m * tiles_n <= 0x7FFFFFFFl, SIMX_ERR_BAD_SHAPE, "%s: too many tiles (nq=%d nc=%d)", what, nq, nc);
   const int nwg = tiles_m * tiles_n;
-  hipLaunchKernelGGL(ip_scores_f16_kernel, dim3(nwg), dim3(256), 0, s, nq, nc, H, (const f16_t*)q16, (const f16_t*)c16, scores, ld, tiles_m, nwg);
-  SIMX_CHECK_LAUNCH("ip_scores_f16");
+  SIMX_REQUIRE(!planes || ip_planes_device(), SIMX_ERR_HIP, "%s: the LDS limit of the plane kernels could not be set", what);
+  if (planes) hipLaunchKernelGGL(ip_scores_planes_kernel, dim3(nwg), dim3(256), IPP_LDS, s, nq, nc, H, q.hi, q.lo, c.hi, c.lo, scores, ld, tiles_m, nwg);
+  else hipLaunchKernelGGL(ip_scores_f16_kernel, dim3(nwg), dim3(256), 0, s, nq, nc, H, q.hi, c.hi, scores, ld, tiles_m, nwg);
+  SIMX_CHECK_LAUNCH(what);
   return SIMX_OK;
+}
+
+// the filter launcher of both matrix-core modes
+static int ip_filter_h16(const char* what, bool planes, simx_stream_t stream, int nq, int nc, int H, IphOperand q, IphOperand c, int64_t id0, int k,
+                         const float* run_scores, const int64_t* run_ids, float* cand_scores, int64_t* cand_ids, int cand_cap, int* cand_count) {
+  hipStream_t s = (hipStream_t)stream;
+  SIMX_PROF(SIMX_K_TOPK, s, (planes ? 6.0 : 2.0) * nq * nc * H);
+  SIMX_REQUIRE(nq > 0 && nc > 0 && H > 0 && H % 8 == 0, SIMX_ERR_BAD_SHAPE, "%s: bad shape nq=%d nc=%d H=%d", what, nq, nc, H);
+  SIMX_REQUIRE(k > 0 && k <= TK_KMAX && cand_cap > 0, SIMX_ERR_BAD_SHAPE, "%s: need 0 < k=%d <= %d and cand_cap=%d > 0", what, k, TK_KMAX, cand_cap);
+  SIMX_REQUIRE(iph_ok(q, planes) && iph_ok(c, planes), SIMX_ERR_BAD_SHAPE, "%s: the operands must be non-NULL and 16-byte aligned", what);
+  SIMX_REQUIRE(run_scores && run_ids && cand_scores && cand_ids && cand_count, SIMX_ERR_BAD_SHAPE, "%s: NULL argument", what);
+  SIMX_REQUIRE(id0 >= 0 && id0 + nc < 0xFFFFFFFFll, SIMX_ERR_BAD_SHAPE, "%s: ids must fit 32 bits", what);
+  const int tiles_m = cdiv(nq, IPH_BM), tiles_n = cdiv(nc, IPH_BN);
+  SIMX_REQUIRE((long)tiles_m * tiles_n <= 0x7FFFFFFFl, SIMX_ERR_BAD_SHAPE, "%s: too many tiles (nq=%d nc=%d)", what, nq, nc);
+  const int nwg = tiles_m * tiles_n;
+  SIMX_REQUIRE(!planes || ip_planes_device(), SIMX_ERR_HIP, "%s: the LDS limit of the plane kernels could not be set", what);
+  if (planes)
+    hipLaunchKernelGGL(ip_filter_planes_kernel, dim3(nwg), dim3(256), IPP_LDS, s, nq, nc, H, q.hi, q.lo, c.hi, c.lo, (long long)id0, k, run_scores,
+                       (const long long*)run_ids, cand_scores, (long long*)cand_ids, cand_cap, cand_count, tiles_m, nwg);
+  else
+    hipLaunchKernelGGL(ip_filter_f16_kernel, dim3(nwg), dim3(256), 0, s, nq, nc, H, q.hi, c.hi, (long long)id0, k, run_scores,
+                       (const long long*)run_ids, cand_scores, (long long*)cand_ids, cand_cap, cand_count, tiles_m, nwg);
+  SIMX_CHECK_LAUNCH(what);
+  return SIMX_OK;
+}
+
+extern "C" int simx_ip_scores_f16(simx_stream_t stream, int nq, int nc, int H, const void* q16, const void* c16, float* scores, long ld) {
+  return ip_scores_h16("ip_scores_f16", false, stream, nq, nc, H, IphOperand{(const f16_t*)q16, nullptr}, IphOperand{(const f16_t*)c16, nullptr}, scores, ld);
+}
+
+extern "C" int simx_ip_scores_planes(simx_stream_t stream, int nq, int nc, int H, const void* q_hi, const void* q_lo, const void* c_hi, const void* c_lo,
+                                     float* scores, long ld) {
+  return ip_scores_h16("ip_scores_planes", true, stream, nq, nc, H, IphOperand{(const f16_t*)q_hi, (const f16_t*)q_lo},
+                       IphOperand{(const f16_t*)c_hi, (const f16_t*)c_lo}, scores, ld);
 }
 
 extern "C" int simx_ip_filter_f16(simx_stream_t stream, int nq, int nc, int H, const void* q16, const void* c16, int64_t id0, int k,
                                   const float* run_scores, const int64_t* run_ids, float* cand_scores, int64_t* cand_ids, int cand_cap,
                                   int* cand_count) {
-  hipStream_t s = (hipStream_t)stream;
-  SIMX_PROF(SIMX_K_TOPK, s, 2.0 * nq * nc * H);
-  SIMX_REQUIRE(nq > 0 && nc > 0 && H > 0 && H % 8 == 0, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: bad shape nq=%d nc=%d H=%d", nq, nc, H);
-  SIMX_REQUIRE(k > 0 && k <= TK_KMAX && cand_cap > 0, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: need 0 < k=%d <= %d and cand_cap=%d > 0", k, TK_KMAX, cand_cap);
-  SIMX_REQUIRE(q16 && c16 && simx_al16(q16) && simx_al16(c16), SIMX_ERR_BAD_SHAPE, "ip_filter_f16: q16 / c16 must be non-NULL and 16-byte aligned");
-  SIMX_REQUIRE(run_scores && run_ids && cand_scores && cand_ids && cand_count, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: NULL argument");
-  SIMX_REQUIRE(id0 >= 0 && id0 + nc < 0xFFFFFFFFll, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: ids must fit 32 bits");
-  const int tiles_m = cdiv(nq, IPH_BM), tiles_n = cdiv(nc, IPH_BN);
-  SIMX_REQUIRE((long)tiles_m * tiles_n <= 0x7FFFFFFFl, SIMX_ERR_BAD_SHAPE, "ip_filter_f16: too many tiles (nq=%d nc=%d)", nq, nc);
-  const int nwg = tiles_m * tiles_n;
-  hipLaunchKernelGGL(ip_filter_f16_kernel, dim3(nwg), dim3(256), 0, s, nq, nc, H, (const f16_t*)q16, (const f16_t*)c16, (long long)id0, k,
-                     run_scores, (const long long*)run_ids, cand_scores, (long long*)cand_ids, cand_cap, cand_count, tiles_m, nwg);
-  SIMX_CHECK_LAUNCH("ip_filter_f16");
-  return SIMX_OK;
+  return ip_filter_h16("ip_filter_f16", false, stream, nq, nc, H, IphOperand{(const f16_t*)q16, nullptr}, IphOperand{(const f16_t*)c16, nullptr}, id0, k,
+                       run_scores, run_ids, cand_scores, cand_ids, cand_cap, cand_count);
+}
+
+extern "C" int simx_ip_filter_planes(simx_stream_t stream, int nq, int nc, int H, const void* q_hi, const void* q_lo, const void* c_hi, const void* c_lo,
+                                     int64_t id0, int k, const float* run_scores, const int64_t* run_ids, float* cand_scores, int64_t* cand_ids,
+                                     int cand_cap, int* cand_count) {
+  return ip_filter_h16("ip_filter_planes", true, stream, nq, nc, H, IphOperand{(const f16_t*)q_hi, (const f16_t*)q_lo},
+                       IphOperand{(const f16_t*)c_hi, (const f16_t*)c_lo}, id0, k, run_scores, run_ids, cand_scores, cand_ids, cand_cap, cand_count);
 }
 
 extern "C" int simx_topk_update(simx_stream_t stream, int nq, int m, const float* scores, long ld, const int64_t* ids, long ld_ids,
@@ -444,19 +562,22 @@ __global__ void topk_init_kernel(long n, float* s, long long* i) {
 
 extern "C" size_t simx_flat_ip_workspace_bytes(int nq, int chunk) { return (size_t)nq * (size_t)((chunk + 3) & ~3) * sizeof(float); }
 
-// index.search over a float32 (f16 == false) or binary16 shard: the chunk walk is the same, the score kernel differs
-static int flat_ip_search(const char* what, bool f16, simx_stream_t stream, int nq, long nc, int H, const void* q, const void* corpus,
-                          int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_ids) {
+// index.search over a shard in one of the three storage modes: the chunk walk is the same, the score kernel differs
+enum IpMode { IP_F32, IP_F16, IP_PLANES };
+static int flat_ip_search(const char* what, IpMode mode, simx_stream_t stream, int nq, long nc, int H, const void* q, const void* q_lo,
+                          const void* corpus, const void* corpus_lo, int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
+                          float* out_scores, int64_t* out_ids) {
   hipStream_t s = (hipStream_t)stream;
   SIMX_REQUIRE(nq > 0 && nc >= 0 && chunk > 0, SIMX_ERR_BAD_SHAPE, "%s: bad shape", what);
   SIMX_REQUIRE(workspace_bytes >= simx_flat_ip_workspace_bytes(nq, chunk), SIMX_ERR_WORKSPACE, "%s: workspace too small", what);
   const long ld = (chunk + 3) & ~3;
+  const IphOperand q16{(const f16_t*)q, (const f16_t*)q_lo}, c16{(const f16_t*)corpus, (const f16_t*)corpus_lo};
   hipLaunchKernelGGL(topk_init_kernel, dim3(cdiv((int)((long)nq * k), 256)), dim3(256), 0, s, (long)nq * k, out_scores, (long long*)out_ids);
   SIMX_CHECK_LAUNCH("topk_init");
   for (long c0 = 0; c0 < nc; c0 += chunk) {
     const int m = (int)((nc - c0) < chunk ? (nc - c0) : chunk);
-    int rc = f16 ? simx_ip_scores_f16(stream, nq, m, H, q, (const f16_t*)corpus + c0 * H, (float*)workspace, ld)
-                 : simx_ip_scores(stream, nq, m, H, (const float*)q, (const float*)corpus + c0 * H, (float*)workspace, ld);
+    int rc = mode == IP_F32 ? simx_ip_scores(stream, nq, m, H, (const float*)q, (const float*)corpus + c0 * H, (float*)workspace, ld)
+                            : ip_scores_h16(what, mode == IP_PLANES, stream, nq, m, H, q16, iph_rows(c16, c0, H), (float*)workspace, ld);
     if (rc) return rc;
     rc = simx_topk_update(stream, nq, m, (const float*)workspace, ld, nullptr, 0, id_base + c0, k, out_scores, out_ids);
     if (rc) return rc;
@@ -467,17 +588,25 @@ static int flat_ip_search(const char* what, bool f16, simx_stream_t stream, int 
 extern "C" int simx_flat_ip_search(simx_stream_t stream, int nq, long nc, int H, const float* q, const float* corpus,
                                    int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
                                    float* out_scores, int64_t* out_ids) {
-  return flat_ip_search("flat_ip_search", false, stream, nq, nc, H, q, corpus, id_base, k, chunk, workspace, workspace_bytes, out_scores, out_ids);
+  return flat_ip_search("flat_ip_search", IP_F32, stream, nq, nc, H, q, nullptr, corpus, nullptr, id_base, k, chunk, workspace, workspace_bytes,
+                        out_scores, out_ids);
 }
 
 extern "C" int simx_flat_ip_search_f16(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
                                        int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
                                        float* out_scores, int64_t* out_ids) {
-  return flat_ip_search("flat_ip_search_f16", true, stream, nq, nc, H, q16, corpus16, id_base, k, chunk, workspace, workspace_bytes, out_scores,
-                        out_ids);
+  return flat_ip_search("flat_ip_search_f16", IP_F16, stream, nq, nc, H, q16, nullptr, corpus16, nullptr, id_base, k, chunk, workspace,
+                        workspace_bytes, out_scores, out_ids);
 }
 
-// ---- one-pass float16 search: seed pass unfused, then filter + fold per chunk -------------------------------------------
+extern "C" int simx_flat_ip_search_planes(simx_stream_t stream, int nq, long nc, int H, const void* q_hi, const void* q_lo, const void* corpus_hi,
+                                          const void* corpus_lo, int64_t id_base, int k, int chunk, void* workspace, size_t workspace_bytes,
+                                          float* out_scores, int64_t* out_ids) {
+  return flat_ip_search("flat_ip_search_planes", IP_PLANES, stream, nq, nc, H, q_hi, q_lo, corpus_hi, corpus_lo, id_base, k, chunk, workspace,
+                        workspace_bytes, out_scores, out_ids);
+}
+
+// ---- one-pass matrix-core search: seed pass unfused, then filter + fold per chunk -------------------------------------------
 // workspace: [seed scores nq x ld][cand_scores nq x cap][cand_ids nq x cap][cand_count nq][overflow word], each part 16-byte aligned
 struct FusedWs { size_t ld, cand_s, cand_i, count, ovf, total; };
 static FusedWs fused_ws(int nq, int seed_rows, int cand_cap) {
@@ -499,20 +628,19 @@ extern "C" size_t simx_flat_ip_fused_workspace_bytes(int nq, int seed_rows, int 
 
 __global__ void fused_overflow_out_kernel(const int* __restrict__ word, int* __restrict__ out) { *out = *word; }
 
-extern "C" int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
-                                             int64_t id_base, int k, int chunk, int seed_rows, int cand_cap, void* workspace,
-                                             size_t workspace_bytes, float* out_scores, int64_t* out_ids, int* overflow) {
+// the one schedule of both matrix-core modes: seed pass, growing chunks, fold, overflow word
+static int flat_ip_search_fused(const char* what, bool planes, simx_stream_t stream, int nq, long nc, int H, IphOperand q, IphOperand corpus,
+                                int64_t id_base, int k, int chunk, int seed_rows, int cand_cap, void* workspace, size_t workspace_bytes,
+                                float* out_scores, int64_t* out_ids, int* overflow) {
   hipStream_t s = (hipStream_t)stream;
   SIMX_REQUIRE(nq > 0 && nc >= 0 && chunk > 0 && seed_rows > 0 && cand_cap > 0, SIMX_ERR_BAD_SHAPE,
-               "flat_ip_search_f16_fused: bad shape nq=%d nc=%ld chunk=%d seed_rows=%d cand_cap=%d", nq, nc, chunk, seed_rows, cand_cap);
-  SIMX_REQUIRE(H > 0 && H % 8 == 0 && k > 0 && k <= TK_KMAX, SIMX_ERR_BAD_SHAPE, "flat_ip_search_f16_fused: need H=%d %% 8 == 0 and 0 < k=%d <= %d", H, k,
-               TK_KMAX);
-  SIMX_REQUIRE(q16 && simx_al16(q16) && (nc == 0 || (corpus16 && simx_al16(corpus16))) && workspace && simx_al16(workspace), SIMX_ERR_BAD_SHAPE,
-               "flat_ip_search_f16_fused: q16 / corpus16 / workspace must be non-NULL and 16-byte aligned");
-  SIMX_REQUIRE(out_scores && out_ids && overflow, SIMX_ERR_BAD_SHAPE, "flat_ip_search_f16_fused: NULL output");
-  SIMX_REQUIRE(id_base >= 0 && id_base + nc < 0xFFFFFFFFll, SIMX_ERR_BAD_SHAPE, "flat_ip_search_f16_fused: ids must fit 32 bits");
-  SIMX_REQUIRE(workspace_bytes >= simx_flat_ip_fused_workspace_bytes(nq, seed_rows, cand_cap), SIMX_ERR_WORKSPACE,
-               "flat_ip_search_f16_fused: workspace too small");
+               "%s: bad shape nq=%d nc=%ld chunk=%d seed_rows=%d cand_cap=%d", what, nq, nc, chunk, seed_rows, cand_cap);
+  SIMX_REQUIRE(H > 0 && H % 8 == 0 && k > 0 && k <= TK_KMAX, SIMX_ERR_BAD_SHAPE, "%s: need H=%d %% 8 == 0 and 0 < k=%d <= %d", what, H, k, TK_KMAX);
+  SIMX_REQUIRE(iph_ok(q, planes) && (nc == 0 || iph_ok(corpus, planes)) && workspace && simx_al16(workspace), SIMX_ERR_BAD_SHAPE,
+               "%s: queries / corpus / workspace must be non-NULL and 16-byte aligned", what);
+  SIMX_REQUIRE(out_scores && out_ids && overflow, SIMX_ERR_BAD_SHAPE, "%s: NULL output", what);
+  SIMX_REQUIRE(id_base >= 0 && id_base + nc < 0xFFFFFFFFll, SIMX_ERR_BAD_SHAPE, "%s: ids must fit 32 bits", what);
+  SIMX_REQUIRE(workspace_bytes >= simx_flat_ip_fused_workspace_bytes(nq, seed_rows, cand_cap), SIMX_ERR_WORKSPACE, "%s: workspace too small", what);
   const FusedWs w = fused_ws(nq, seed_rows, cand_cap);
   char* base = (char*)workspace;
   float* seed_s = (float*)base;
@@ -520,17 +648,16 @@ extern "C" int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long 
   int64_t* cand_i = (int64_t*)(base + w.cand_i);
   int* count = (int*)(base + w.count);
   int* ovf = (int*)(base + w.ovf);
-  const f16_t* corpus = (const f16_t*)corpus16;
   hipLaunchKernelGGL(topk_init_kernel, dim3(cdiv((int)((long)nq * k), 256)), dim3(256), 0, s, (long)nq * k, out_scores, (long long*)out_ids);
   SIMX_CHECK_LAUNCH("topk_init");
   if (hipMemsetAsync(count, 0, w.total - w.count, s) != hipSuccess) {          // the counts and the overflow word
-    simx_set_error("flat_ip_search_f16_fused: hipMemsetAsync failed");
+    simx_set_error("%s: hipMemsetAsync failed", what);
     return SIMX_ERR_HIP;
   }
   // with an empty running set every score survives: the first seed_rows rows take the unfused pass
   long seen = nc < seed_rows ? nc : seed_rows;
   if (seen > 0) {
-    int rc = simx_ip_scores_f16(stream, nq, (int)seen, H, q16, corpus, seed_s, (long)w.ld);
+    int rc = ip_scores_h16(what, planes, stream, nq, (int)seen, H, q, corpus, seed_s, (long)w.ld);
     if (rc) return rc;
     rc = simx_topk_update(stream, nq, (int)seen, seed_s, (long)w.ld, nullptr, 0, id_base, k, out_scores, out_ids);
     if (rc) return rc;
@@ -540,7 +667,8 @@ extern "C" int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long 
     long m = nc - seen;
     if (m > seen) m = seen;
     if (m > chunk) m = chunk;
-    int rc = simx_ip_filter_f16(stream, nq, (int)m, H, q16, corpus + seen * H, id_base + seen, k, out_scores, out_ids, cand_s, cand_i, cand_cap, count);
+    int rc = ip_filter_h16(what, planes, stream, nq, (int)m, H, q, iph_rows(corpus, seen, H), id_base + seen, k, out_scores, out_ids, cand_s, cand_i,
+                           cand_cap, count);
     if (rc) return rc;
     rc = simx_topk_fold_lists(stream, nq, cand_s, cand_i, cand_cap, count, k, out_scores, out_ids, ovf);
     if (rc) return rc;
@@ -549,4 +677,21 @@ extern "C" int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long 
   hipLaunchKernelGGL(fused_overflow_out_kernel, dim3(1), dim3(1), 0, s, ovf, overflow);
   SIMX_CHECK_LAUNCH("fused_overflow_out");
   return SIMX_OK;
+}
+
+extern "C" int simx_flat_ip_search_f16_fused(simx_stream_t stream, int nq, long nc, int H, const void* q16, const void* corpus16,
+                                             int64_t id_base, int k, int chunk, int seed_rows, int cand_cap, void* workspace,
+                                             size_t workspace_bytes, float* out_scores, int64_t* out_ids, int* overflow) {
+  return flat_ip_search_fused("flat_ip_search_f16_fused", false, stream, nq, nc, H, IphOperand{(const f16_t*)q16, nullptr},
+                              IphOperand{(const f16_t*)corpus16, nullptr}, id_base, k, chunk, seed_rows, cand_cap, workspace, workspace_bytes, out_scores,
+                              out_ids, overflow);
+}
+
+extern "C" int simx_flat_ip_search_planes_fused(simx_stream_t stream, int nq, long nc, int H, const void* q_hi, const void* q_lo,
+                                                const void* corpus_hi, const void* corpus_lo, int64_t id_base, int k, int chunk, int seed_rows,
+                                                int cand_cap, void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_ids,
+                                                int* overflow) {
+  return flat_ip_search_fused("flat_ip_search_planes_fused", true, stream, nq, nc, H, IphOperand{(const f16_t*)q_hi, (const f16_t*)q_lo},
+                              IphOperand{(const f16_t*)corpus_hi, (const f16_t*)corpus_lo}, id_base, k, chunk, seed_rows, cand_cap, workspace,
+                              workspace_bytes, out_scores, out_ids, overflow);
 }

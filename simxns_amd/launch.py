@@ -107,12 +107,17 @@ def main(argv=None):
     ap.add_argument("--index_float16", "--index-float16", dest="index_float16", action="store_true",
                     help="pass --index_float16 to the generate jobs: binary16 index storage scored on the matrix cores (the reference's "
                          "co.useFloat16, which its NQ / TQ generate job sets).  Off by default in every recipe")
+    ap.add_argument("--index_planes", "--index-planes", dest="index_planes", action="store_true",
+                    help="pass --index_planes to the generate jobs: the float32 rows held as binary16 plane pairs, float32-grade scores "
+                         "from the matrix cores.  Not with --index_float16.  Off by default in every recipe")
     ap.add_argument("--index_fused", "--index-fused", dest="index_fused", action="store_true",
-                    help="with --index_float16: pass --index_fused to the generate jobs, the one-pass float16 search that filters the scores "
-                         "in the score kernel (experimental).  Off by default in every recipe")
+                    help="with --index_float16 or --index_planes: pass --index_fused to the generate jobs, the one-pass search that filters "
+                         "the scores in the score kernel (experimental).  Off by default in every recipe")
     args, extra = ap.parse_known_args(argv)
-    if args.index_fused and not args.index_float16:
-        ap.error("--index_fused needs --index_float16: the one-pass search exists for the binary16 index only")
+    if args.index_float16 and args.index_planes:
+        ap.error("--index_float16 and --index_planes exclude each other: an index has one storage mode")
+    if args.index_fused and not (args.index_float16 or args.index_planes):
+        ap.error("--index_fused needs --index_float16 or --index_planes: the one-pass search exists for the two matrix-core index modes only")
     extra = [e for e in extra if e != "--"]
     r = RECIPES[args.recipe]()
     if args.fold_accumulation:
@@ -128,7 +133,8 @@ def main(argv=None):
         jobs = [job_argv(script, dict(flags, global_step=global_step, **loop), args.nproc, args.port) + extra]
         if r["generate"] is not None:
             script, flags = r["generate"]
-            jobs.append(job_argv(script, dict(flags, global_step=global_step + step, index_float16=args.index_float16, index_fused=args.index_fused,
+            jobs.append(job_argv(script, dict(flags, global_step=global_step + step, index_float16=args.index_float16, index_planes=args.index_planes,
+                                             index_fused=args.index_fused,
                                              **loop),
                                  args.nproc, args.port))
         elif os.environ.get("SIMX_GENERATE_CMD"):

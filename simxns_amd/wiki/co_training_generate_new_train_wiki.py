@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from ..co_training.co_training_generate import embed_table, tokenize_table
-from ..retrieval import FlatIPIndex
+from ..retrieval import FlatIPIndex, index_storage
 from ..utils.dpr_utils import Eval_Tool, SimpleTokenizer, get_model_obj, has_answer
 from ..utils.util import is_first_worker
 
@@ -114,13 +114,12 @@ def read_train_pos(ground_truth_path):
 
 class RenewTools(object):
     def __init__(self, passages_path, tokenizer, output_dir, temp_dir=None, max_seq_length=128, rank=0, world=1,
-                 index_float16=False, index_fused=False):
+                 index_float16=False, index_fused=False, index_planes=False):
         """Reads the whole passage file (texts are needed for the answer match and the output), tokenises only this rank's
         contiguous slice (title, text pairs as TextCollator :38-52).  ``index_float16``: the reference's
         ``co.useFloat16 = True`` (:324), FlatIPIndex(storage="fp16"); off unless asked for."""
-        if index_fused and not index_float16:
-            raise ValueError("index_fused (FlatIPIndex(fused=True), the one-pass float16 search) needs index_float16")
-        self.index_float16, self.index_fused = bool(index_float16), bool(index_fused)
+        self.index_storage = index_storage(index_float16, index_planes, index_fused)     # refuses both modes, or fused with neither
+        self.index_float16, self.index_planes, self.index_fused = bool(index_float16), bool(index_planes), bool(index_fused)
         self.passages = load_passage(passages_path)
         self.tokenizer, self.output_dir, self.temp_dir = tokenizer, output_dir, temp_dir
         if is_first_worker():
@@ -137,7 +136,7 @@ class RenewTools(object):
         """this rank's shard of the exact inner-product index (:311-337); ids are positions in the passage file."""
         emb = embed_table(get_model_obj(model).body_emb, self.passage_table, device)
         index = FlatIPIndex(emb.shape[1] if emb.numel() else 768, id_base=self.slice[0],
-                            storage="fp16" if self.index_float16 else "fp32", fused=self.index_fused)
+                            storage=self.index_storage, fused=self.index_fused)
         if emb.numel():
             index.add(emb)
         return index

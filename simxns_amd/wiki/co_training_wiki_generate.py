@@ -16,6 +16,7 @@ from simxns_amd.model.models import BiBertEncoder                               
 from simxns_amd.utils.MARCO_until_new import HashTokenizer                                    # noqa: E402
 from simxns_amd.utils.dpr_utils import get_model_obj, load_states_from_checkpoint             # noqa: E402
 from simxns_amd.utils.util import is_first_worker                                             # noqa: E402
+from simxns_amd.retrieval import index_storage                                                # noqa: E402
 from simxns_amd.wiki.co_training_generate_new_train_wiki import RenewTools                    # noqa: E402
 
 logger = logging.getLogger("__main__")
@@ -52,13 +53,16 @@ def get_new_dataset(args, model, global_step, renew_tools):
 
 def get_arguments(argv=None):
     """the train job's flags plus --index_float16 (binary16 index storage, the reference's co.useFloat16; default off) and,
-    with it, --index_fused (its one-pass search; experimental, default off)."""
+    --index_planes (binary16 plane pairs of the float32 rows, float32-grade scores from the matrix cores; default off, not with
+    --index_float16) and, with either, --index_fused (the one-pass search; experimental, default off)."""
     argv = list(sys.argv[1:] if argv is None else argv)
-    index_float16, index_fused = "--index_float16" in argv, "--index_fused" in argv
-    if index_fused and not index_float16:
-        raise SystemExit("--index_fused needs --index_float16: the one-pass search exists for the binary16 index only")
-    args = M.get_arguments([a for a in argv if a not in ("--index_float16", "--index_fused")])
-    args.index_float16, args.index_fused = index_float16, index_fused
+    index_float16, index_planes, index_fused = "--index_float16" in argv, "--index_planes" in argv, "--index_fused" in argv
+    try:
+        index_storage(index_float16, index_planes, index_fused)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    args = M.get_arguments([a for a in argv if a not in ("--index_float16", "--index_planes", "--index_fused")])
+    args.index_float16, args.index_planes, args.index_fused = index_float16, index_planes, index_fused
     return args
 
 
@@ -71,7 +75,7 @@ def main(argv=None):
     renew_tools = RenewTools(passages_path=args.passage_path, tokenizer=tokenizer, output_dir=args.ann_dir,
                              temp_dir=os.path.join(args.ann_dir, 'temp'), max_seq_length=args.max_seq_length, rank=args.rank,
                              world=args.world_size, index_float16=args.index_float16,
-                             index_fused=args.index_fused)
+                             index_fused=args.index_fused, index_planes=args.index_planes)
     if args.world_size > 1:
         dist.barrier()
     if args.global_step <= args.max_steps:

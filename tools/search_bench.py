@@ -1,9 +1,11 @@
 """Micro-benchmark of the generate job's search on one GPU (not part of bench.py's metric): inner-product scores + exact
 top-k over a corpus shard resident in HBM, timed for the index storages on the same corpus in one process -- float32 (one
-fmaf chain per score, VALU), float16 (binary16 rows, matrix cores) and float16 fused (the one-pass search; its searches alternate with
-the unfused float16 ones) -- one JSON record each, then their ratios, then the kernels of one default-size chunk (all queries x 65536
-rows) timed apart by device events: the unfused pair, and the fused pair at the warm running set of a search's last chunk.
-usage: python tools/search_bench.py [nq nc k] [--out FILE]"""
+fmaf chain per score, VALU), planes and planes fused (binary16 plane pairs of the float32 rows, three MFMA terms; their searches
+alternate with the float32 ones, which are their baseline), float16 (binary16 rows, matrix cores) and float16 fused (the one-pass
+search; its searches alternate with the unfused float16 ones) -- one JSON record each, then their ratios, then the kernels of one
+default-size chunk (all queries x 65536 rows) timed apart by device events: the unfused kernels, and the fused pairs at the warm
+running set of a search's last chunk.
+usage: python tools/search_bench.py [nq nc k] [--out FILE] [--planes-out FILE]"""
 import json
 import subprocess
 import sys
@@ -13,13 +15,18 @@ import torch
 
 sys.path.insert(0, ".")
 from simxns_amd import _lib as L                  # noqa: E402
-from simxns_amd.retrieval import FlatIPIndex      # noqa: E402
+from simxns_amd.retrieval import FlatIPIndex, split_planes      # noqa: E402
 
 argv = sys.argv[1:]
 out_path = None
 if "--out" in argv:
     i = argv.index("--out")
     out_path = argv[i + 1]
+    del argv[i:i + 2]
+planes_out_path = None
+if "--planes-out" in argv:
+    i = argv.index("--planes-out")
+    planes_out_path = argv[i + 1]
     del argv[i:i + 2]
 nq, nc, k = (int(a) for a in argv[:3]) if len(argv) >= 3 else (2048, 1000000, 200)
 H = 768
@@ -55,7 +62,7 @@ def run(indexes, repeats=3):
         rate = 2.0 * nq * nc * H / dt
         rec = {"storage": index.storage, "fused": index.fused, "nq": nq, "nc": nc, "k": k, "H": H, "seconds": round(dt, 4),
                "seconds_all": [round(t, 4) for t in ts], "queries_per_s": round(nq / dt, 1), "tflops": round(rate / 1e12, 2),
-               "index_gb": round(nc * H * (2 if index.storage == "fp16" else 4) / 1e9, 3),
+               "index_gb": round(nc * H * (2 if index.storage == "fp16" else 4) / 1e9, 3),      # planes: two binary16 planes
                "full_msmarco_train_job_s_per_gpu_of_8": round(502939 * 8841823 / 8 * H * 2 / rate, 1)}
         if index.fused:
             rec["last_search_fallbacks"] = fb                                   # summed over the timed searches
@@ -86,6 +93,7 @@ def split(chunk=65536):
     c = parts[0][:m] if parts[0].shape[0] >= m else torch.cat(parts, 0)[:m]
     m = c.shape[0]
     q16, c16 = q.half(), c.half()
+    qp, cp = split_planes(q), split_planes(c.contiguous())
     S = torch.empty(nq, m, device=dev)
     D = torch.full((nq, k), float("-inf"), device=dev)
     I = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
@@ -104,16 +112,20 @@ def split(chunk=65536):
 
     t32 = ms(lambda: L.call("simx_ip_scores", sp, nq, m, H, L.ptr(q), L.ptr(c), L.ptr(S), m), 3)
     t16 = ms(lambda: L.call("simx_ip_scores_f16", sp, nq, m, H, L.ptr(q16), L.ptr(c16), L.ptr(S), m), 10)
+    tpl = ms(lambda: L.call("simx_ip_scores_planes", sp, nq, m, H, L.ptr(qp[0]), L.ptr(qp[1]), L.ptr(cp[0]), L.ptr(cp[1]), L.ptr(S), m), 10)
     ttk = ms(lambda: L.call("simx_topk_update", sp, nq, m, L.ptr(S), m, None, 0, 0, k, L.ptr(D), L.ptr(I)), 10)
     fl = 2.0 * nq * m * H
     fused = {}
-    if nc > m:
-        head = FlatIPIndex(H, storage="fp16")
+    for storage in (("fp16", "planes") if nc > m else ()):
+        head = FlatIPIndex(H, storage=storage)
         allrows = torch.cat(parts, 0)
         head.add(allrows[:nc - m])
         D0, I0 = head.search(q, k)
-        c16 = allrows[nc - m:].half()
-        del head, allrows
+        tail = allrows[nc - m:].contiguous()
+        qo, co = ((q16,), (tail.half(),)) if storage == "fp16" else (qp, split_planes(tail))
+        operands = [L.ptr(t) for t in qo + co]
+        name = "ip_filter_f16" if storage == "fp16" else "ip_filter_planes"
+        del head, allrows, tail
         cap = 4096
         cs = torch.empty(nq, cap, device=dev)
         ci = torch.empty(nq, cap, dtype=torch.int64, device=dev)
@@ -123,7 +135,7 @@ def split(chunk=65536):
 
         def filt():
             cnt.zero_()
-            L.call("simx_ip_filter_f16", sp, nq, m, H, L.ptr(q16), L.ptr(c16), nc - m, k, L.ptr(D0), L.ptr(I0), L.ptr(cs), L.ptr(ci), cap, L.ptr(cnt))
+            L.call("simx_" + name, sp, nq, m, H, *operands, nc - m, k, L.ptr(D0), L.ptr(I0), L.ptr(cs), L.ptr(ci), cap, L.ptr(cnt))
 
         def restore():
             D.copy_(D0); I.copy_(I0); cnt.copy_(cnt0)
@@ -137,13 +149,18 @@ def split(chunk=65536):
         tz = ms(cnt.zero_, 10)
         tfo = ms(fold, 10)
         tre = ms(restore, 10)
-        fused = {"fused_chunk_rows_seen_before": nc - m, "ip_filter_f16_ms": round(tfi - tz, 3), "ip_filter_f16_tflops": round(fl / (tfi - tz) / 1e9, 1),
-                 "count_zero_ms_subtracted": round(tz, 4), "topk_fold_lists_ms": round(tfo - tre, 3), "restore_ms_subtracted": round(tre, 4),
-                 "survivors_per_query_mean": round(cnt0.float().mean().item(), 2), "survivors_per_query_max": int(cnt0.max().item()),
-                 "fold_overflows": int(ovf.item())}
+        one = {"fused_chunk_rows_seen_before": nc - m, name + "_ms": round(tfi - tz, 3), name + "_tflops": round(fl / (tfi - tz) / 1e9, 1),
+               "count_zero_ms_subtracted": round(tz, 4), "topk_fold_lists_ms": round(tfo - tre, 3), "restore_ms_subtracted": round(tre, 4),
+               "survivors_per_query_mean": round(cnt0.float().mean().item(), 2), "survivors_per_query_max": int(cnt0.max().item()),
+               "fold_overflows": int(ovf.item())}
+        if storage == "fp16":
+            fused.update(one)
+        else:                                         # tflops of the planes kernels count 2 nq m H, the work of the product they stand for
+            fused["planes"] = one
     return {"chunk": [nq, m, H], **fused, "ip_scores_f16_ms": round(t16, 3), "ip_scores_f16_tflops": round(fl / t16 / 1e9, 1),
             "ip_scores_f16_store_tb_s": round(nq * m * 4 / t16 / 1e9, 3), "ip_scores_f32_ms": round(t32, 3),
-            "ip_scores_f32_tflops": round(fl / t32 / 1e9, 1), "topk_update_ms": round(ttk, 3), "topk_read_tb_s": round(nq * m * 4 / ttk / 1e9, 3)}
+            "ip_scores_f32_tflops": round(fl / t32 / 1e9, 1), "ip_scores_planes_ms": round(tpl, 3),
+            "ip_scores_planes_tflops": round(fl / tpl / 1e9, 1), "topk_update_ms": round(ttk, 3), "topk_read_tb_s": round(nq * m * 4 / ttk / 1e9, 3)}
 
 
 def commit():
@@ -153,12 +170,19 @@ def commit():
         return None
 
 
+def same_result(a, b):
+    """do two indexes return the same bits for the benchmark's queries?"""
+    (Da, Ia), (Db, Ib) = a.search(q, k), b.search(q, k)
+    return bool((Ia == Ib).all().item() and (Da.view(torch.int32) == Db.view(torch.int32)).all().item())
+
+
 f16, fus = make_index("fp16"), make_index("fp16", fused=True)
-D16, I16 = f16.search(q, k)
-Dfu, Ifu = fus.search(q, k)
-same = bool((I16 == Ifu).all().item() and (D16.view(torch.int32) == Dfu.view(torch.int32)).all().item())
-del D16, I16, Dfu, Ifu
-records = run([make_index("fp32")]) + run([f16, fus])
+same = same_result(f16, fus)
+pl, plf = make_index("planes"), make_index("planes", fused=True)
+same_planes = same_result(pl, plf)
+r32 = run([make_index("fp32"), pl, plf])              # the float32 baseline of the planes rows is timed between them
+del pl, plf
+records = r32[:1] + run([f16, fus]) + r32[1:]
 del f16, fus
 for r in records:
     print(json.dumps(r))
@@ -166,11 +190,16 @@ summary = {"fp32_seconds": records[0]["seconds"], "fp16_seconds": records[1]["se
            "fp16_speedup": round(records[0]["seconds"] / records[1]["seconds"], 2),
            "fused_speedup_over_fp16": round(records[1]["seconds"] / records[2]["seconds"], 2),
            "fused_result_equals_fp16_bit_for_bit": same, "last_search_fallbacks": records[2]["last_search_fallbacks"],
+           "planes_seconds": records[3]["seconds"], "planes_fused_seconds": records[4]["seconds"],
+           "planes_speedup_over_fp32": round(records[0]["seconds"] / records[3]["seconds"], 2),
+           "planes_fused_speedup_over_fp32": round(records[0]["seconds"] / records[4]["seconds"], 2),
+           "planes_fused_result_equals_planes_bit_for_bit": same_planes, "planes_last_search_fallbacks": records[4]["last_search_fallbacks"],
            "sclk": clock_mhz(), "commit": commit(), "device": torch.cuda.get_device_name(0)}
 print(json.dumps(summary))
 per_chunk = split()
 print(json.dumps(per_chunk))
-if out_path:
-    with open(out_path, "w") as f:
-        json.dump({"records": records, "summary": summary, "per_chunk": per_chunk}, f, indent=1)
-        f.write("\n")
+for path, recs in ((out_path, records), (planes_out_path, [records[0], records[3], records[4]])):
+    if path:
+        with open(path, "w") as f:
+            json.dump({"records": recs, "summary": summary, "per_chunk": per_chunk}, f, indent=1)
+            f.write("\n")
