@@ -71,19 +71,9 @@ __device__ __forceinline__ void af_store_t_planes(const f32x16 (&o)[2], float mu
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float a = f32_pin(o[dt][4 * g] * mul), b = f32_pin(o[dt][4 * g + 1] * mul), c = f32_pin(o[dt][4 * g + 2] * mul), d = f32_pin(o[dt][4 * g + 3] * mul);
-      const uint32_t h0 = H16<F>::pack2(a, b), h1 = H16<F>::pack2(c, d);
-      const uint32_t l0 = H16<F>::pack2(a - H16<F>::lo(h0), b - H16<F>::hi(h0)), l1 = H16<F>::pack2(c - H16<F>::lo(h1), d - H16<F>::hi(h1));
-      bf16_t* q = dst + dt * 32 + 8 * g + 4 * half;
-      *reinterpret_cast<uint2*>(q) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(q + ps) = make_uint2(l0, l1);
+      const float v[4] = {o[dt][4 * g] * mul, o[dt][4 * g + 1] * mul, o[dt][4 * g + 2] * mul, o[dt][4 * g + 3] * mul};
+      plane_st4<F>(dst + dt * 32 + 8 * g + 4 * half, ps, v);
     }
-}
-// 4 consecutive values hi + lo of an fp16 plane pair
-__device__ __forceinline__ float4 af_ld4_planes(const bf16_t* __restrict__ p, long ps) {
-  const uint2 h = *reinterpret_cast<const uint2*>(p), l = *reinterpret_cast<const uint2*>(p + ps);
-  return make_float4(H16<f16_t>::lo(h.x) + H16<f16_t>::lo(l.x), H16<f16_t>::hi(h.x) + H16<f16_t>::hi(l.x),
-                     H16<f16_t>::lo(h.y) + H16<f16_t>::lo(l.y), H16<f16_t>::hi(h.y) + H16<f16_t>::hi(l.y));
 }
 
 // ------------------------------------------------------------------------------------------ forward
@@ -220,7 +210,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dq_f32_kernel(const float* __rest
       const float4* po = reinterpret_cast<const float4*>(Og + (long)qc * H + 32 * half);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const float4 v = PL ? af_ld4_planes(Opl + (long)qc * H + 32 * half + 4 * i, ops) : po[i];
+        const float4 v = PL ? plane_ld4<f16_t>(Opl + (long)qc * H + 32 * half + 4 * i, ops) : po[i];
         delta += dr[4 * i] * v.x + dr[4 * i + 1] * v.y + dr[4 * i + 2] * v.z + dr[4 * i + 3] * v.w;
       }
     }
@@ -296,7 +286,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dkv_f32_kernel(const float* __res
       const float4* pd = reinterpret_cast<const float4*>(dOg + (long)r * H);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const float4 a = PL ? af_ld4_planes(Opl + (long)r * H + 4 * i, ops) : po[i], b = pd[i];
+        const float4 a = PL ? plane_ld4<f16_t>(Opl + (long)r * H + 4 * i, ops) : po[i], b = pd[i];
         del += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
       }
       l = lse[(long)h * T + t0 + r] * AF_LOG2E;
@@ -503,7 +493,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_f32_long_kernel(const float
     const float4* po = reinterpret_cast<const float4*>(Og + (long)qcl * H + 32 * half);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const float4 v = PL ? af_ld4_planes(Opl + (long)qcl * H + 32 * half + 4 * i, ops) : po[i];
+      const float4 v = PL ? plane_ld4<f16_t>(Opl + (long)qcl * H + 32 * half + 4 * i, ops) : po[i];
       delta += dr[4 * i] * v.x + dr[4 * i + 1] * v.y + dr[4 * i + 2] * v.z + dr[4 * i + 3] * v.w;
     }
   }
@@ -598,7 +588,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_f32_long_kernel(const floa
         const float4* pd = reinterpret_cast<const float4*>(dOg + (long)(q0 + r) * H);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const float4 a = PL ? af_ld4_planes(Opl + (long)(q0 + r) * H + 4 * i, ops) : po[i], b = pd[i];
+          const float4 a = PL ? plane_ld4<f16_t>(Opl + (long)(q0 + r) * H + 4 * i, ops) : po[i], b = pd[i];
           del += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
         }
         l = lse[(long)h * T + t0 + q0 + r] * AF_LOG2E;

@@ -20,8 +20,6 @@
 #include "common.h"
 #include "prof.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 #define X3_LOG2E 1.4426950408889634f
 
 __device__ __forceinline__ int x3a_f(int row) {
@@ -35,30 +33,11 @@ __device__ __forceinline__ void x3a_stage(const bf16_t* __restrict__ G, long ld,
     const int r = i * 8 + (lane >> 3);
     const int c = (lane & 7) ^ x3a_f(r);
     const int gr = r < len ? r : len - 1;
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(G + (long)gr * ld + c * 8), (lds_ptr_t)(lds + i * 1024), 16, 0, 0);
+    glds16(G + (long)gr * ld + c * 8, lds + i * 1024);
   }
 }
 __device__ __forceinline__ bf16x8 x3a_row_frag(const char* tile, int row, int c16) {
   return *reinterpret_cast<const bf16x8*>(tile + x3a_off(row, c16));
-}
-__device__ __forceinline__ f32x4 x3a_mfma(const bf16x8& a, const bf16x8& b, const f32x4& c) { return H16<f16_t>::mfma(a, b, c); }
-// acc += (ah + al) . (bh + bl) without the lo.lo term, corrections first
-__device__ __forceinline__ f32x4 x3a_mfma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4 c) {
-  c = x3a_mfma(al, bh, c);
-  c = x3a_mfma(ah, bl, c);
-  return x3a_mfma(ah, bh, c);
-}
-// fp16 pair of 8 f32 values (two accumulator quads) in fragment order
-__device__ __forceinline__ void x3a_split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float ar = f32_pin(a[r]), br = f32_pin(b[r]);
-    const f16_t ha = (f16_t)ar, hb = (f16_t)br;
-    hi[r] = __builtin_bit_cast(short, ha);
-    hi[4 + r] = __builtin_bit_cast(short, hb);
-    lo[r] = __builtin_bit_cast(short, (f16_t)(ar - (float)ha));
-    lo[4 + r] = __builtin_bit_cast(short, (f16_t)(br - (float)hb));
-  }
 }
 #define X3A_RDTR(DST, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=&v"(DST) : "v"(ADDR) : "memory")
 #define X3A_CAT(LO, HI) ((bf16x8){LO[0], LO[1], LO[2], LO[3], HI[0], HI[1], HI[2], HI[3]})
@@ -119,8 +98,8 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_kernel(const bf16_t* __rest
     for (int kt = 0; kt < NKT; ++kt) {
       if (ALLT || kt < nkt) {
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        a = x3a_mfma3(x3a_row_frag(sKh, kt * 16 + fr, fg), x3a_row_frag(sKl, kt * 16 + fr, fg), qh[0], ql[0], a);
-        a = x3a_mfma3(x3a_row_frag(sKh, kt * 16 + fr, 4 + fg), x3a_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[1], ql[1], a);
+        a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, fg), x3a_row_frag(sKl, kt * 16 + fr, fg), qh[0], ql[0], a);
+        a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, 4 + fg), x3a_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[1], ql[1], a);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = kt * 16 + 4 * fg + r;
@@ -172,22 +151,19 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_kernel(const bf16_t* __rest
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
         bf16x8 ph, pl;
-        x3a_split8(s[2 * kb], s[2 * kb + 1], ph, pl);
-        o[0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, o[0]);
-        o[1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, o[1]);
-        o[2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, o[2]);
-        o[3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, o[3]);
+        plane_split_frag<f16_t>(s[2 * kb], s[2 * kb + 1], ph, pl);
+        o[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, o[0]);
+        o[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, o[1]);
+        o[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, o[2]);
+        o[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, o[3]);
       }
     }
     if (q < len) {
       bf16_t* dst = ctx + (long)(t0 + q) * H + h * 64 + 4 * fg;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        const float v0 = f32_pin(o[dt][0] * inv), v1 = f32_pin(o[dt][1] * inv), v2 = f32_pin(o[dt][2] * inv), v3 = f32_pin(o[dt][3] * inv);
-        const uint32_t h0 = pack2h(v0, v1), h1 = pack2h(v2, v3);
-        const uint32_t l0 = pack2h(v0 - H16<f16_t>::lo(h0), v1 - H16<f16_t>::hi(h0)), l1 = pack2h(v2 - H16<f16_t>::lo(h1), v3 - H16<f16_t>::hi(h1));
-        *reinterpret_cast<uint2*>(dst + dt * 16) = make_uint2(h0, h1);
-        *reinterpret_cast<uint2*>(dst + cps + dt * 16) = make_uint2(l0, l1);
+        const float v[4] = {o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv};
+        plane_st4<f16_t>(dst + dt * 16, cps, v);
       }
       if (fg == 0) lse[(long)h * T + t0 + q] = m * scale + (logf(sum) - 10.0f * 0.69314718055994531f);
     }
@@ -220,26 +196,6 @@ __device__ __forceinline__ float x3a_block_absmax(const float* __restrict__ dOg,
   __syncthreads();
   return r;
 }
-// 8 consecutive values hi + lo of an fp16 plane pair
-__device__ __forceinline__ void x3a_ld8_planes(const bf16_t* __restrict__ p, long ps, float (&v)[8]) {
-  const uint4 h = *reinterpret_cast<const uint4*>(p), l = *reinterpret_cast<const uint4*>(p + ps);
-  const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[2 * e] = H16<f16_t>::lo(hw[e]) + H16<f16_t>::lo(lw[e]);
-    v[2 * e + 1] = H16<f16_t>::hi(hw[e]) + H16<f16_t>::hi(lw[e]);
-  }
-}
-// fp16 pair fragment of 8 f32 values
-__device__ __forceinline__ void x3a_split_frag(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float ve = f32_pin(v[e]);
-    const f16_t h = (f16_t)ve;
-    hi[e] = __builtin_bit_cast(short, h);
-    lo[e] = __builtin_bit_cast(short, (f16_t)(ve - (float)h));
-  }
-}
 // a wave's 16 x 64 accumulator tile (lane = row fr, 4 columns dt * 16 + 4 fg) x mul as a bf16 plane pair, rows < nrows
 __device__ __forceinline__ void x3a_store_planes_bf16(const f32x4 (&acc)[4], float mul, bf16_t* __restrict__ dst, long ld, long ps, int nrows, int lane) {
   const int fr = lane & 15, fg = lane >> 4;
@@ -247,11 +203,8 @@ __device__ __forceinline__ void x3a_store_planes_bf16(const f32x4 (&acc)[4], flo
   bf16_t* d = dst + (long)fr * ld + 4 * fg;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
-    const float v0 = f32_pin(acc[dt][0] * mul), v1 = f32_pin(acc[dt][1] * mul), v2 = f32_pin(acc[dt][2] * mul), v3 = f32_pin(acc[dt][3] * mul);
-    const uint32_t h0 = pack2bf(v0, v1), h1 = pack2bf(v2, v3);
-    const uint32_t l0 = pack2bf(v0 - H16<bf16_t>::lo(h0), v1 - H16<bf16_t>::hi(h0)), l1 = pack2bf(v2 - H16<bf16_t>::lo(h1), v3 - H16<bf16_t>::hi(h1));
-    *reinterpret_cast<uint2*>(d + dt * 16) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(d + ps + dt * 16) = make_uint2(l0, l1);
+    const float v[4] = {acc[dt][0] * mul, acc[dt][1] * mul, acc[dt][2] * mul, acc[dt][3] * mul};
+    plane_st4<bf16_t>(d + dt * 16, ps, v);
   }
 }
 
@@ -336,12 +289,12 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_kernel(const bf16_t* __r
       const float4 a = pd[0], b = pd[1], c = pd[8], e = pd[9];
       d0[0] = a.x * sc; d0[1] = a.y * sc; d0[2] = a.z * sc; d0[3] = a.w * sc; d0[4] = b.x * sc; d0[5] = b.y * sc; d0[6] = b.z * sc; d0[7] = b.w * sc;
       d1[0] = c.x * sc; d1[1] = c.y * sc; d1[2] = c.z * sc; d1[3] = c.w * sc; d1[4] = e.x * sc; d1[5] = e.y * sc; d1[6] = e.z * sc; d1[7] = e.w * sc;
-      x3a_ld8_planes(Og + (long)qc * H + fg * 8, ops, o0);
-      x3a_ld8_planes(Og + (long)qc * H + 32 + fg * 8, ops, o1);
+      plane_ld8<f16_t>(Og + (long)qc * H + fg * 8, ops, o0);
+      plane_ld8<f16_t>(Og + (long)qc * H + 32 + fg * 8, ops, o1);
 #pragma unroll
       for (int i = 0; i < 8; ++i) delta += d0[i] * o0[i] + d1[i] * o1[i];
-      x3a_split_frag(d0, dh0, dl0);
-      x3a_split_frag(d1, dh1, dl1);
+      plane_split_frag<f16_t>(d0, dh0, dl0);
+      plane_split_frag<f16_t>(d1, dh1, dl1);
     }
     delta += __shfl_xor(delta, 16, 64);
     delta += __shfl_xor(delta, 32, 64);
@@ -364,10 +317,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_kernel(const bf16_t* __r
       for (int hf = 0; hf < 2; ++hf) {
         const int kt = 2 * kp + hf;
         f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-        s = x3a_mfma3(kh[hf][0], kl[hf][0], qh0, ql0, s);
-        s = x3a_mfma3(kh[hf][1], kl[hf][1], qh1, ql1, s);
-        dp = x3a_mfma3(vh[hf][0], vl[hf][0], dh0, dl0, dp);
-        dp = x3a_mfma3(vh[hf][1], vl[hf][1], dh1, dl1, dp);
+        s = plane_mfma3<f16_t>(kh[hf][0], kl[hf][0], qh0, ql0, s);
+        s = plane_mfma3<f16_t>(kh[hf][1], kl[hf][1], qh1, ql1, s);
+        dp = plane_mfma3<f16_t>(vh[hf][0], vl[hf][0], dh0, dl0, dp);
+        dp = plane_mfma3<f16_t>(vh[hf][1], vl[hf][1], dh1, dl1, dp);
         float m4[4] = {1.f, 1.f, 1.f, 1.f};
         if (DROP) drop_mult4(drop, (uint32_t)(h * T + t0 + q), (uint32_t)(kt * 16 + 4 * fg), m4);
 #pragma unroll
@@ -385,11 +338,11 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_kernel(const bf16_t* __r
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                    "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
       bf16x8 sh, sl;
-      x3a_split8(ds[0], ds[1], sh, sl);
-      dq[0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dq[0]);
-      dq[1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dq[1]);
-      dq[2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dq[2]);
-      dq[3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dq[3]);
+      plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
+      dq[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dq[0]);
+      dq[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dq[1]);
+      dq[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dq[2]);
+      dq[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dq[3]);
     }
     x3a_store_planes_bf16(dq, isc, dqkv + (long)(t0 + qt * 16) * H3 + h * 64, H3, dps, len - qt * 16, lane);
 #pragma unroll
@@ -448,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
     const float4* pd = reinterpret_cast<const float4*>(dOg + (long)gr * H + c * 8);
     const float4 a = pd[0], b = pd[1];
     d[0] = a.x * sc; d[1] = a.y * sc; d[2] = a.z * sc; d[3] = a.w * sc; d[4] = b.x * sc; d[5] = b.y * sc; d[6] = b.z * sc; d[7] = b.w * sc;
-    x3a_ld8_planes(Og + (long)gr * H + c * 8, ops, o);
+    plane_ld8<f16_t>(Og + (long)gr * H + c * 8, ops, o);
     float del = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) del += d[i] * o[i];
@@ -456,7 +409,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
     del += __shfl_xor(del, 2, 64);
     del += __shfl_xor(del, 4, 64);
     bf16x8 fh, fl;
-    x3a_split_frag(d, fh, fl);
+    plane_split_frag<f16_t>(d, fh, fl);
     *reinterpret_cast<bf16x8*>(sDh + x3a_off(r, c)) = fh;
     *reinterpret_cast<bf16x8*>(sDl + x3a_off(r, c)) = fl;
     if (c == 0) {
@@ -530,10 +483,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
       for (int hf = 0; hf < 2; ++hf) {
         const int qt = 2 * qp + hf;
         f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-        s = x3a_mfma3(qhf[hf][0], qlf[hf][0], kh0, kl0, s);
-        s = x3a_mfma3(qhf[hf][1], qlf[hf][1], kh1, kl1, s);
-        dp = x3a_mfma3(dhf[hf][0], dlf[hf][0], vh0, vl0, dp);
-        dp = x3a_mfma3(dhf[hf][1], dlf[hf][1], vh1, vl1, dp);
+        s = plane_mfma3<f16_t>(qhf[hf][0], qlf[hf][0], kh0, kl0, s);
+        s = plane_mfma3<f16_t>(qhf[hf][1], qlf[hf][1], kh1, kl1, s);
+        dp = plane_mfma3<f16_t>(dhf[hf][0], dlf[hf][0], vh0, vl0, dp);
+        dp = plane_mfma3<f16_t>(dhf[hf][1], dlf[hf][1], vh1, vl1, dp);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qrow = qt * 16 + 4 * fg + r;
@@ -546,8 +499,8 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
         }
       }
       bf16x8 ph, pl, sh, sl;
-      x3a_split8(pp[0], pp[1], ph, pl);
-      x3a_split8(ds[0], ds[1], sh, sl);
+      plane_split_frag<f16_t>(pp[0], pp[1], ph, pl);
+      plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
       {
         bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
         X3A_RDTR(h0l, bdh + tr[0], 0); X3A_RDTR(h0h, bdh + tr[0], 2048); X3A_RDTR(h1l, bdh + tr[1], 0); X3A_RDTR(h1h, bdh + tr[1], 2048);
@@ -556,10 +509,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
         X3A_RDTR(l2l, bdl + tr[2], 0); X3A_RDTR(l2h, bdl + tr[2], 2048); X3A_RDTR(l3l, bdl + tr[3], 0); X3A_RDTR(l3h, bdl + tr[3], 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
-        dv[0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, dv[0]);
-        dv[1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, dv[1]);
-        dv[2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, dv[2]);
-        dv[3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, dv[3]);
+        dv[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, dv[0]);
+        dv[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, dv[1]);
+        dv[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, dv[2]);
+        dv[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, dv[3]);
       }
       {
         bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
@@ -569,10 +522,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
         X3A_RDTR(l2l, bql + tr[2], 0); X3A_RDTR(l2h, bql + tr[2], 2048); X3A_RDTR(l3l, bql + tr[3], 0); X3A_RDTR(l3h, bql + tr[3], 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
-        dk[0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dk[0]);
-        dk[1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dk[1]);
-        dk[2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dk[2]);
-        dk[3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dk[3]);
+        dk[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dk[0]);
+        dk[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dk[1]);
+        dk[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dk[2]);
+        dk[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dk[3]);
       }
     }
     bf16_t* dst = dqkv + (long)(t0 + kt * 16) * H3 + H + h * 64;
@@ -672,8 +625,8 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* _
         for (int kt = 0; kt < 8; ++kt) {
           if (ALLT || kt < nkt) {
             f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            a = x3a_mfma3(x3a_row_frag(sKh, kt * 16 + fr, fg), x3a_row_frag(sKl, kt * 16 + fr, fg), qh[j][0], ql[j][0], a);
-            a = x3a_mfma3(x3a_row_frag(sKh, kt * 16 + fr, 4 + fg), x3a_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[j][1], ql[j][1], a);
+            a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, fg), x3a_row_frag(sKl, kt * 16 + fr, fg), qh[j][0], ql[j][0], a);
+            a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, 4 + fg), x3a_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[j][1], ql[j][1], a);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               if (!ALLT) a[r] = k0 + kt * 16 + 4 * fg + r < len ? a[r] : -INFINITY;
@@ -728,11 +681,11 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* _
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                          "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
             bf16x8 ph, pl;
-            x3a_split8(s[2 * kb], s[2 * kb + 1], ph, pl);
-            o[j][0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, o[j][0]);
-            o[j][1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, o[j][1]);
-            o[j][2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, o[j][2]);
-            o[j][3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, o[j][3]);
+            plane_split_frag<f16_t>(s[2 * kb], s[2 * kb + 1], ph, pl);
+            o[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, o[j][0]);
+            o[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, o[j][1]);
+            o[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, o[j][2]);
+            o[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, o[j][3]);
           }
         }
       }
@@ -747,11 +700,8 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* _
       bf16_t* dst = ctx + (long)(t0 + q) * H + h * 64 + 4 * fg;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        const float v0 = f32_pin(o[j][dt][0] * inv), v1 = f32_pin(o[j][dt][1] * inv), v2 = f32_pin(o[j][dt][2] * inv), v3 = f32_pin(o[j][dt][3] * inv);
-        const uint32_t h0 = pack2h(v0, v1), h1 = pack2h(v2, v3);
-        const uint32_t l0 = pack2h(v0 - H16<f16_t>::lo(h0), v1 - H16<f16_t>::hi(h0)), l1 = pack2h(v2 - H16<f16_t>::lo(h1), v3 - H16<f16_t>::hi(h1));
-        *reinterpret_cast<uint2*>(dst + dt * 16) = make_uint2(h0, h1);
-        *reinterpret_cast<uint2*>(dst + cps + dt * 16) = make_uint2(l0, l1);
+        const float v[4] = {o[j][dt][0] * inv, o[j][dt][1] * inv, o[j][dt][2] * inv, o[j][dt][3] * inv};
+        plane_st4<f16_t>(dst + dt * 16, cps, v);
       }
       if (fg == 0) lse[(long)h * T + t0 + q] = mrun[j] * scale + (logf(lrun[j]) - 10.0f * 0.69314718055994531f);
     }
@@ -807,13 +757,13 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
     const float4 a = pd[0], b = pd[1], c = pd[8], e = pd[9];
     d0[0] = a.x * sc; d0[1] = a.y * sc; d0[2] = a.z * sc; d0[3] = a.w * sc; d0[4] = b.x * sc; d0[5] = b.y * sc; d0[6] = b.z * sc; d0[7] = b.w * sc;
     d1[0] = c.x * sc; d1[1] = c.y * sc; d1[2] = c.z * sc; d1[3] = c.w * sc; d1[4] = e.x * sc; d1[5] = e.y * sc; d1[6] = e.z * sc; d1[7] = e.w * sc;
-    x3a_ld8_planes(Og + (long)qcl * H + fg * 8, ops, o0);
-    x3a_ld8_planes(Og + (long)qcl * H + 32 + fg * 8, ops, o1);
+    plane_ld8<f16_t>(Og + (long)qcl * H + fg * 8, ops, o0);
+    plane_ld8<f16_t>(Og + (long)qcl * H + 32 + fg * 8, ops, o1);
     float del = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) del += d0[i] * o0[i] + d1[i] * o1[i];
-    x3a_split_frag(d0, dh[j][0], dl[j][0]);
-    x3a_split_frag(d1, dh[j][1], dl[j][1]);
+    plane_split_frag<f16_t>(d0, dh[j][0], dl[j][0]);
+    plane_split_frag<f16_t>(d1, dh[j][1], dl[j][1]);
     del += __shfl_xor(del, 16, 64);
     del += __shfl_xor(del, 32, 64);
     delta[j] = del;
@@ -851,10 +801,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
         for (int hf = 0; hf < 2; ++hf) {
           const int kt = 2 * kp + hf;
           f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-          s = x3a_mfma3(kh[hf][0], kl[hf][0], qh[j][0], ql[j][0], s);
-          s = x3a_mfma3(kh[hf][1], kl[hf][1], qh[j][1], ql[j][1], s);
-          dp = x3a_mfma3(vh[hf][0], vl[hf][0], dh[j][0], dl[j][0], dp);
-          dp = x3a_mfma3(vh[hf][1], vl[hf][1], dh[j][1], dl[j][1], dp);
+          s = plane_mfma3<f16_t>(kh[hf][0], kl[hf][0], qh[j][0], ql[j][0], s);
+          s = plane_mfma3<f16_t>(kh[hf][1], kl[hf][1], qh[j][1], ql[j][1], s);
+          dp = plane_mfma3<f16_t>(vh[hf][0], vl[hf][0], dh[j][0], dl[j][0], dp);
+          dp = plane_mfma3<f16_t>(vh[hf][1], vl[hf][1], dh[j][1], dl[j][1], dp);
           float m4[4] = {1.f, 1.f, 1.f, 1.f};
           if (DROP) drop_mult4(drop, (uint32_t)(h * T + t0 + q), (uint32_t)(k0 + kt * 16 + 4 * fg), m4);
 #pragma unroll
@@ -872,11 +822,11 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
         bf16x8 sh, sl;
-        x3a_split8(ds[0], ds[1], sh, sl);
-        dq[j][0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dq[j][0]);
-        dq[j][1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dq[j][1]);
-        dq[j][2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dq[j][2]);
-        dq[j][3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dq[j][3]);
+        plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
+        dq[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dq[j][0]);
+        dq[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dq[j][1]);
+        dq[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dq[j][2]);
+        dq[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dq[j][3]);
       }
     }
   }
@@ -953,7 +903,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
       const float4* pd = reinterpret_cast<const float4*>(dOg + (long)gr * H + c * 8);
       const float4 a = pd[0], b = pd[1];
       d[0] = a.x * sc; d[1] = a.y * sc; d[2] = a.z * sc; d[3] = a.w * sc; d[4] = b.x * sc; d[5] = b.y * sc; d[6] = b.z * sc; d[7] = b.w * sc;
-      x3a_ld8_planes(Og + (long)gr * H + c * 8, ops, o);
+      plane_ld8<f16_t>(Og + (long)gr * H + c * 8, ops, o);
       float del = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) del += d[i] * o[i];
@@ -961,7 +911,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
       del += __shfl_xor(del, 2, 64);
       del += __shfl_xor(del, 4, 64);
       bf16x8 fh, fl;
-      x3a_split_frag(d, fh, fl);
+      plane_split_frag<f16_t>(d, fh, fl);
       *reinterpret_cast<bf16x8*>(sDh + x3a_off(r, c)) = fh;
       *reinterpret_cast<bf16x8*>(sDl + x3a_off(r, c)) = fl;
       if (c == 0) {
@@ -1025,10 +975,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
         for (int hf = 0; hf < 2; ++hf) {
           const int qt = 2 * qp + hf;
           f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-          s = x3a_mfma3(qhf[hf][0], qlf[hf][0], kh0, kl0, s);
-          s = x3a_mfma3(qhf[hf][1], qlf[hf][1], kh1, kl1, s);
-          dp = x3a_mfma3(dhf[hf][0], dlf[hf][0], vh0, vl0, dp);
-          dp = x3a_mfma3(dhf[hf][1], dlf[hf][1], vh1, vl1, dp);
+          s = plane_mfma3<f16_t>(qhf[hf][0], qlf[hf][0], kh0, kl0, s);
+          s = plane_mfma3<f16_t>(qhf[hf][1], qlf[hf][1], kh1, kl1, s);
+          dp = plane_mfma3<f16_t>(dhf[hf][0], dlf[hf][0], vh0, vl0, dp);
+          dp = plane_mfma3<f16_t>(dhf[hf][1], dlf[hf][1], vh1, vl1, dp);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int qrow = qt * 16 + 4 * fg + r;
@@ -1041,8 +991,8 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
           }
         }
         bf16x8 ph, pl, sh, sl;
-        x3a_split8(pp[0], pp[1], ph, pl);
-        x3a_split8(ds[0], ds[1], sh, sl);
+        plane_split_frag<f16_t>(pp[0], pp[1], ph, pl);
+        plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
         {
           bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
           X3A_RDTR(h0l, bdh + tr[0], 0); X3A_RDTR(h0h, bdh + tr[0], 2048); X3A_RDTR(h1l, bdh + tr[1], 0); X3A_RDTR(h1h, bdh + tr[1], 2048);
@@ -1051,10 +1001,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
           X3A_RDTR(l2l, bdl + tr[2], 0); X3A_RDTR(l2h, bdl + tr[2], 2048); X3A_RDTR(l3l, bdl + tr[3], 0); X3A_RDTR(l3h, bdl + tr[3], 2048);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                        "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
-          dv[j][0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, dv[j][0]);
-          dv[j][1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, dv[j][1]);
-          dv[j][2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, dv[j][2]);
-          dv[j][3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, dv[j][3]);
+          dv[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, dv[j][0]);
+          dv[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, dv[j][1]);
+          dv[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, dv[j][2]);
+          dv[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, dv[j][3]);
         }
         {
           bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
@@ -1064,10 +1014,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
           X3A_RDTR(l2l, bql + tr[2], 0); X3A_RDTR(l2h, bql + tr[2], 2048); X3A_RDTR(l3l, bql + tr[3], 0); X3A_RDTR(l3h, bql + tr[3], 2048);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                        "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
-          dk[j][0] = x3a_mfma3(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dk[j][0]);
-          dk[j][1] = x3a_mfma3(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dk[j][1]);
-          dk[j][2] = x3a_mfma3(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dk[j][2]);
-          dk[j][3] = x3a_mfma3(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dk[j][3]);
+          dk[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dk[j][0]);
+          dk[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dk[j][1]);
+          dk[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dk[j][2]);
+          dk[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dk[j][3]);
         }
       }
     }

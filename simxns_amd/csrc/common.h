@@ -98,6 +98,83 @@ template <> struct H16<f16_t> {
 // split shared a basic block: three rows in 10^4 wrong at 5e-5).  Every split goes through this.
 __device__ __forceinline__ float f32_pin(float x) { asm("" : "+v"(x)); return x; }
 
+// ---- plane pairs ("operand planes", simx.h / DESIGN.md 3): an f32 value x travels as two 16-bit values of format F,
+//     hi = rnd16(x),  lo = rnd16(x - hi)  (the subtraction in f32),     x ~= hi + lo  (the join, in f32),
+// hi at p, lo at p + ps elements (ps = the plane stride).  These helpers are the only statement of that rule on the device;
+// every producer and consumer calls them.  The pin is INSIDE the split so that no caller can hand it an unrounded product
+// (callers that scale first pass `o * inv` as it is): see f32_pin above for what happens otherwise.
+template <typename F>
+__device__ __forceinline__ uint32_t plane_lo2(float a, float b, uint32_t hi) {   // (for the splits below: a, b pinned, hi = pack2(a, b))
+  return H16<F>::pack2(a - H16<F>::lo(hi), b - H16<F>::hi(hi));
+}
+template <typename F>
+__device__ __forceinline__ void plane_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
+  a = f32_pin(a); b = f32_pin(b);
+  hi = H16<F>::pack2(a, b);
+  lo = plane_lo2<F>(a, b, hi);
+}
+// (four values: all pins, then both hi words, then both lo words -- the order the producers' stores were scheduled in)
+template <typename F>
+__device__ __forceinline__ void plane_split4(const float (&v)[4], uint2& hi, uint2& lo) {
+  const float o[4] = {f32_pin(v[0]), f32_pin(v[1]), f32_pin(v[2]), f32_pin(v[3])};
+  hi = make_uint2(H16<F>::pack2(o[0], o[1]), H16<F>::pack2(o[2], o[3]));
+  lo = make_uint2(plane_lo2<F>(o[0], o[1], hi.x), plane_lo2<F>(o[2], o[3], hi.y));
+}
+// split 4 consecutive values and store them: 8 B per plane (p and p + ps 8-byte aligned)
+template <typename F>
+__device__ __forceinline__ void plane_st4(bf16_t* p, long ps, const float (&v)[4]) {
+  uint2 hi, lo;
+  plane_split4<F>(v, hi, lo);
+  *reinterpret_cast<uint2*>(p) = hi;
+  *reinterpret_cast<uint2*>(p + ps) = lo;
+}
+// the join hi + lo of 4 / 8 consecutive values (8 / 16 B per plane, so aligned)
+template <typename F>
+__device__ __forceinline__ float4 plane_ld4(const bf16_t* __restrict__ p, long ps) {
+  const uint2 h = *reinterpret_cast<const uint2*>(p), l = *reinterpret_cast<const uint2*>(p + ps);
+  return make_float4(H16<F>::lo(h.x) + H16<F>::lo(l.x), H16<F>::hi(h.x) + H16<F>::hi(l.x),
+                     H16<F>::lo(h.y) + H16<F>::lo(l.y), H16<F>::hi(h.y) + H16<F>::hi(l.y));
+}
+template <typename F>
+__device__ __forceinline__ void plane_ld8(const bf16_t* __restrict__ p, long ps, float (&v)[8]) {
+  const uint4 h = *reinterpret_cast<const uint4*>(p), l = *reinterpret_cast<const uint4*>(p + ps);
+  const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[2 * e] = H16<F>::lo(hw[e]) + H16<F>::lo(lw[e]);
+    v[2 * e + 1] = H16<F>::hi(hw[e]) + H16<F>::hi(lw[e]);
+  }
+}
+// MFMA fragment pair of 8 values in fragment order (v[0..7], or two accumulator quads a then b): the same rule element by element
+// (H16::bits rounds one value as pack2 rounds each of its two), elements r and 4 + r per step -- the order in which the attention
+// kernels split their P / dS quads, and the one the schedule of mha_fwd_x3_kernel was tuned with
+template <typename F>
+__device__ __forceinline__ void plane_split_frag(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float x = f32_pin(v[r]), y = f32_pin(v[4 + r]);
+    const short hx = H16<F>::bits(x), hy = H16<F>::bits(y);
+    hi[r] = hx;
+    hi[4 + r] = hy;
+    lo[r] = H16<F>::bits(x - H16<F>::one(hx));
+    lo[4 + r] = H16<F>::bits(y - H16<F>::one(hy));
+  }
+}
+template <typename F>
+__device__ __forceinline__ void plane_split_frag(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
+  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  plane_split_frag<F>(v, hi, lo);
+}
+// returns c + (xh + xl) . (yh + yl) without the lo.lo term (below the f32 round-off of the sum), corrections first.  The order of the
+// three terms into an accumulator is part of the result's bits: loops that interleave terms differently (the hand-scheduled
+// plane GEMMs, the retrieval scorer) keep their own.
+template <typename F>
+__device__ __forceinline__ f32x4 plane_mfma3(const bf16x8& xh, const bf16x8& xl, const bf16x8& yh, const bf16x8& yl, f32x4 c) {
+  c = H16<F>::mfma(xl, yh, c);
+  c = H16<F>::mfma(xh, yl, c);
+  return H16<F>::mfma(xh, yh, c);
+}
+
 // ---- stream correction in ONE byte per element (simx.h stream_lo): x = hi + (b - 128) * ulp(hi) / 256, ulp(hi) = the
 // spacing of the 16-bit format at hi's exponent.  |x - hi| <= ulp / 2, so b lands in [0, 256]: clamped to [1, 255] (at most
 // 1/256 ulp lost at the two ends).  The stream then carries 11 + 8 = 19 significand bits in fp16 (8 + 8 = 16 in bf16) at 3 B
@@ -358,6 +435,20 @@ __device__ __forceinline__ void erf_and_gauss(float u, float& erf_x, float& gaus
   p = fmaf(p, t, -0.284496736f);
   p = fmaf(p, t, 0.254829592f);
   erf_x = copysignf(1.0f - p * t * gauss, u);
+}
+
+// ---- XCD-aware tile id: block b runs on XCD b%8 (observed placement, speed only); give every XCD a contiguous range of
+// logical tiles.  Bijective for any grid size.
+__device__ __forceinline__ int xcd_remap(int b, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = b & 7, loc = b >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
+// ---- LDS-DMA: 16 B per lane from global memory straight into LDS (lane l lands at lds_wave_base + 16 l)
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+__device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)lds_wave_base, 16, 0, 0);
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

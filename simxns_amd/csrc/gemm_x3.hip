@@ -27,13 +27,6 @@
 #include "common.h"
 #include "prof.h"
 
-template <typename F>
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  a = f32_pin(a); b = f32_pin(b);
-  hi = H16<F>::pack2(a, b);
-  lo = H16<F>::pack2(a - H16<F>::lo(hi), b - H16<F>::hi(hi));
-}
-
 #define X3_BM 128
 #define X3_BN 128
 #define X3_BK 32
@@ -53,8 +46,7 @@ __global__ __launch_bounds__(256, 3) void gemm_x3_nt_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // XCD-aware order: block b runs on XCD b % 8; every XCD walks a contiguous range of tiles so that the N-tiles sharing an
   // A panel (and all tiles sharing B) sit behind one L2
-  const int q8 = ntiles >> 3, r8 = ntiles & 7, xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int tile = xcd_remap(blockIdx.x, ntiles);
   const int m0 = (tile / tiles_n) * X3_BM, n0 = (tile % tiles_n) * X3_BN;
   const int wr = wave >> 1, wc = wave & 1;
   const int fr = lane & 15, fg = lane >> 4;
@@ -97,10 +89,10 @@ __global__ __launch_bounds__(256, 3) void gemm_x3_nt_kernel(
       const int row = srow + 32 * e;
       char* d = stage + row * 64 + (((((tid & 7) >> 1) ^ (((row >> 3) & 1) << 1))) << 4) + (tid & 1) * 8;
       uint32_t h0, h1, l0, l1;
-      split2<F>(ra[e].x, ra[e].y, h0, l0); split2<F>(ra[e].z, ra[e].w, h1, l1);
+      plane_split2<F>(ra[e].x, ra[e].y, h0, l0); plane_split2<F>(ra[e].z, ra[e].w, h1, l1);
       *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(d + X3_PLANE) = make_uint2(l0, l1);
-      split2<F>(rb[e].x, rb[e].y, h0, l0); split2<F>(rb[e].z, rb[e].w, h1, l1);
+      plane_split2<F>(rb[e].x, rb[e].y, h0, l0); plane_split2<F>(rb[e].z, rb[e].w, h1, l1);
       *reinterpret_cast<uint2*>(d + 2 * X3_PLANE) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(d + 3 * X3_PLANE) = make_uint2(l0, l1);
     }
@@ -134,9 +126,7 @@ __global__ __launch_bounds__(256, 3) void gemm_x3_nt_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         // (operands swapped so that a lane ends up with 4 consecutive output columns of one row; corrections first)
-        acc[i][j] = H16<F>::mfma(bl[j], ah[i], acc[i][j]);
-        acc[i][j] = H16<F>::mfma(bh[j], al[i], acc[i][j]);
-        acc[i][j] = H16<F>::mfma(bh[j], ah[i], acc[i][j]);
+        acc[i][j] = plane_mfma3<F>(bh[j], bl[j], ah[i], al[i], acc[i][j]);
       }
     __syncthreads();                               // every wave has its fragments of this stage
     if (st + 1 < nst) sstore(smem);
@@ -244,10 +234,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_tn_kernel(
       const int kr = skr + 8 * e;
       char* d = stage + kr * 256 + (((sc4 >> 4) ^ (kr & 7)) << 5) + (sc4 & 15) * 2;
       uint32_t h0, l0, h1, l1;
-      split2<F>(ra[e].x, ra[e].y, h0, l0); split2<F>(ra[e].z, ra[e].w, h1, l1);
+      plane_split2<F>(ra[e].x, ra[e].y, h0, l0); plane_split2<F>(ra[e].z, ra[e].w, h1, l1);
       *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(d + X3_PLANE) = make_uint2(l0, l1);
-      split2<F>(rb[e].x, rb[e].y, h0, l0); split2<F>(rb[e].z, rb[e].w, h1, l1);
+      plane_split2<F>(rb[e].x, rb[e].y, h0, l0); plane_split2<F>(rb[e].z, rb[e].w, h1, l1);
       *reinterpret_cast<uint2*>(d + 2 * X3_PLANE) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(d + 3 * X3_PLANE) = make_uint2(l0, l1);
     }
@@ -283,9 +273,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_tn_kernel(
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        acc[i][j] = H16<F>::mfma(bl[j], ah[i], acc[i][j]);
-        acc[i][j] = H16<F>::mfma(bh[j], al[i], acc[i][j]);
-        acc[i][j] = H16<F>::mfma(bh[j], ah[i], acc[i][j]);
+        acc[i][j] = plane_mfma3<F>(bh[j], bl[j], ah[i], al[i], acc[i][j]);
       }
     if (st + 1 < nst) sstore(smem + ((st + 1) & 1) * X3_STAGE);
     __syncthreads();

@@ -22,13 +22,6 @@
 #include "prof.h"
 #include "p3.h"
 
-template <typename F>
-__device__ __forceinline__ void xp_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  a = f32_pin(a); b = f32_pin(b);
-  hi = H16<F>::pack2(a, b);
-  lo = H16<F>::pack2(a - H16<F>::lo(hi), b - H16<F>::hi(hi));
-}
-
 // element offset of stream stage s inside an operand: k block s / 3, and the lo plane for the one term that takes it
 // (A: term 1, B: term 0).  s < 2^15.
 __device__ __forceinline__ long xp_off(int s, long plane_stride, int lo_term) {
@@ -283,8 +276,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_xp_kernel(
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             uint32_t h0, l0, h1, l1;
-            xp_split2<F>(vv[j][0], vv[j][1], h0, l0);
-            xp_split2<F>(vv[j][2], vv[j][3], h1, l1);
+            plane_split2<F>(vv[j][0], vv[j][1], h0, l0);
+            plane_split2<F>(vv[j][2], vv[j][3], h1, l1);
             const uint32_t ad = slot + (uint32_t)(((j * 2 + (fg >> 1)) ^ sw) << 4);
             const uint2 oh = make_uint2(h0, h1), ol = make_uint2(l0, l1);
             asm volatile("ds_write_b64 %0, %1\n\tds_write_b64 %0, %2 offset:2048" ::"v"(ad), "v"(oh), "v"(ol) : "memory");
@@ -617,18 +610,11 @@ __global__ __launch_bounds__(256) void planes_kernel(int rows, int cols8, const 
       const float4 a = p[0], b = p[1];
       v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     } else {
-      const bf16_t* ph = reinterpret_cast<const bf16_t*>(src) + (long)r * lds_ + c;
-      const uint4 h = *reinterpret_cast<const uint4*>(ph), l = *reinterpret_cast<const uint4*>(ph + src_ps);
-      const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[2 * e] = H16<SRC>::lo(hw[e]) + H16<SRC>::lo(lw[e]);
-        v[2 * e + 1] = H16<SRC>::hi(hw[e]) + H16<SRC>::hi(lw[e]);
-      }
+      plane_ld8<SRC>(reinterpret_cast<const bf16_t*>(src) + (long)r * lds_ + c, src_ps, v);
     }
     uint32_t ho[4], lo[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) xp_split2<DST>(v[2 * e], v[2 * e + 1], ho[e], lo[e]);
+    for (int e = 0; e < 4; ++e) plane_split2<DST>(v[2 * e], v[2 * e + 1], ho[e], lo[e]);
     bf16_t* pd = dst + (long)r * ldd + c;
     *reinterpret_cast<uint4*>(pd) = make_uint4(ho[0], ho[1], ho[2], ho[3]);
     *reinterpret_cast<uint4*>(pd + dst_ps) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -642,15 +628,8 @@ __global__ __launch_bounds__(256) void planes_join_kernel(int rows, int cols8, c
   const long total = (long)rows * cols8;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int r = (int)(i / cols8), c = (int)(i % cols8) * 8;
-    const bf16_t* ph = src + (long)r * lds_ + c;
-    const uint4 h = *reinterpret_cast<const uint4*>(ph), l = *reinterpret_cast<const uint4*>(ph + src_ps);
-    const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
     float v[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[2 * e] = H16<SRC>::lo(hw[e]) + H16<SRC>::lo(lw[e]);
-      v[2 * e + 1] = H16<SRC>::hi(hw[e]) + H16<SRC>::hi(lw[e]);
-    }
+    plane_ld8<SRC>(src + (long)r * lds_ + c, src_ps, v);
     float4* pd = reinterpret_cast<float4*>(dst + (long)r * ldd + c);
     pd[0] = make_float4(v[0], v[1], v[2], v[3]);
     pd[1] = make_float4(v[4], v[5], v[6], v[7]);
@@ -729,7 +708,7 @@ __global__ __launch_bounds__(256) void split_weight_group64_kernel(SimxSplitGrou
     if (oh) {
       uint32_t hw[4], lw[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) xp_split2<f16_t>(v[2 * e], v[2 * e + 1], hw[e], lw[e]);
+      for (int e = 0; e < 4; ++e) plane_split2<f16_t>(v[2 * e], v[2 * e + 1], hw[e], lw[e]);
       *reinterpret_cast<uint4*>(oh + off) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
       *reinterpret_cast<uint4*>(oh + ps + off) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
     }
@@ -750,7 +729,7 @@ __global__ __launch_bounds__(256) void split_weight_group64_kernel(SimxSplitGrou
     if (ot) {
       uint32_t hw[4], lw[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) xp_split2<bf16_t>(v[2 * e], v[2 * e + 1], hw[e], lw[e]);
+      for (int e = 0; e < 4; ++e) plane_split2<bf16_t>(v[2 * e], v[2 * e + 1], hw[e], lw[e]);
       *reinterpret_cast<uint4*>(ot + off) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
       *reinterpret_cast<uint4*>(ot + ps + off) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
     }

@@ -73,17 +73,6 @@ __device__ __forceinline__ void st4_residue(T* p, const float (&o)[4], float (&r
   }
 }
 
-// plane pair (csrc/gemm_xp.hip, simx.h "operand planes") of 4 consecutive f32 values: hi = rnd16(o), lo = rnd16(o - hi)
-template <typename F>
-__device__ __forceinline__ void st4_planes(bf16_t* p, long plane_stride, const float (&oo)[4]) {
-  const float o[4] = {f32_pin(oo[0]), f32_pin(oo[1]), f32_pin(oo[2]), f32_pin(oo[3])};
-  const uint32_t h0 = H16<F>::pack2(o[0], o[1]), h1 = H16<F>::pack2(o[2], o[3]);
-  const uint32_t l0 = H16<F>::pack2(o[0] - H16<F>::lo(h0), o[1] - H16<F>::hi(h0));
-  const uint32_t l1 = H16<F>::pack2(o[2] - H16<F>::lo(h1), o[3] - H16<F>::hi(h1));
-  *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-  *reinterpret_cast<uint2*>(p + plane_stride) = make_uint2(l0, l1);
-}
-
 // ------------------------------------------------------------------------------------------ the row algorithm, step by step
 // f(v, c) for the lane's live vectors: vector v holds columns c .. c + 3, c = (v * 64 + lane) * 4 < H
 template <int VPL, typename F>
@@ -204,7 +193,7 @@ __device__ __forceinline__ void ln_store_row(int H, int lane, int row, float (&x
       *reinterpret_cast<uint32_t*>(ylo + (long)row * H + c) = lo8_encode4<T>(w0, w1, rr);
     } else {
       st4(yr + c, o);
-      if constexpr (std::is_same<T, float>::value) { if (yp) st4_planes<f16_t>(yp + (long)row * H + c, yps, o); }
+      if constexpr (std::is_same<T, float>::value) { if (yp) plane_st4<f16_t>(yp + (long)row * H + c, yps, o); }
     }
   });
 }
@@ -375,7 +364,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int rows, int H, int rows_p
         for (int e = 0; e < 4; ++e) dz[v][e] *= m4[e];
         if (!dzpl) st4(dzm + (long)row * H + c, dz[v]);
       }
-      if constexpr (std::is_same<T, float>::value) { if (dzpl) st4_planes<bf16_t>(dzpl + (long)row * H + c, dzps, dz[v]); }
+      if constexpr (std::is_same<T, float>::value) { if (dzpl) plane_st4<bf16_t>(dzpl + (long)row * H + c, dzps, dz[v]); }
 #pragma unroll
       for (int e = 0; e < 4; ++e) pz[v][e] += dz[v][e];
     });

@@ -1,5 +1,5 @@
 // The device-side text that the LDS-DMA GEMM units share.  Included by csrc/gemm.hip, gemm_xp.hip, gemm_p5.hip and gemm_tn5.hip.
-//   1. common forms -- xcd_remap, glds16, the V3_* fragment reads / MFMA row / scheduling fence, the P_* global and LDS-DMA
+//   1. common forms -- (xcd_remap and glds16 are in common.h) the V3_* fragment reads / MFMA row / scheduling fence, the P_* global and LDS-DMA
 //      accesses, P_LDS: all four units (the V3_* row forms: gemm_nt_h16_v5_kernel, gemm_nt_p3_kernel, gemm_nt_xp_kernel)
 //   2. the persistent NT main loop -- p3_half, P_STEP, P_BND_*, the per-tile skeleton: gemm_nt_p3_kernel (gemm.hip) and
 //      gemm_nt_xp_kernel (gemm_xp.hip)
@@ -11,22 +11,6 @@
 // defines (P_AK / P_BK / P_BND_LAST; TN2_ONE_A / TN2_ONE_B / TN2_BOUNDARY).  A unit #undefs what it defined, nothing of this file.
 #pragma once
 #include "common.h"
-
-// ------------------------------------------------------------------------------------------
-// XCD-aware tile id: block b runs on XCD b%8 (observed placement, speed only); give every XCD
-// a contiguous range of logical tiles.  Bijective for any grid size.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int xcd_remap(int b, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = b & 7, loc = b >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-__device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_ptr_t)g, (lds_ptr_t)lds_wave_base, 16, 0, 0);
-}
 
 #define V3_READ4(F0, F1, F2, F3, ADDR, O0, O1, O2, O3)                                              \
   asm volatile("ds_read_b128 %0, %4 offset:" #O0 "\n\tds_read_b128 %1, %4 offset:" #O1 "\n\t"       \

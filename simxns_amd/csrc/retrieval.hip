@@ -12,7 +12,7 @@
 //                      NT GEMMs, K tail zero-filled in LDS.  Bounds: 16-bit MFMA rate and, for a whole search, the 8 B
 //                      of HBM traffic per score of the write-then-top-k design.
 //   ip_scores_planes_kernel / ip_filter_planes_kernel  the plane-pair storage mode: every float32 row and query is held as two binary16
-//                      planes, hi = rnd16(x), lo = rnd16(x - hi) (the xp_split2 rule of gemm_xp.hip, taken by simx_planes_from), and a
+//                      planes, hi = rnd16(x), lo = rnd16(x - hi) (the plane_split2 rule of common.h, taken by simx_planes_from), and a
 //                      score is the float32 MFMA accumulation of Qhi.Clo + Qlo.Chi + Qhi.Chi (lo.lo dropped by definition): 22
 //                      significand bits per operand element on the 16-bit matrix cores.  The loop is iph_main_loop<true>: the same
 //                      staging, LDS image, fragment reads and K order as the binary16 kernels, with four operand tiles per stage and

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from oracle import bert as obert
+from oracle import planes as oplanes
 from tests.test_kernels_gpu import TOL, L, assert_close, back, code, rnd, rounded, tdt, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -59,9 +60,9 @@ def mult(rows, H, p=P):
 
 
 def split(v, t):
-    """plane pair of an f32 tensor: hi = rnd16(v), lo = rnd16(v - hi)"""
-    hi = v.to(t)
-    return hi, (v - hi.float()).to(t)
+    """plane pair of an f32 tensor (oracle/planes.py), on the tensor's device"""
+    hi, lo = oplanes.split16(v, t)
+    return hi.to(v.device), lo.to(v.device)
 
 
 def assert_planes(planes, v, t, what):

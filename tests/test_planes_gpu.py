@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import bert as obert
+from oracle import planes as oplanes
 
 pytestmark = pytest.mark.gpu
 F32, BF16, F16 = 0, 1, 2
@@ -188,8 +189,7 @@ def test_split_weight_forms(dev, rows, cols):
     torch.cuda.synchronize()
     assert torch.equal(wT, w.t().contiguous())
     for planes, src, t in ((ph, w, torch.float16), (pt, w.t().contiguous(), torch.bfloat16)):
-        hi = src.to(t)
-        lo = (src - hi.float()).to(t)
+        hi, lo = (p.to(dev) for p in oplanes.split16(src, t))
         assert torch.equal(planes[0].view(t), hi) and torch.equal(planes[1].view(t), lo)
     # any output may be absent
     ph.fill_(-1)
@@ -202,3 +202,72 @@ def test_split_weight_forms(dev, rows, cols):
         gbs = rows * cols * 16 / ms / 1e6
         print("split_weight %d x %d: %.3f ms = %.0f GB/s" % (rows, cols, ms, gbs))
         assert gbs > 1000, gbs                       # (the 32 x 32 scalar-store kernel ran at 220 GB/s)
+
+
+# ------------------------------------------------------------------------------------------ pair outputs against their f32 twins
+# A kernel that can leave the same f32 value either as f32 or as a plane pair must leave EXACTLY oracle.planes.split16 of the f32
+# form: these pin the bits of pair outputs that the tests above compare for accuracy only.
+def assert_pair_bits(planes, v, fmt):
+    """int16 device tensor [2, rows, cols] == the plane pair of the f32 tensor v, bit for bit"""
+    hi, lo = oplanes.split16(v, fmt)
+    assert torch.equal(planes[0].cpu(), hi.view(torch.int16)), "hi plane"
+    assert torch.equal(planes[1].cpu(), lo.view(torch.int16)), "lo plane"
+
+
+# (256, 256, 128 / 192): the smallest shapes simx_gemm_nt_planes_ok accepts, an even and an odd stage count.  512 x 768 is six
+# tiles, one per workgroup on any chip (the grid is never below 8 workgroups), so the last case gives the launch a budget of 8 CUs:
+# 12 tiles on 8 workgroups, i.e. the persistent loop runs a second tile in half of them.
+@pytest.mark.parametrize("M,N,K,cus", [(256, 256, 128, 0), (256, 256, 192, 0), (512, 768, 256, 0), (1024, 768, 256, 8)])
+def test_gemm_nt_planes_pair_is_the_split_of_the_f32_twin(dev, M, N, K, cus):
+    """gemm_nt_xp_kernel: SIMX_EPI_NONE_PLANES (pair out) == split16 of SIMX_EPI_NONE (f32 C), same fp16 operand planes and bias"""
+    lib = L()
+    Ap = planes_of(torch.from_numpy(rnd((M, K), 1, 0.5)).to(dev), F16, dev)
+    Bp = planes_of(torch.from_numpy(rnd((N, K), 2, 0.05)).to(dev), F16, dev)
+    bias = torch.from_numpy(rnd((N,), 3, 0.5)).to(dev)
+    Cc = torch.full((M, N), float("nan"), device=dev)
+    Cp = torch.full((2, M, N), -1, device=dev, dtype=torch.int16)
+    try:
+        lib.call("simx_set_compute_cus", cus)
+        for epi, c, cp in ((0, Cc, None), (4, None, Cp)):
+            lib.call("simx_gemm_nt_planes", lib.stream_ptr(), F16, epi, M, N, K, lib.ptr(Ap), K, M * K, lib.ptr(Bp), K, N * K, lib.ptr(c), N,
+                     lib.ptr(bias), None, N, lib.ptr(cp), N, M * N, None)
+        torch.cuda.synchronize()
+    finally:
+        lib.call("simx_set_compute_cus", 0)
+    assert torch.isfinite(Cc).all()
+    assert_pair_bits(Cp, Cc, "f16")
+
+
+# 1, 17 and 40 tokens in one batch: the resident kernel; 257: the first length simx_mha_fwd_f32 gives to its _long kernel
+# (max_len > 256, csrc/attention_f32.hip).  The backward has no such twin: its PL form reads ctx from the pair.
+@pytest.mark.parametrize("lens", [[1, 17, 40], [257]])
+def test_mha_fwd_f32_pair_is_the_split_of_the_f32_twin(dev, lens):
+    """mha_fwd_f32_kernel / mha_fwd_f32_long_kernel: the PL form's fp16 pair == split16 of the plain form's f32 ctx; equal lse"""
+    lib = L()
+    heads, d, T = 2, 64, sum(lens)
+    H = heads * d
+    qkv = torch.from_numpy(rnd((T, 3 * H), 1)).to(dev)
+    cu = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)).to(dev)
+    ctx = torch.full((T, H), float("nan"), device=dev)
+    ctxp = torch.full((2, T, H), -1, device=dev, dtype=torch.int16)
+    lse, lse2 = torch.full((heads, T), float("nan"), device=dev), torch.full((heads, T), float("nan"), device=dev)
+    lib.call("simx_mha_fwd_ex", lib.stream_ptr(), F32, len(lens), heads, d, lib.ptr(cu), max(lens), T, lib.ptr(qkv), lib.ptr(ctx), lib.ptr(lse), None)
+    lib.call("simx_mha_fwd_planes", lib.stream_ptr(), len(lens), heads, d, lib.ptr(cu), max(lens), T, lib.ptr(qkv), lib.ptr(ctxp), T * H,
+             lib.ptr(lse2), None)
+    torch.cuda.synchronize()
+    assert torch.isfinite(ctx).all() and torch.isfinite(lse).all()
+    assert_pair_bits(ctxp, ctx, "f16")
+    assert torch.equal(lse, lse2)
+
+
+def test_planes_from_pair_to_pair_is_split_of_join(dev):
+    """planes_kernel pair -> pair (plane_ld8 then plane_split2): fp16 pair -> bf16 pair == split16(join(hi, lo), bf16)"""
+    lib = L()
+    rows, cols = 37, 72
+    rs = np.random.RandomState(11)
+    x = (rs.choice([-1.0, 1.0], size=(rows, cols)) * 2.0 ** rs.uniform(-8, 8, size=(rows, cols))).astype(np.float32)
+    p = planes_of(torch.from_numpy(x).to(dev), F16, dev)
+    q = torch.full((2, rows, cols), -1, device=dev, dtype=torch.int16)
+    lib.call("simx_planes_from", lib.stream_ptr(), F16, BF16, rows, cols, lib.ptr(p), cols, rows * cols, lib.ptr(q), cols, rows * cols)
+    torch.cuda.synchronize()
+    assert_pair_bits(q, oplanes.join(p[0].view(torch.float16), p[1].view(torch.float16)), "bf16")

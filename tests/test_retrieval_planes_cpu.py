@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import planes as oplanes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("simx_ip_scores_planes", "simx_ip_filter_planes", "simx_flat_ip_search_planes", "simx_flat_ip_search_planes_fused")
 # each new entry point and the binary16 one whose argument list it takes, with (hi, lo) for each of the two 16-bit operands
@@ -32,11 +34,9 @@ def grid_emb(seed, n, H):
 
 
 def split16(x):
-    """the plane pair of a float32 array, both planes as float32: hi = rnd16(x), lo = rnd16(x - hi), the subtraction in float32"""
-    x = np.ascontiguousarray(x, np.float32)
-    hi = x.astype(np.float16).astype(np.float32)
-    lo = (x - hi).astype(np.float16).astype(np.float32)
-    return hi, lo
+    """the binary16 plane pair of a float32 array (oracle/planes.py), both planes as float32"""
+    hi, lo = oplanes.split16(np.asarray(x), "f16")
+    return hi.float().numpy(), lo.float().numpy()
 
 
 def three_term(q, c):
