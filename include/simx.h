@@ -660,6 +660,28 @@ int simx_flat_ip_search_planes_fused(simx_stream_t stream, int nq, long nc, int 
                                      int cand_cap, void* workspace, size_t workspace_bytes, float* out_scores, int64_t* out_ids,
                                      int* overflow);
 
+/* Mined-negative pool: a search result turned, on the device, into the tables the train job's device sampler works from -- the
+ * device form of the generate job's write_to_file (co_training_generate.py) plus the rank its compute_metrics looks for.
+ * scores / ids [nq,k] are a search result: rows sorted, padding (-inf, -1) at the tail.  pos_ptr [nq+1] / pos_ids [pos_ptr[nq]] are
+ * the CSR of each query's positives, in the id space of `ids`.  Per query q:
+ *   v = the number of leading entries with ids >= 0 (everything after the first negative id is ignored); t = min(top, v).
+ *   For rank r < t: if ids[r] is one of the query's positives, every CSR slot holding that id gets pos_scores[slot] = scores[r];
+ *   otherwise the entry is a negative.  A positive slot matched by no rank < t gets 0.0f (a positive retrieved at rank >= top keeps
+ *   0, as in the text file).  Every slot is written: the caller does not pre-zero.
+ *   Negatives keep rank order and are right-aligned: with c negatives, entry i goes to column top - c + i of neg_rows / neg_scores
+ *   [nq,top] (the id as int32, the score); the columns to its left hold row 0 and score +inf (SimANS weight 0); neg_cnt[q] = c.
+ *   first_hit[q] = 1 + the smallest r < v (all k columns, not only top) whose id is a positive, 0 if there is none.
+ * neg_rows, neg_scores and neg_cnt are given together or all NULL; pos_scores and first_hit may each be NULL.
+ * Requirements: 0 < k <= 1024, 0 < top <= 1024 (top > k is legal), ids < 2^31, pos_ptr[0] == 0 and non-decreasing, ids distinct
+ * within a row, positives distinct within a query (duplicates are not detected; they break no bound).  A violation returns
+ * SIMX_ERR_BAD_SHAPE and nothing is written.  The id range and pos_ptr are device data: they are checked by a reduction on the stream
+ * whose two flag words the host reads back, so the call synchronises the stream once before the mining kernel is launched.
+ * One wavefront per query, membership against the whole CSR segment (no cap on its length), order-preserving compaction by wave
+ * ballot and lane prefix count (a count pass, then a write pass); no atomics: the output is a pure function of the inputs. */
+int simx_mine_negatives(simx_stream_t stream, int nq, int k, int top, const float* scores, const int64_t* ids,
+                        const int32_t* pos_ptr, const int64_t* pos_ids, int32_t* neg_rows, float* neg_scores, int32_t* neg_cnt,
+                        float* pos_scores, int32_t* first_hit);
+
 /* -------------------------------------------------------------- SimANS sampler
  * S1+S2 (SimANS/utils/MARCO_until_new.py:174-202, util_wiki.py:609-639, MARCO_until_Doc.py:110-148).
  * scores [nq,C] f64 candidate scores (rank order), pos_score [nq] f64.  form 0: exp(-|s-s+|*tau);

@@ -121,6 +121,7 @@ SIGNATURES = {
     "simx_ip_filter_planes": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, C.c_int64, _i, _p, _p, _p, _p, _i, _p]),
     "simx_flat_ip_search_planes": (_i, [_p, _i, C.c_long, _i, _p, _p, _p, _p, C.c_int64, _i, _i, _p, _z, _p, _p]),
     "simx_flat_ip_search_planes_fused": (_i, [_p, _i, C.c_long, _i, _p, _p, _p, _p, C.c_int64, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
+    "simx_mine_negatives": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "simx_simans_sample": (_i, [_p, _i, _i, _i, _p, _p, _i, _d, _d, _d, C.c_uint64, C.c_uint32, _p, _p, _p, _p]),
     "simx_sqnorm_accum": (_i, [_p, _p, _z, _p]),
     "simx_sqnorm_accum_det": (_i, [_p, _p, _z, _p, _p]),

@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from simxns_amd import mined_pool as MP                                               # noqa: E402
 from simxns_amd.model.models import BiBertEncoder                                     # noqa: E402
 from simxns_amd.retrieval import FlatIPIndex, index_storage                           # noqa: E402
 from simxns_amd.utils.MARCO_until_new import HashTokenizer, load_id_text              # noqa: E402
@@ -115,15 +116,25 @@ def write_to_file(qids_to_ranked_candidate_passages, qids_to_ranked_candidate_sc
     return out_path
 
 
+MINED_FORMATS = ("tsv", "pool", "both")
+
+
 class RenewTools(object):
     """The reference's driver object (:269-460) reduced to what the job needs."""
 
     def __init__(self, passages_path, tokenizer, output_dir, passage_title_path=None, max_passage_length=128, rank=0, world=1,
-                 index_float16=False, index_fused=False, index_planes=False):
+                 index_float16=False, index_fused=False, index_planes=False, mined_format="tsv"):
         """Reads the corpus file once (ids of every row: the search returns global corpus rows), but TOKENISES only this
         rank's contiguous slice [rank*n/world, (rank+1)*n/world) -- the only rows this rank embeds.  ``index_float16``: the
         reference's (commented-out) ``co.useFloat16 = True``, FlatIPIndex(storage="fp16"); ``index_planes``: float32-grade scores on
-        the matrix cores, FlatIPIndex(storage="planes"); ``index_fused``: the one-pass search of either (FlatIPIndex(fused=True))."""
+        the matrix cores, FlatIPIndex(storage="planes"); ``index_fused``: the one-pass search of either (FlatIPIndex(fused=True)).
+        ``mined_format``: "tsv" (the text file, as the reference), "pool" (the binary pool of simxns_amd.mined_pool: D, I stay on
+        the device, ops.mine_negatives builds the train job's tables, no text is written) or "both".  With "pool" / "both" the token
+        table of the slice is also kept in ``output_dir`` (corpus_tok.r<rank>of<world>.npy), and read back instead of tokenising when
+        the description beside it still matches."""
+        if mined_format not in MINED_FORMATS:
+            raise ValueError("mined_format %r: one of %s" % (mined_format, ", ".join(MINED_FORMATS)))
+        self.mined_format, self.rank, self.world, self.max_passage_length = mined_format, rank, world, max_passage_length
         self.index_storage = index_storage(index_float16, index_planes, index_fused)
         self.tokenizer, self.output_dir, self.index_float16 = tokenizer, output_dir, bool(index_float16)
         self.index_planes, self.index_fused = bool(index_planes), bool(index_fused)
@@ -136,7 +147,15 @@ class RenewTools(object):
         n = len(rows)
         self.passage_ids = np.fromiter((r[0] for r in rows), np.int64, n)
         self.slice = (rank * n // world, (rank + 1) * n // world)
-        _, self.passage_table = tokenize_table(rows[self.slice[0]:self.slice[1]], tokenizer, max_passage_length, pair=True)
+        self.corpus_tok = self.pool_path = None
+        if mined_format == "tsv":
+            _, self.passage_table = tokenize_table(rows[self.slice[0]:self.slice[1]], tokenizer, max_passage_length, pair=True)
+            return
+        self.corpus_tok = MP.corpus_tok_description(n, max_passage_length, tokenizer, world)
+        self.passage_table = MP.load_corpus_slice(output_dir, rank, world, self.corpus_tok)
+        if self.passage_table is None:
+            _, self.passage_table = tokenize_table(rows[self.slice[0]:self.slice[1]], tokenizer, max_passage_length, pair=True)
+            MP.save_corpus_slice(output_dir, rank, world, self.passage_table)
 
     def build_index(self, model, device, rank=0, world=1):
         """embed this rank's contiguous corpus slice and hold it in HBM; ids are global corpus rows."""
@@ -161,18 +180,60 @@ class RenewTools(object):
         qemb = embed_table(get_model_obj(model).query_emb, qtab, device)
         k = 200 if mode == "train" else 1000
         D, I = index.search(qemb, k, group=group)
-        D, I = D.cpu().numpy(), I.cpu().numpy()
-        cand = {int(q): [int(self.passage_ids[j]) for j in I[r] if j >= 0] for r, q in enumerate(qids)}
-        scores = {int(q): [float(s) for s, j in zip(D[r], I[r]) if j >= 0] for r, q in enumerate(qids)}
-        result = None
-        if golden_path and os.path.exists(golden_path):
-            result = compute_metrics(load_reference_from_stream(golden_path), cand)
+        result, path = None, None
+        have_gold = bool(golden_path and os.path.exists(golden_path))
+        eval_path = os.path.join(self.output_dir, mode + "_eval_result" + str(step_num) + ".json")
+        if self.mined_format != "pool":
+            Dh, Ih = D.cpu().numpy(), I.cpu().numpy()
+            cand = {int(q): [int(self.passage_ids[j]) for j in Ih[r] if j >= 0] for r, q in enumerate(qids)}
+            scores = {int(q): [float(s) for s, j in zip(Dh[r], Ih[r]) if j >= 0] for r, q in enumerate(qids)}
+            if have_gold:
+                result = compute_metrics(load_reference_from_stream(golden_path), cand)
+            if is_first_worker():
+                path = write_to_file(cand, scores, questions, pos_qp, pos_qp_add or {}, mode, self.output_dir, step_num)
+        if self.mined_format != "tsv":
+            pool_result, self.pool_path = self._mine_pool(D, I, qids, qtab, golden_path if have_gold else None, pos_qp, pos_qp_add or {},
+                                                          mode, step_num)
+            if self.mined_format == "pool":
+                result, path = pool_result, self.pool_path
+        if result is not None:
             logger.info("***** Done %s validate ***** %s", mode, result)
-            with open(os.path.join(self.output_dir, mode + "_eval_result" + str(step_num) + ".json"), "w") as f:
+            with open(eval_path, "w") as f:
                 json.dump(result, f, indent=2)
-        path = None
-        if is_first_worker():
-            path = write_to_file(cand, scores, questions, pos_qp, pos_qp_add or {}, mode, self.output_dir, step_num)
+        return result, path
+
+    def _mine_pool(self, D, I, qids, qtab, golden_path, pos_qp, pos_qp_add, mode, step_num):
+        """The pool form of compute_metrics + write_to_file on the search result still on the device: one ops.mine_negatives call
+        against the qrels positives gives the first relevant rank of every query (-> the metrics); for the train queries one call
+        against qrels + additions gives the negative / positive tables (the same call when the two positive sets agree), which
+        rank 0 saves as <mode>_ce_<step>.pool.npz.  -> (metrics or None, pool path or None)."""
+        from simxns_amd import ops
+        dev = D.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        train_csr = MP.positives_csr(qids, pos_qp, pos_qp_add, self.passage_ids) if mode == "train" else None
+        result, mined = None, None
+        if golden_path:
+            gold = load_reference_from_stream(golden_path)
+            gold_csr = MP.positives_csr(qids, gold, {}, self.passage_ids)
+            shared = train_csr is not None and all(np.array_equal(a, b) for a, b in zip(gold_csr, train_csr))
+            out = ops.mine_negatives(D, I, up(gold_csr[0]), up(gold_csr[1]), top=200, want_negatives=shared)
+            labelled = np.fromiter((int(q) in gold for q in qids), bool, len(qids))
+            result = MP.metrics_from_first_hit(out["first_hit"].cpu().numpy(), labelled, len(gold))
+            mined = out if shared else None
+        if train_csr is None:
+            return result, None
+        if mined is None:
+            mined = ops.mine_negatives(D, I, up(train_csr[0]), up(train_csr[1]), top=200, want_negatives=True)
+        if not is_first_worker():
+            return result, None
+        meta = dict(MP.tokenizer_description(self.tokenizer), corpus_rows=int(len(self.passage_ids)), q_len=int(qtab.shape[1]),
+                    p_len=int(self.max_passage_length), pad_id=int(self.tokenizer.pad_token_id), sep_id=int(self.tokenizer.sep_token_id),
+                    corpus_slices=int(self.world), step=int(step_num))
+        host = {k: mined[k].cpu().numpy() for k in ("neg_rows", "neg_scores", "neg_cnt", "pos_scores")}
+        # every rank compared the old description with its own before the (collective) search: rank 0 may replace it now
+        MP.write_corpus_tok_description(self.output_dir, self.corpus_tok)
+        path = MP.save_pool(MP.pool_path(self.output_dir, step_num, mode), qids, qtab, host["neg_rows"], host["neg_scores"], host["neg_cnt"],
+                            train_csr[0], train_csr[1], host["pos_scores"], meta)
         return result, path
 
 
@@ -197,7 +258,8 @@ def get_arguments(argv=None):
     the mined file goes to --ann_dir.  --index_float16: binary16 index storage (the reference's co.useFloat16, off there too);
     --index_planes: float32 rows as binary16 plane pairs, float32-grade scores from the matrix cores (off by default; not with
     --index_float16); --index_fused: with either, the one-pass search that filters the scores in the score kernel (experimental,
-    off by default)."""
+    off by default).  --mined_format: tsv (default: train_ce_<step>.tsv, as the reference), pool (train_ce_<step>.pool.npz, the binary
+    hand-off to the train job's --mined_pool; no text is written) or both."""
     ap = argparse.ArgumentParser()
     A = ap.add_argument
     A("--model_type", required=True); A("--model_name_or_path", default=None); A("--output_dir", required=True)
@@ -210,6 +272,7 @@ def get_arguments(argv=None):
         A(ignored, type=int, default=0)
     A("--log_dir", default=None); A("--gradient_checkpointing", action="store_true")
     A("--index_float16", action="store_true"); A("--index_planes", action="store_true"); A("--index_fused", action="store_true")
+    A("--mined_format", default="tsv", choices=list(MINED_FORMATS))
     args = ap.parse_args(argv)
     try:
         index_storage(args.index_float16, args.index_planes, args.index_fused)
@@ -244,7 +307,8 @@ def main():
         tok = BertTokenizer.from_pretrained(args.tokenizer_name or "bert-base-uncased", do_lower_case=True)
     data_dir = args.passage_path
     tools = RenewTools(os.path.join(data_dir, "para.txt"), tok, ann_dir, os.path.join(data_dir, "para.title.txt"), rank=rank, world=world,
-                       index_float16=args.index_float16, index_fused=args.index_fused, index_planes=args.index_planes)
+                       index_float16=args.index_float16, index_fused=args.index_fused, index_planes=args.index_planes,
+                       mined_format=args.mined_format)
     index = tools.build_index(model, device, rank, world)
     for mode, qa in (("train", args.train_qa_path), ("dev", args.dev_qa_path)):
         if qa:

@@ -119,9 +119,13 @@ def train(args, model, teacher_model, tokenizer, global_step=0, dataset_cls=Rock
     def iteration_loader(gstep):
         """Dataset + batch iterator of the shell-loop iteration that starts at optimiser step `gstep` (train_ce_<gstep>.tsv)."""
         train_data_path = os.path.join(args.ann_dir, 'train_ce_' + str(gstep) + '.tsv') if gstep != 0 else args.origin_data_dir
+        kwargs = dict(dataset_kwargs or {})
+        if getattr(args, "mined_pool", False) and gstep != 0:
+            # --mined_pool: the binary pool the generate job's --mined_format pool wrote, instead of train_ce_<gstep>.tsv
+            kwargs["pool_path"] = os.path.join(args.ann_dir, 'train_ce_' + str(gstep) + '.pool.npz')
         train_dataset = dataset_cls(train_data_path, tokenizer, num_hard_negatives=args.number_neg,
                                     trainer_id=max(args.local_rank, 0), trainer_num=world,
-                                    corpus_path=args.passage_path, rand_pool=100, **(dataset_kwargs or {}))
+                                    corpus_path=args.passage_path, rand_pool=100, **kwargs)
         gpu_sampler = getattr(args, "sampler", "host") == "gpu" and hasattr(train_dataset, "build_device_pool")
         if gpu_sampler:
             # --sampler gpu: the SimANS draw and the collate run on the device from tables tokenised once per iteration
@@ -282,6 +286,9 @@ def get_arguments(argv=None):
     A("--seed", type=int, default=42)
     A("--sampler", default="host", choices=["host", "gpu"],
       help="gpu: SimANS draw + collate on the device from a pool tokenised once per iteration (no DataLoader workers)")
+    A("--mined_pool", action="store_true",
+      help="for --global_step != 0 read <ann_dir>/train_ce_<step>.pool.npz (the generate job's --mined_format pool) instead of the "
+           ".tsv: the device pool is taken from the binary tables, nothing is parsed or tokenised.  Needs --sampler gpu")
     A("--fp16", action="store_true")
     A("--fp16_opt_level", type=str, default="O1")
     A("--single_warmup", default=False, action="store_true")
@@ -317,7 +324,10 @@ def get_arguments(argv=None):
     A("--ann_dir", type=str, default="")
     A("--global_step", type=int, default=0)
     A("--num_workers", type=int, default=15)            # reference hard-codes 15 (:156)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.mined_pool and args.sampler != "gpu":
+        p.error("--mined_pool needs --sampler gpu: the pool holds token tables for the device sampler and no text for the host one")
+    return args
 
 
 def set_env(args):

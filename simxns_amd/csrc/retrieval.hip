@@ -695,3 +695,133 @@ extern "C" int simx_flat_ip_search_planes_fused(simx_stream_t stream, int nq, lo
                               IphOperand{(const f16_t*)corpus_hi, (const f16_t*)corpus_lo}, id_base, k, chunk, seed_rows, cand_cap, workspace,
                               workspace_bytes, out_scores, out_ids, overflow);
 }
+
+// ---- mined-negative pool: the device form of the generate job's write_to_file + the rank compute_metrics looks for ------------------
+// One wavefront per query over its search-result row (ranks in blocks of 64, lane = rank within the block).  v = the leading
+// entries with id >= 0, t = min(top, v).  A rank is a positive when its id is in the query's CSR segment (every lane walks the
+// whole segment: no cap on its length; the segment address is wave-uniform).  Negatives are compacted in rank order with a wave
+// ballot and a lane prefix count: a count pass (which also finds the first positive rank over all v ranks), then a write pass that
+// right-aligns them in [top] columns behind (row 0, +inf) padding.  Positive scores are written slot by slot (the wave looks the
+// slot's id up among the first t ranks; unmatched slots get 0), so every output word has exactly one writer: no atomics, no
+// pre-zeroing, the output is a pure function of the inputs.
+__device__ __forceinline__ bool mn_is_positive(long long id, const long long* __restrict__ pos_ids, int p0, int p1) {
+  bool hit = false;
+  for (int j = p0; j < p1; ++j) hit |= pos_ids[j] == id;
+  return hit;
+}
+
+__global__ __launch_bounds__(256) void mine_negatives_kernel(int nq, int k, int top, const float* __restrict__ scores,
+                                                             const long long* __restrict__ ids, const int* __restrict__ pos_ptr,
+                                                             const long long* __restrict__ pos_ids, int* __restrict__ neg_rows,
+                                                             float* __restrict__ neg_scores, int* __restrict__ neg_cnt,
+                                                             float* __restrict__ pos_scores, int* __restrict__ first_hit) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;                                       // wave-uniform: the ballots below see whole waves
+  const float* S = scores + (long)q * k;
+  const long long* I = ids + (long)q * k;
+  const int p0 = pos_ptr[q], p1 = pos_ptr[q + 1];
+  int v = k;
+  for (int b = 0; b * 64 < k; ++b) {
+    const int r = b * 64 + lane;
+    const unsigned long long m = __ballot(r < k && I[r] < 0);
+    if (m) { v = b * 64 + __ffsll((long long)m) - 1; break; }
+  }
+  const int t = top < v ? top : v;
+  // count pass: negatives among the first t ranks, first positive among the first v
+  const int last = first_hit ? v : t;
+  int c = 0, first = 0;
+  for (int b = 0; b * 64 < last; ++b) {
+    const int r = b * 64 + lane;
+    const bool pos = r < last && mn_is_positive(I[r], pos_ids, p0, p1);
+    const unsigned long long m = __ballot(pos);
+    if (!first && m) first = b * 64 + __ffsll((long long)m);
+    c += __popcll(__ballot(r < t && !pos));
+    if (first && (b + 1) * 64 >= t) break;
+  }
+  if (first_hit && lane == 0) first_hit[q] = first;
+  if (pos_scores) {
+    for (int j = p0; j < p1; ++j) {
+      const long long pid = pos_ids[j];
+      bool found = false;
+      for (int b = 0; b * 64 < t; ++b) {
+        const int r = b * 64 + lane;
+        const bool hit = r < t && I[r] == pid;
+        if (__ballot(hit)) {
+          if (hit) pos_scores[j] = S[r];
+          found = true;
+          break;
+        }
+      }
+      if (!found && lane == 0) pos_scores[j] = 0.f;
+    }
+  }
+  if (neg_rows) {
+    int* rows = neg_rows + (long)q * top;
+    float* sc = neg_scores + (long)q * top;
+    const int base = top - c;
+    for (int i = lane; i < base; i += 64) { rows[i] = 0; sc[i] = INFINITY; }
+    int run = 0;
+    for (int b = 0; b * 64 < t; ++b) {
+      const int r = b * 64 + lane;
+      long long id = 0;
+      bool neg = false;
+      if (r < t) { id = I[r]; neg = !mn_is_positive(id, pos_ids, p0, p1); }
+      const unsigned long long m = __ballot(neg);
+      if (neg) {
+        const int col = base + run + __popcll(m & ((1ull << lane) - 1ull));
+        rows[col] = (int)id;
+        sc[col] = S[r];
+      }
+      run += __popcll(m);
+    }
+    if (lane == 0) neg_cnt[q] = c;
+  }
+}
+
+// what the host cannot see: flag[0] = an id >= 2^31, flag[1] = pos_ptr does not start at 0 or decreases
+__global__ void mine_check_kernel(long n, const long long* __restrict__ ids, int nq, const int* __restrict__ pos_ptr, int* __restrict__ flag) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n && ids[i] >= 0x80000000ll) flag[0] = 1;
+  if (i < nq && (pos_ptr[i + 1] < pos_ptr[i] || (i == 0 && pos_ptr[0] != 0))) flag[1] = 1;
+}
+
+extern "C" int simx_mine_negatives(simx_stream_t stream, int nq, int k, int top, const float* scores, const int64_t* ids, const int32_t* pos_ptr,
+                                   const int64_t* pos_ids, int32_t* neg_rows, float* neg_scores, int32_t* neg_cnt, float* pos_scores,
+                                   int32_t* first_hit) {
+  hipStream_t s = (hipStream_t)stream;
+  SIMX_REQUIRE(nq > 0 && k > 0 && k <= TK_KMAX && top > 0 && top <= TK_KMAX, SIMX_ERR_BAD_SHAPE,
+               "mine_negatives: need nq=%d > 0, 0 < k=%d <= %d and 0 < top=%d <= %d", nq, k, TK_KMAX, top, TK_KMAX);
+  SIMX_REQUIRE(scores && ids && pos_ptr, SIMX_ERR_BAD_SHAPE, "mine_negatives: NULL input (pos_ids may be NULL only when there are no positives)");
+  const int n_neg_out = (neg_rows != nullptr) + (neg_scores != nullptr) + (neg_cnt != nullptr);
+  SIMX_REQUIRE(n_neg_out == 0 || n_neg_out == 3, SIMX_ERR_BAD_SHAPE, "mine_negatives: neg_rows, neg_scores and neg_cnt come together or not at all");
+  SIMX_REQUIRE(n_neg_out || pos_scores || first_hit, SIMX_ERR_BAD_SHAPE, "mine_negatives: no output asked for");
+  SIMX_REQUIRE((long)nq * k <= 0x7FFFFFFFl * 256, SIMX_ERR_BAD_SHAPE, "mine_negatives: nq * k too large");
+  // the contents the shapes do not show are checked on the device first; one 8-byte read and a stream synchronisation
+  int* flag = nullptr;
+  int host_flag[2] = {0, 0};
+  if (hipMalloc((void**)&flag, sizeof(host_flag)) != hipSuccess) {
+    simx_set_error("mine_negatives: hipMalloc of the check word failed");
+    return SIMX_ERR_HIP;
+  }
+  const long n = (long)nq * k;
+  hipError_t e = hipMemsetAsync(flag, 0, sizeof(host_flag), s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(mine_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const long long*)ids, nq, pos_ptr, flag);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_flag, flag, sizeof(host_flag), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(flag);
+  if (e != hipSuccess) {
+    simx_set_error("mine_negatives: input check failed: %s", hipGetErrorString(e));
+    return SIMX_ERR_HIP;
+  }
+  SIMX_REQUIRE(!host_flag[0], SIMX_ERR_BAD_SHAPE, "mine_negatives: an id is >= 2^31 (rows are stored as int32)");
+  SIMX_REQUIRE(!host_flag[1], SIMX_ERR_BAD_SHAPE, "mine_negatives: pos_ptr must start at 0 and never decrease");
+  SIMX_PROF(SIMX_K_OTHER, s, (double)nq * (12.0 * k + 8.0 * top));
+  hipLaunchKernelGGL(mine_negatives_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, s, nq, k, top, scores, (const long long*)ids, pos_ptr,
+                     (const long long*)pos_ids, neg_rows, neg_scores, neg_cnt, pos_scores, first_hit);
+  SIMX_CHECK_LAUNCH("mine_negatives");
+  return SIMX_OK;
+}

@@ -113,7 +113,13 @@ def main(argv=None):
     ap.add_argument("--index_fused", "--index-fused", dest="index_fused", action="store_true",
                     help="with --index_float16 or --index_planes: pass --index_fused to the generate jobs, the one-pass search that filters "
                          "the scores in the score kernel (experimental).  Off by default in every recipe")
+    ap.add_argument("--mined_pool", "--mined-pool", dest="mined_pool", action="store_true",
+                    help="MS_Pas only: hand the mined hard negatives from the generate job to the train job as the binary pool "
+                         "train_ce_<step>.pool.npz instead of the .tsv (--mined_format=pool to the generate jobs, --mined_pool to the train "
+                         "jobs): no text is formatted, parsed or tokenised again.  Off by default")
     args, extra = ap.parse_known_args(argv)
+    if args.mined_pool and args.recipe != "MS_Pas":
+        ap.error("--mined_pool is for the MS_Pas recipe only: the other recipes' train jobs have no device sampler to hand a pool to")
     if args.index_float16 and args.index_planes:
         ap.error("--index_float16 and --index_planes exclude each other: an index has one storage mode")
     if args.index_fused and not (args.index_float16 or args.index_planes):
@@ -130,11 +136,12 @@ def main(argv=None):
     for global_step in range(args.first_step, last + 1, step):
         loop = dict(max_steps=r["max_steps"], iteration_step=step, iteration_reranker_step=r["iteration_reranker_step"])
         script, flags = r["train"]
-        jobs = [job_argv(script, dict(flags, global_step=global_step, **loop), args.nproc, args.port) + extra]
+        pool = dict(mined_pool=True) if args.mined_pool else {}
+        jobs = [job_argv(script, dict(flags, global_step=global_step, **pool, **loop), args.nproc, args.port) + extra]
         if r["generate"] is not None:
             script, flags = r["generate"]
             jobs.append(job_argv(script, dict(flags, global_step=global_step + step, index_float16=args.index_float16, index_planes=args.index_planes,
-                                             index_fused=args.index_fused,
+                                             index_fused=args.index_fused, mined_format="pool" if args.mined_pool else None,
                                              **loop),
                                  args.nproc, args.port))
         elif os.environ.get("SIMX_GENERATE_CMD"):

@@ -294,6 +294,40 @@ def simans_sample(scores, pos_score, num_neg, form=LAPLACE, a=0.5, b=0.0, tau=3.
     return out if len(out) > 1 else neg
 
 
+# ------------------------------------------------------------------------------------------ mined-negative pool
+def mine_negatives(D, I, pos_ptr, pos_ids, top=200, want_negatives=True):
+    """A search result D, I [nq,k] (f32 scores, int64 ids, rows sorted, (-inf, -1) padding at the tail) against the CSR of each
+    query's positives (pos_ptr int32 [nq+1], pos_ids int64, in the id space of I) -> dict of device tensors: ``pos_scores``
+    f32 [len(pos_ids)] (0 where the positive is not among the first ``top`` valid ranks), ``first_hit`` int32 [nq] (1 + the first
+    rank of a positive over all k columns, 0 = none) and, with ``want_negatives``, ``neg_rows`` int32 / ``neg_scores`` f32
+    [nq,top] (the non-positives of the first ``top`` valid ranks, rank order, right-aligned behind (0, +inf) padding) and
+    ``neg_cnt`` int32 [nq].  Semantics and requirements: simx_mine_negatives (include/simx.h)."""
+    for t in (D, I, pos_ptr, pos_ids):
+        if not t.is_cuda:
+            raise L.SimxError("mine_negatives runs only on a HIP device (no CPU fallback)")
+    if D.dim() != 2 or D.shape != I.shape:
+        raise ValueError("mine_negatives: D and I must be [nq, k] of one shape, got %s and %s" % (tuple(D.shape), tuple(I.shape)))
+    nq, k = D.shape
+    dev = D.device
+    D = D.contiguous().to(torch.float32)
+    I = I.contiguous().to(torch.int64)
+    pos_ptr = pos_ptr.contiguous().to(torch.int32)
+    pos_ids = pos_ids.contiguous().to(torch.int64)
+    if pos_ptr.numel() != nq + 1 or int(pos_ptr[-1]) != pos_ids.numel():
+        raise ValueError("mine_negatives: pos_ptr must hold nq + 1 = %d offsets ending at len(pos_ids) = %d" % (nq + 1, pos_ids.numel()))
+    top = int(top)
+    out = {"pos_scores": torch.empty(pos_ids.numel(), dtype=torch.float32, device=dev),
+           "first_hit": torch.empty(nq, dtype=torch.int32, device=dev)}
+    if want_negatives:
+        out["neg_rows"] = torch.empty(nq, max(top, 0), dtype=torch.int32, device=dev)
+        out["neg_scores"] = torch.empty(nq, max(top, 0), dtype=torch.float32, device=dev)
+        out["neg_cnt"] = torch.empty(nq, dtype=torch.int32, device=dev)
+    L.call("simx_mine_negatives", L.stream_ptr(), nq, k, top, L.ptr(D), L.ptr(I), L.ptr(pos_ptr), L.ptr(pos_ids),
+           L.ptr(out.get("neg_rows")), L.ptr(out.get("neg_scores")), L.ptr(out.get("neg_cnt")), L.ptr(out["pos_scores"]),
+           L.ptr(out["first_hit"]))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ D1
 def assemble_batch(q_tok, p_tok, q_rows, p_rows, docs_per_question, pad_id=0, sep_id=102, ce_len=160):
     """Device-side collate (MARCO_until_new.py:204-258) on pre-tokenised int32 tables in HBM.

@@ -13,6 +13,9 @@ the host a list of B row numbers per step -- positive pick, SimANS draw (``ops.s
 with-replacement draws, dedupe, remove, repeat; Philox instead of CPython's Mersenne twister, so the picks follow the same
 law but not the same sequence) and collate (``ops.assemble_batch``, bit-identical to the host collate) run on the GPU and
 return the collate's dictionary with device tensors.
+``pool_path=`` (``--mined_pool`` of the train job) takes the same device pool from the binary ``train_ce_<step>.pool.npz`` the
+generate job's ``--mined_format pool`` wrote (simxns_amd.mined_pool) instead of the text file: no parsing and no tokenising, the
+passage tokens come from the corpus-token slices beside the pool.  It carries no text, so it serves ``sampler="gpu"`` only.
 Collate -> {'student': [q[B,32], q_mask, ctx[B(1+N),128], ctx_mask, positive_ctx_indices],
             'teacher': [ce[B,1+N,160], ce_mask, tgt]}  (MARCO_until_new.py:241-258).
 """
@@ -46,6 +49,11 @@ def load_id_text(file_name):
     return id_text
 
 
+def parse_pairs(column):
+    """'pid score,pid score,...' -> [(pid, score)] (MARCO_until_new.py:166-168)"""
+    return [(int(p.split()[0]), float(p.split()[1])) for p in column.split(',')]
+
+
 def simans_draw(neg_pairs, pos_score, num_neg, tau=3.0, rng=random):
     """MARCO_until_new.py:179-202 (Laplace form)."""
     if pos_score == 0:
@@ -62,16 +70,24 @@ def simans_draw(neg_pairs, pos_score, num_neg, tau=3.0, rng=random):
 
 class Rocketqa_v2Dataset(Dataset):
     def __init__(self, file_path, tokenizer, num_hard_negatives=1, trainer_id=0, trainer_num=1, is_training=True,
-                 corpus_path='', rand_pool=50, p_text=None, p_title=None, sampler="host"):
+                 corpus_path='', rand_pool=50, p_text=None, p_title=None, sampler="host", pool_path=None):
         self.file_path, self.tokenizer = file_path, tokenizer
-        self.data = read_sharded_tsv(file_path, trainer_id, trainer_num)
         self.is_training, self.num_hard_negatives, self.rand_pool, self.tau = is_training, num_hard_negatives, rand_pool, 3
         self.sampler = sampler
+        self.pool_path, self.mined = pool_path, None
+        if pool_path is not None:                # the binary pool: this rank's queries are rows i % trainer_num == trainer_id
+            from ..mined_pool import load_pool
+            import numpy as np
+            self.mined = load_pool(pool_path)
+            self.mined_rows = np.arange(trainer_id, self.mined["qids"].shape[0], trainer_num)
+            self.data = self.p_text = self.p_title = None
+            return
+        self.data = read_sharded_tsv(file_path, trainer_id, trainer_num)
         self.p_text = load_id_text(os.path.join(corpus_path, 'para.txt')) if p_text is None else p_text
         self.p_title = load_id_text(os.path.join(corpus_path, 'para.title.txt')) if p_title is None else p_text  # sic (:139)
 
     def __len__(self):
-        return len(self.data)
+        return len(self.data) if self.mined is None else len(self.mined_rows)
 
     # ---- sampler="gpu": SimANS draw + collate on the device (MARCO_until_new.py:165-258 without the DataLoader workers) -------
     def build_device_pool(self, device, q_len=32, p_len=128):
@@ -79,6 +95,8 @@ class Rocketqa_v2Dataset(Dataset):
         candidate scores in HBM.  Candidates are RIGHT-aligned in [NQ, Cmax] tables (pad score = +inf -> weight exp(-inf) = 0;
         the ``pos_score == 0`` rule "last N candidates" then still means the last N real ones)."""
         import numpy as np
+        if self.mined is not None:
+            return self._device_pool_from_mined(device, q_len, p_len)
         pad = self.tokenizer.pad_token_id
         rows, ptok = {}, []
 
@@ -95,8 +113,7 @@ class Rocketqa_v2Dataset(Dataset):
         for i, sample in enumerate(self.data):
             q = self.tokenizer.encode(sample.query_string, add_special_tokens=True, max_length=q_len, truncation=True)
             qtok[i, :len(q)] = q
-            pos = [(int(p.split()[0]), float(p.split()[1])) for p in sample.pos_id.split(',')]
-            neg = [(int(p.split()[0]), float(p.split()[1])) for p in sample.neg_id.split(',')]
+            pos, neg = parse_pairs(sample.pos_id), parse_pairs(sample.neg_id)
             if len(neg) < self.num_hard_negatives:
                 raise ValueError("query %s has %d mined negatives, fewer than --number_neg %d" % (sample.query_id, len(neg), self.num_hard_negatives))
             parsed.append((pos, neg))
@@ -118,6 +135,46 @@ class Rocketqa_v2Dataset(Dataset):
         self.pool = {"q_tok": t(qtok), "p_tok": t(np.asarray(ptok, dtype=np.int32).reshape(-1, p_len)), "cand_rows": t(cand_rows),
                      "cand_scores": t(cand_scores), "pos_rows": t(pos_rows), "pos_scores": t(pos_scores), "pos_cnt": t(pos_cnt),
                      "row_of": rows, "device": torch.device(device)}
+        return self.pool
+
+    def _device_pool_from_mined(self, device, q_len, p_len):
+        """build_device_pool from the binary pool: the rank's rows of the mined tables, trimmed to its own Cmax columns and
+        widened to float64 (the very table the text path builds), positives padded to Pmax, and ``p_tok`` gathered from the
+        corpus-token slices for the distinct corpus rows this rank mentions (rows renumbered in ascending order)."""
+        import numpy as np
+        from ..mined_pool import gather_corpus_rows, tokenizer_description
+        M, sel = self.mined, self.mined_rows
+        meta = M["meta"]
+        mine = dict(tokenizer_description(self.tokenizer), q_len=q_len, p_len=p_len, pad_id=self.tokenizer.pad_token_id,
+                    sep_id=self.tokenizer.sep_token_id)
+        theirs = {k: meta.get(k) for k in mine}
+        if mine != theirs:
+            raise ValueError("%s was mined with %s, this job runs with %s" % (self.pool_path, theirs, mine))
+        cnt = M["neg_cnt"][sel].astype(np.int64)
+        pos_cnt = np.diff(M["pos_ptr"].astype(np.int64))[sel]
+        for i in np.flatnonzero(cnt < self.num_hard_negatives)[:1]:
+            raise ValueError("query %s has %d mined negatives, fewer than --number_neg %d" % (M["qids"][sel[i]], cnt[i], self.num_hard_negatives))
+        for i in np.flatnonzero(pos_cnt == 0)[:1]:
+            raise ValueError("query %s has no positive passage" % M["qids"][sel[i]])
+        NQ, top = len(sel), M["neg_rows"].shape[1]
+        cmax, pmax = (int(cnt.max()), int(pos_cnt.max())) if NQ else (0, 0)
+        cand_src = M["neg_rows"][sel][:, top - cmax:].astype(np.int64)
+        cand_scores = M["neg_scores"][sel][:, top - cmax:].astype(np.float64)
+        real = np.arange(cmax)[None, :] >= (cmax - cnt)[:, None]
+        pcol = np.arange(pmax)[None, :]
+        pmask = pcol < pos_cnt[:, None]
+        pslot = (M["pos_ptr"].astype(np.int64)[sel][:, None] + pcol)[pmask]
+        used = np.unique(np.concatenate([cand_src[real], M["pos_rows"][pslot].astype(np.int64)]))
+        cand_rows = np.zeros((NQ, cmax), dtype=np.int32)
+        cand_rows[real] = np.searchsorted(used, cand_src[real])
+        pos_rows = np.zeros((NQ, pmax), dtype=np.int32)
+        pos_rows[pmask] = np.searchsorted(used, M["pos_rows"][pslot])
+        pos_scores = np.zeros((NQ, pmax), dtype=np.float64)
+        pos_scores[pmask] = M["pos_scores"][pslot]
+        ptok = gather_corpus_rows(os.path.dirname(os.path.abspath(self.pool_path)), used, meta)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self.pool = {"q_tok": t(M["q_tok"][sel]), "p_tok": t(ptok), "cand_rows": t(cand_rows), "cand_scores": t(cand_scores),
+                     "pos_rows": t(pos_rows), "pos_scores": t(pos_scores), "pos_cnt": t(pos_cnt), "device": torch.device(device)}
         return self.pool
 
     def device_batch(self, indices, seed=0, step=0, pos_choice=None, neg_choice=None):
@@ -157,9 +214,11 @@ class Rocketqa_v2Dataset(Dataset):
         return self.tokenizer.encode(title, text_pair=para, add_special_tokens=True, max_length=128, truncation=True)
 
     def __getitem__(self, index):
+        if self.mined is not None:
+            raise RuntimeError("a dataset opened from a mined pool carries no text: it serves sampler='gpu' (device_batch) only")
         sample = self.data[index]
         pos_pairs = sample.pos_id.split(',')
-        neg_pairs = [(int(p.split()[0]), float(p.split()[1])) for p in sample.neg_id.split(',')]
+        neg_pairs = parse_pairs(sample.neg_id)
         pos_id, pos_score = (random.choice(pos_pairs) if self.is_training else pos_pairs[0]).split()
         pos_id, pos_score = int(pos_id), float(pos_score)
         neg_ids = simans_draw(neg_pairs, pos_score, self.num_hard_negatives, self.tau)
