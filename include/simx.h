@@ -377,6 +377,10 @@ int simx_cls_scatter(simx_stream_t stream, int dtype, int nseq, int H, int T, co
 /* dx = S * dcls: where an f32 gradient enters the SIMX_F16 backward (gs = {S, 1/S}, NULL = 1) */
 int simx_cls_scatter_gs(simx_stream_t stream, int dtype, int nseq, int H, int T, const int32_t* cu_seqlens,
                         const float* dcls, void* dx, const float* gs);
+/* x[cu_seqlens ? cu_seqlens[s] : s] += S * add[s] for s < nseq (add f32 [nseq,H], x rows of H elements in `dtype`; S = gs[0],
+ * NULL = 1): one more reader of every sequence's [CLS] row joins the gradient already in x (simx_bert_bwd_taps). */
+int simx_cls_rows_add_gs(simx_stream_t stream, int dtype, int nseq, int H, const int32_t* cu_seqlens,
+                         const float* add, void* x, const float* gs);
 /* Row gather / scatter / dtype conversion: dst[dst_idx ? dst_idx[s] : s] = src[src_idx ? src_idx[s] : s], s < n, rows of
  * H elements (sequence_output[:, 0, :] and its transpose for same-dtype tensors; SimANS/model/models.py:81). */
 int simx_rows_copy(simx_stream_t stream, int src_dtype, int dst_dtype, int n, int H, const int32_t* src_idx,
@@ -475,6 +479,24 @@ int simx_bert_bwd_ex(simx_stream_t stream, const simx_bert_cfg* cfg, const float
                      const int32_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens,
                      int nseq, int T, int max_len, const void* act, size_t act_bytes,
                      const float* dcls, const void* dhidden, float* grads, void* scratch, size_t scratch_bytes);
+/* [CLS] taps: the [CLS] rows of chosen INTERMEDIATE layers beside the embedding (LEAD/modeling_bert.py:575-646: the
+ * all_hidden_states[i][:, 0] its layer-score distillation reads; i = the output of encoder layer i, 0-based).  tap_layers: a host
+ * array of ntap strictly ascending layer indices in [0, layers); tap_cls f32 [ntap, nseq, hidden]: slot k receives the [CLS] row
+ * of every sequence from the output of layer tap_layers[k], at the precision cls_out has (a stream_lo tower: hi + correction
+ * byte).  A tap on the last layer equals cls_out, with cfg->cls_only_last_layer too.  ntap == 0 is simx_bert_fwd.
+ * The backward takes a gradient for every tap, dtap_cls f32 [ntap, nseq, hidden]: before layer l is differentiated the [CLS]
+ * rows of the inter-layer gradient receive += S * dtap_cls[k] for tap_layers[k] == l (S: the gradient scale of the fp16
+ * engine); a tap on the last layer joins dcls in f32 before it enters the stack.  Taps outside [layer_lo, layer_hi] are
+ * ignored by that call, so a backward in parts applies each tap once. */
+int simx_bert_fwd_taps(simx_stream_t stream, const simx_bert_cfg* cfg, const float* params, const void* wcache,
+                       const int32_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens,
+                       int nseq, int T, int max_len, void* act, size_t act_bytes, int save_for_bwd,
+                       float* cls_out, void* hidden_out, const int32_t* tap_layers, int ntap, float* tap_cls);
+int simx_bert_bwd_taps(simx_stream_t stream, const simx_bert_cfg* cfg, const float* params, const void* wcache,
+                       const int32_t* ids, const int32_t* pos_ids, const int32_t* cu_seqlens,
+                       int nseq, int T, int max_len, void* act, size_t act_bytes,
+                       const float* dcls, const void* dhidden, float* grads, void* scratch, size_t scratch_bytes,
+                       int layer_hi, int layer_lo, const int32_t* tap_layers, int ntap, const float* dtap_cls);
 /* masked mean over the real tokens of each sequence of a packed [T,H] tensor -> f32 [nseq,H] (EmbeddingMixin.masked_mean,
  * SimANS/model/models.py:296-299), and its adjoint (dx[t] = dmean[seq(t)] / len) */
 int simx_seq_mean_fwd(simx_stream_t stream, int dtype, int nseq, int H, const int32_t* cu_seqlens, const void* x, float* mean);
@@ -551,6 +573,36 @@ int simx_scores_kd_type_fwd_bwd(simx_stream_t stream, int kd_type, int Q, int C,
                                 float dkd_beta, float loss_scale, int q_lo, int q_n, int c_lo, int c_n,
                                 float* scores, float* tscores, float* losses, float* dq_local, float* dctx_local,
                                 void* ws, size_t ws_bytes);
+
+/* L7: the LEAD layer-score objective (LEAD/util.py:540-831, distill_loss with distill_de, distill_db and
+ * distill_de_db_layer_score) over n slots of (student, teacher) embeddings: q [n,Q,H], ctx [n,C,H], tq [n,Q,HT],
+ * tctx [n,C,HT].  Per slot, with S = q ctx^T, Z = tq tctx^T, p = softmax(S), v = softmax(S/T), r = softmax(Z), u = softmax(Z/T):
+ *   nll_s = mean_q -log p[q,pos]                    nll_t = mean_q -log r[q,pos]
+ *   kl_ts = (1/Q) sum_q sum_c u (log u - log p)     kl_st = (1/Q) sum_q sum_c v (log v - log r)      (0 log 0 = 0)
+ *   slot loss = a nll_s + b nll_t + w kl_ts + x kl_st
+ * and total = loss_scale * sum of the slot losses.  Nothing is a constant: the student's gradient flows through v, the
+ * teacher's (teacher_grad != 0) through u, as autograd of F.kl_div does for its target.  A slot with reweight != 0 takes
+ * w = softmax_i(-nll_t,i / layer_temperature) over the flagged slots (a constant, formed on the device before any gradient
+ * is written; one flagged slot: 1) in place of its own w.  slot_losses [n,4] = {nll_s, nll_t, kl_ts, kl_st} (unscaled),
+ * weights [n] = the w applied.  Local-slot semantics of simx_scores_nll_fwd_bwd: dq / dtq [n,q_n,H|HT] and dctx / dtctx
+ * [n,c_n,H|HT] are the gradients of rows [q_lo,q_lo+q_n) and [c_lo,c_lo+c_n), already times loss_scale; dtq / dtctx are not
+ * touched when teacher_grad == 0.  scores / tscores [n,Q,C] f32 scratch.  The per-slot sums are ordered reductions (no
+ * atomics): two runs agree bit for bit.  ws is required: simx_lead_scores_workspace_bytes (row statistics + the split-K
+ * workspace of the backward products).  n > SIMX_LEAD_MAX_SLOTS, n < 1, temperature <= 0, layer_temperature <= 0 with a
+ * flagged slot, a local slot out of range, a NULL buffer or a short workspace: an error, nothing is launched. */
+#define SIMX_LEAD_MAX_SLOTS 32
+typedef struct simx_lead_slot {
+  float a, b, w, x;     /* weights of nll_s, nll_t, kl_ts, kl_st */
+  int32_t reweight;     /* != 0: w is the layer-score softmax weight, the field w is ignored */
+} simx_lead_slot;
+size_t simx_lead_scores_workspace_bytes(int n, int Q, int C, int H, int HT, int q_n, int c_n);
+int simx_lead_scores_fwd_bwd(simx_stream_t stream, int n, int Q, int C, int H, int HT,
+                             const float* q, const float* ctx, const float* tq, const float* tctx,
+                             const int32_t* pos_idx, float temperature, float layer_temperature,
+                             const simx_lead_slot* slots_host, int teacher_grad, float loss_scale,
+                             int q_lo, int q_n, int c_lo, int c_n,
+                             float* scores, float* tscores, float* slot_losses, float* weights, float* total,
+                             float* dq, float* dctx, float* dtq, float* dtctx, void* ws, size_t ws_bytes);
 
 /* -------------------------------------------------------------- D1: device-side batch assembly
  * The collate of SimANS/utils/MARCO_until_new.py:204-258 (Rocketqa_v2Dataset.__getitem__ tail +

@@ -42,6 +42,12 @@ class LossParams(C.Structure):
                 ("dkd_beta", C.c_float)]
 
 
+class LeadSlot(C.Structure):
+    _fields_ = [("a", C.c_float), ("b", C.c_float), ("w", C.c_float), ("x", C.c_float), ("reweight", C.c_int32)]
+
+
+LEAD_MAX_SLOTS = 32                # SIMX_LEAD_MAX_SLOTS (include/simx.h)
+
 _p, _i, _f, _d, _z, _l = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_long
 _cfgp, _lpp, _dp = C.POINTER(BertCfg), C.POINTER(LossParams), C.POINTER(Dropout)
 
@@ -89,7 +95,10 @@ SIGNATURES = {
     "simx_bert_bwd": (_i, [_p, _cfgp, _p, _p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _z]),
     "simx_bert_bwd_ex": (_i, [_p, _cfgp, _p, _p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _p, _z]),
     "simx_bert_bwd_range": (_i, [_p, _cfgp, _p, _p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _p, _z, _i, _i]),
-    "simx_seq_mean_fwd": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "simx_bert_fwd_taps": (_i, [_p, _cfgp, _p, _p, _p, _p, _p, _i, _i, _i, _p, _z, _i, _p, _p, C.POINTER(C.c_int32), _i, _p]),
+    "simx_bert_bwd_taps": (_i, [_p, _cfgp, _p, _p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _p, _z, _i, _i, C.POINTER(C.c_int32), _i, _p]),
+    "simx_cls_rows_add_gs": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "simx_seq_mean_fwd":(_i, [_p, _i, _i, _i, _p, _p, _p]),
     "simx_seq_mean_bwd": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "simx_sim_loss_fwd_bwd": (_i, [_p, _i, _i, _i, _p, _p, _p, _lpp, _p, _p, _p, _p]),
     "simx_gemm_hm_ok": (_i, [_i, _i, _i]),
@@ -105,6 +114,9 @@ SIGNATURES = {
     "simx_scores_kd_fwd_bwd": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _z]),
     "simx_scores_kd_type_fwd_bwd": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p,
                                          _p, _z]),
+    "simx_lead_scores_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i]),
+    "simx_lead_scores_fwd_bwd": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _f, C.POINTER(LeadSlot), _i, _f, _i, _i, _i, _i,
+                                      _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z]),
     "simx_gemm_f32_workspace_bytes": (_z, [_i, _i, _i]),
     "simx_assemble_batch": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "simx_ip_scores": (_i, [_p, _i, _i, _i, _p, _p, _p, C.c_long]),

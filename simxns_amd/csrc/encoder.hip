@@ -518,10 +518,31 @@ static int layer_fwd(const Ctx& cx, int l, const XS& x, const ALayer& a, int kee
   return layer_fwd_dense(cx, l, x, a, keep);
 }
 
-extern "C" int simx_bert_fwd(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
-                             const int32_t* ids, const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len,
-                             void* act, size_t act_bytes, int save, float* cls_out, void* hidden_out) {
+// [CLS] taps (simx.h simx_bert_fwd_taps): strictly ascending layer indices in [0, layers), with the buffer they fill / are read from
+static int check_taps(const simx_bert_cfg* c, const int32_t* tap_layers, int ntap, const float* tap_buf, const char* who) {
+  SIMX_REQUIRE(ntap >= 0 && (ntap == 0 || (tap_layers && tap_buf)), SIMX_ERR_BAD_SHAPE, "%s: %d taps without their layers / buffer", who, ntap);
+  for (int k = 0; k < ntap; ++k)
+    SIMX_REQUIRE(tap_layers[k] >= 0 && tap_layers[k] < c->layers && (k == 0 || tap_layers[k] > tap_layers[k - 1]), SIMX_ERR_BAD_SHAPE,
+                 "%s: tap_layers must be strictly ascending in [0, %d)", who, c->layers);
+  return SIMX_OK;
+}
+// slot of the tap on layer l, -1 = none
+static int tap_slot(const int32_t* tap_layers, int ntap, int l) {
+  for (int k = 0; k < ntap; ++k)
+    if (tap_layers[k] == l) return k;
+  return -1;
+}
+// the [CLS] rows of a full residual-stream tensor as f32 (a stream_lo tower: hi + correction byte)
+static int cls_rows_out(const Ctx& cx, const XS& x, float* out) {
+  if (x.lo) return simx_stream_rows(cx.stream, cx.c->dtype, cx.nseq, cx.c->hidden, cx.cu, x.hi, x.lo, nullptr, nullptr, out);
+  return simx_cls_gather(cx.stream, cx.c->dtype, cx.nseq, cx.c->hidden, cx.cu, x.hi, out);
+}
+
+static int bert_fwd(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache, const int32_t* ids,
+                    const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len, void* act, size_t act_bytes, int save,
+                    float* cls_out, void* hidden_out, const int32_t* tap_layers, int ntap, float* tap_cls) {
   RUN(check_io(c, nseq, T, max_len, "bert_fwd"));
+  RUN(check_taps(c, tap_layers, ntap, tap_cls, "bert_fwd"));
   SIMX_REQUIRE(params && wcache && ids && pos_ids && cu && act, SIMX_ERR_BAD_SHAPE, "bert_fwd: NULL buffer");
   const Ctx cx = make_ctx(stream, c, params, nullptr, wcache, cu, nseq, T, max_len, act, save);
   SIMX_REQUIRE(act_bytes >= cx.A.bytes, SIMX_ERR_WORKSPACE, "bert_fwd: activation buffer %zu < %zu", act_bytes, cx.A.bytes);
@@ -538,19 +559,27 @@ extern "C" int simx_bert_fwd(simx_stream_t stream, const simx_bert_cfg* c, const
   }
   const bool cls_only = c->cls_only_last_layer != 0;
   SIMX_REQUIRE(!(cls_only && hidden_out), SIMX_ERR_BAD_SHAPE, "bert_fwd: cls_only_last_layer leaves no full hidden state to return");
+  // a tap on the last layer is the embedding itself: computed once (into cls_out when the caller wants both), then copied
+  const int last_k = tap_slot(tap_layers, ntap, c->layers - 1);
+  float* last_tap = last_k >= 0 ? tap_cls + (size_t)last_k * nseq * H : nullptr;
+  float* emb_out = cls_out ? cls_out : last_tap;
   for (int l = 0; l < c->layers; ++l) {
     const ALayer a = alayer(c, cx.A, l);
     const bool cls_form = cls_only && l == c->layers - 1;
     // (checkpoint mode: the slot is recomputed by backward, so the forward runs it in its inference form)
-    RUN(layer_fwd(cx, l, x, a, save && !cx.A.ckpt, cls_form, cls_out));
-    if (cls_form) return SIMX_OK;
+    RUN(layer_fwd(cx, l, x, a, save && !cx.A.ckpt, cls_form, emb_out));
+    if (cls_form) break;
     x = XS{a.xout, a.xoutl, a.xoutp};
+    const int k = l < c->layers - 1 ? tap_slot(tap_layers, ntap, l) : -1;
+    if (k >= 0) RUN(cls_rows_out(cx, x, tap_cls + (size_t)k * nseq * H));
   }
-  if (cls_out) {
-    // (a stream_lo tower: the embeddings are f32(hi + correction byte), as the [CLS]-only last layer returns them -- the same
-    // precision whichever form the last layer ran in)
-    if (x.lo) RUN(simx_stream_rows(stream, dt, nseq, H, cu, x.hi, x.lo, nullptr, nullptr, cls_out));
-    else RUN(simx_cls_gather(stream, dt, nseq, H, cu, x.hi, cls_out));
+  // (a stream_lo tower: the embeddings are f32(hi + correction byte), as the [CLS]-only last layer returns them -- the same
+  // precision whichever form the last layer ran in)
+  if (emb_out && !cls_only) RUN(cls_rows_out(cx, x, emb_out));
+  if (last_tap && last_tap != emb_out &&
+      hipMemcpyAsync(last_tap, emb_out, (size_t)nseq * H * sizeof(float), hipMemcpyDeviceToDevice, cx.stream) != hipSuccess) {
+    simx_set_error("bert_fwd: copy of the last layer's tap failed");
+    return SIMX_ERR_HIP;
   }
   if (hidden_out) {
     if (hipMemcpyAsync(hidden_out, x.hi, (size_t)T * H * esz(dt), hipMemcpyDeviceToDevice, cx.stream) != hipSuccess) {
@@ -559,6 +588,19 @@ extern "C" int simx_bert_fwd(simx_stream_t stream, const simx_bert_cfg* c, const
     }
   }
   return SIMX_OK;
+}
+
+extern "C" int simx_bert_fwd(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
+                             const int32_t* ids, const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len,
+                             void* act, size_t act_bytes, int save, float* cls_out, void* hidden_out) {
+  return bert_fwd(stream, c, params, wcache, ids, pos_ids, cu, nseq, T, max_len, act, act_bytes, save, cls_out, hidden_out, nullptr, 0, nullptr);
+}
+extern "C" int simx_bert_fwd_taps(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
+                                  const int32_t* ids, const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len,
+                                  void* act, size_t act_bytes, int save, float* cls_out, void* hidden_out, const int32_t* tap_layers,
+                                  int ntap, float* tap_cls) {
+  return bert_fwd(stream, c, params, wcache, ids, pos_ids, cu, nseq, T, max_len, act, act_bytes, save, cls_out, hidden_out, tap_layers, ntap,
+                  tap_cls);
 }
 
 // ---- backward: the three layer forms, mirroring the forwards.  On entry s.bufB holds the gradient w.r.t. the layer's output, on
@@ -719,11 +761,12 @@ extern "C" int simx_bert_bwd_ex(simx_stream_t stream, const simx_bert_cfg* c, co
                              dhidden, grads, scratch, scratch_bytes, c ? c->layers - 1 : 0, 0);
 }
 
-extern "C" int simx_bert_bwd_range(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
-                                   const int32_t* ids, const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len,
-                                   void* act, size_t act_bytes, const float* dcls, const void* dhidden, float* grads,
-                                   void* scratch, size_t scratch_bytes, int layer_hi, int layer_lo) {
+static int bert_bwd_range(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache, const int32_t* ids,
+                          const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len, void* act, size_t act_bytes,
+                          const float* dcls, const void* dhidden, float* grads, void* scratch, size_t scratch_bytes, int layer_hi,
+                          int layer_lo, const int32_t* tap_layers, int ntap, const float* dtap_cls) {
   RUN(check_io(c, nseq, T, max_len, "bert_bwd"));
+  RUN(check_taps(c, tap_layers, ntap, dtap_cls, "bert_bwd"));
   SIMX_REQUIRE(params && wcache && ids && pos_ids && cu && act && grads && scratch, SIMX_ERR_BAD_SHAPE, "bert_bwd: NULL buffer");
   SIMX_REQUIRE(layer_hi < c->layers && layer_lo >= 0 && layer_lo <= layer_hi, SIMX_ERR_BAD_SHAPE, "bert_bwd: bad layer range %d..%d",
                layer_hi, layer_lo);
@@ -738,6 +781,24 @@ extern "C" int simx_bert_bwd_range(simx_stream_t stream, const simx_bert_cfg* c,
   const int H = c->hidden, dt = c->dtype;
   const bool pl = pl_run(c, cx.Tp, max_len);
 
+  // gradient of the tap on layer l (f32 [nseq,H]), NULL = none
+  auto dtap = [&](int l) -> const float* {
+    const int k = tap_slot(tap_layers, ntap, l);
+    return k >= 0 ? dtap_cls + (size_t)k * nseq * H : nullptr;
+  };
+  // a tap on the last layer is a second reader of the embedding: its gradient joins dcls in f32 before either enters the stack
+  // (the sum lives in dqkv, which no kernel writes before the attention backward of the first layer differentiated)
+  const float* dlast = top ? dtap(c->layers - 1) : nullptr;
+  if (dlast && dcls) {
+    float* sum = reinterpret_cast<float*>(s.dqkv);
+    if (hipMemcpyAsync(sum, dcls, (size_t)nseq * H * sizeof(float), hipMemcpyDeviceToDevice, cx.stream) != hipSuccess) {
+      simx_set_error("bert_bwd: copy of the embedding gradient failed");
+      return SIMX_ERR_HIP;
+    }
+    RUN(simx_cls_rows_add_gs(stream, SIMX_F32, nseq, H, nullptr, dlast, sum, nullptr));
+    dcls = sum;
+    dlast = nullptr;
+  }
   // the gradient w.r.t. the last hidden state -> bufB (the [CLS]-only last layer takes dcls itself)
   int l_top = layer_hi;
   if (top && c->cls_only_last_layer) {
@@ -750,10 +811,32 @@ extern "C" int simx_bert_bwd_range(simx_stream_t stream, const simx_bert_cfg* c,
   } else if (top) {
     RUN(simx_cls_scatter_gs(stream, dt, nseq, H, T, cu, dcls, s.bufB, cx.gs));            // g_x = d(loss)/d(last hidden)
   }
-  for (int l = l_top; l >= layer_lo; --l) RUN(pl ? layer_bwd_planes(cx, s, l) : layer_bwd_dense(cx, s, l));
+  if (dlast) RUN(simx_cls_rows_add_gs(stream, dt, nseq, H, cu, dlast, s.bufB, cx.gs));      // (dhidden form: no dcls to join)
+  for (int l = l_top; l >= layer_lo; --l) {
+    // the [CLS] rows of layer l's output have one more reader: += gs * dtap, before the layer is differentiated
+    const float* dt_l = l < c->layers - 1 ? dtap(l) : nullptr;
+    if (dt_l) RUN(simx_cls_rows_add_gs(stream, dt, nseq, H, cu, dt_l, s.bufB, cx.gs));
+    RUN(pl ? layer_bwd_planes(cx, s, l) : layer_bwd_dense(cx, s, l));
+  }
   if (layer_lo > 0) return SIMX_OK;               // the next part continues from bufB
   const simx_dropout d0 = drop_of(c, -1, 0);
   return simx_embed_ln_bwd_seq_gs(stream, dt, nseq, max_len, T, H, cu, ids, pos_ids, cx.p(-1, SIMX_P_WORD), cx.p(-1, SIMX_P_POS),
                                   cx.p(-1, SIMX_P_TYPE), cx.p(-1, SIMX_P_EMB_LN_G), c->eps, s.bufB, cx.g(-1, SIMX_P_WORD),
                                   cx.g(-1, SIMX_P_POS), cx.g(-1, SIMX_P_TYPE), cx.g(-1, SIMX_P_EMB_LN_G), cx.g(-1, SIMX_P_EMB_LN_B), &d0, cx.gs);
+}
+
+extern "C" int simx_bert_bwd_range(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
+                                   const int32_t* ids, const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len,
+                                   void* act, size_t act_bytes, const float* dcls, const void* dhidden, float* grads,
+                                   void* scratch, size_t scratch_bytes, int layer_hi, int layer_lo) {
+  return bert_bwd_range(stream, c, params, wcache, ids, pos_ids, cu, nseq, T, max_len, act, act_bytes, dcls, dhidden, grads, scratch,
+                        scratch_bytes, layer_hi, layer_lo, nullptr, 0, nullptr);
+}
+extern "C" int simx_bert_bwd_taps(simx_stream_t stream, const simx_bert_cfg* c, const float* params, const void* wcache,
+                                  const int32_t* ids, const int32_t* pos_ids, const int32_t* cu, int nseq, int T, int max_len,
+                                  void* act, size_t act_bytes, const float* dcls, const void* dhidden, float* grads,
+                                  void* scratch, size_t scratch_bytes, int layer_hi, int layer_lo, const int32_t* tap_layers,
+                                  int ntap, const float* dtap_cls) {
+  return bert_bwd_range(stream, c, params, wcache, ids, pos_ids, cu, nseq, T, max_len, act, act_bytes, dcls, dhidden, grads, scratch,
+                        scratch_bytes, layer_hi, layer_lo, tap_layers, ntap, dtap_cls);
 }

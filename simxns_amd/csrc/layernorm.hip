@@ -495,6 +495,19 @@ __global__ __launch_bounds__(256) void cls_scatter_kernel(int nseq, int H, const
   Elem<T>::st(dx + (long)cu[s] * H + c, dcls[i] * gs_scale(gs));
 }
 
+// x[cu ? cu[s] : s] += gs * add[s]: one more reader of a sequence's [CLS] row joins the gradient that is already there (the
+// [CLS] taps of simx_bert_bwd_taps).  One wave per sequence; every row has one writer.
+template <typename T>
+__global__ __launch_bounds__(256) void cls_rows_add_kernel(int nseq, int H, const int* __restrict__ cu, const float* __restrict__ add,
+                                                           T* __restrict__ x, const float* __restrict__ gs) {
+  const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= nseq) return;
+  T* xr = x + (long)(cu ? cu[s] : s) * H;
+  const float* ar = add + (long)s * H;
+  const float sc = gs_scale(gs);
+  for (int c = lane; c < H; c += 64) Elem<T>::st(xr + c, Elem<T>::ld(xr + c) + sc * ar[c]);
+}
+
 // dst[dst_idx ? dst_idx[s] : s] = src[src_idx ? src_idx[s] : s]   (row gather / scatter / dtype conversion)
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void rows_copy_kernel(int n, int H, const int* __restrict__ src_idx, const int* __restrict__ dst_idx,
@@ -877,6 +890,16 @@ extern "C" int simx_cls_scatter_gs(simx_stream_t stream, int dtype, int nseq, in
   const int blocks = (int)(((long)nseq * H + 255) / 256);
   SIMX_DISPATCH3(dtype, TT, hipLaunchKernelGGL((cls_scatter_kernel<TT>), dim3(blocks), dim3(256), 0, s, nseq, H, cu, dcls, (TT*)dx, gs));
   SIMX_CHECK_LAUNCH("cls_scatter");
+  return SIMX_OK;
+}
+
+extern "C" int simx_cls_rows_add_gs(simx_stream_t stream, int dtype, int nseq, int H, const int32_t* cu, const float* add, void* x,
+                                    const float* gs) {
+  SIMX_REQUIRE(nseq > 0 && H > 0 && add && x, SIMX_ERR_BAD_SHAPE, "cls_rows_add: bad arguments");
+  SIMX_REQUIRE(simx_dtype_ok(dtype), SIMX_ERR_BAD_DTYPE, "cls_rows_add: dtype %d", dtype);
+  hipStream_t s = (hipStream_t)stream;
+  SIMX_DISPATCH3(dtype, TT, hipLaunchKernelGGL((cls_rows_add_kernel<TT>), dim3(cdiv(nseq, 4)), dim3(256), 0, s, nseq, H, cu, add, (TT*)x, gs));
+  SIMX_CHECK_LAUNCH("cls_rows_add");
   return SIMX_OK;
 }
 

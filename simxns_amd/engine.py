@@ -234,6 +234,36 @@ class _EncoderFn(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class _EncoderTapsFn(torch.autograd.Function):
+    """[CLS] embeddings [n,H] and the [CLS] rows of the tapped layers' outputs [len(tap_layers),n,H], f32, both differentiable
+    (simx_bert_fwd_taps / simx_bert_bwd_taps)."""
+
+    @staticmethod
+    def forward(ctx, anchor, engine, pb, ccfg, tap_layers):
+        cls, taps, act = engine._run_forward(pb, True, False, ccfg, tap_layers)
+        engine._open_graphs += 1
+        ctx.engine, ctx.pb, ctx.act, ctx.ccfg, ctx.tap_layers = engine, pb, act, ccfg, tap_layers
+        return cls, taps
+
+    @staticmethod
+    def backward(ctx, g_cls, g_taps):
+        e = ctx.engine
+        if g_cls is None:
+            g_cls = torch.zeros(ctx.pb.nseq, e.cfg.hidden_size, dtype=torch.float32, device=e.flat.device)
+        taps = None if g_taps is None else (ctx.tap_layers, g_taps.contiguous().to(torch.float32))
+        e._run_backward(ctx.pb, ctx.act, dcls=g_cls, ccfg=ctx.ccfg, taps=taps)
+        ctx.act = None
+        return None, None, None, None, None
+
+
+def _tap_array(tap_layers, n_layers):
+    """Validated ctypes int32 array of the tapped layers (strictly ascending, in [0, n_layers))."""
+    t = [int(l) for l in tap_layers]
+    if not t or any(l < 0 or l >= n_layers for l in t) or any(b <= a for a, b in zip(t, t[1:])):
+        raise ValueError("tap_layers %r: need strictly ascending layer indices in [0, %d)" % (list(tap_layers), n_layers))
+    return (C.c_int32 * len(t))(*t)
+
+
 class BertEngine(object):
     """One BERT tower on one GPU."""
 
@@ -364,7 +394,8 @@ class BertEngine(object):
             c.dropout_seed = (self.dropout_seed * 0x9E3779B1 + self._drop_calls * 0x85EBCA6B) & 0xFFFFFFFF
         return c
 
-    def _run_forward(self, pb, save, want_hidden, ccfg=None):
+    def _run_forward(self, pb, save, want_hidden, ccfg=None, tap_layers=None):
+        """-> (cls, hidden, act); with ``tap_layers`` (a _tap_array) -> (cls, taps [len,n,H] f32, act)."""
         self._require_gpu()
         self._refresh_wcache()
         ccfg = ccfg if ccfg is not None else self.ccfg
@@ -375,6 +406,12 @@ class BertEngine(object):
         nbytes = int(self.lib.simx_bert_act_bytes(C.byref(self.ccfg), pb.nseq * pb.S, pb.nseq, 1 if save else 0))
         act = self._alloc_act(nbytes, dev, save)
         cls = torch.empty(pb.nseq, H, dtype=torch.float32, device=dev)
+        if tap_layers is not None:
+            taps = torch.empty(len(tap_layers), pb.nseq, H, dtype=torch.float32, device=dev)
+            L.call("simx_bert_fwd_taps", L.stream_ptr(), C.byref(ccfg), L.ptr(self.flat), L.ptr(self.wcache),
+                   L.ptr(pb.ids), L.ptr(pb.pos), L.ptr(pb.cu), pb.nseq, pb.T, pb.max_len, L.ptr(act), nbytes,
+                   1 if save else 0, L.ptr(cls), None, tap_layers, len(tap_layers), L.ptr(taps))
+            return cls, taps, (act if save else None)
         hidden = torch.empty(pb.T, H, dtype=self.act_torch_dtype, device=dev) if want_hidden else None
         L.call("simx_bert_fwd", L.stream_ptr(), C.byref(ccfg), L.ptr(self.flat), L.ptr(self.wcache),
                L.ptr(pb.ids), L.ptr(pb.pos), L.ptr(pb.cu), pb.nseq, pb.T, pb.max_len, L.ptr(act), nbytes,
@@ -415,7 +452,8 @@ class BertEngine(object):
                L.ptr(self.grad_scale_state()))
         return dh
 
-    def _run_backward(self, pb, act, dcls=None, ccfg=None, dhidden=None):
+    def _run_backward(self, pb, act, dcls=None, ccfg=None, dhidden=None, taps=None):
+        """taps = (tap_layers, dtaps f32 [len,n,H]): the gradients of a tapped forward's [CLS] rows."""
         ccfg = ccfg if ccfg is not None else self.ccfg
         if self._reduced_this_step:
             raise L.SimxError("backward into a gradient buffer whose slices were already all-reduced for this optimiser step: "
@@ -441,9 +479,12 @@ class BertEngine(object):
         end = self.n_params
         for i in range(parts):
             hi, lo = bounds[i], bounds[i + 1] + 1
-            L.call("simx_bert_bwd_range", L.stream_ptr(), C.byref(ccfg), L.ptr(self.flat), L.ptr(self.wcache),
-                   L.ptr(pb.ids), L.ptr(pb.pos), L.ptr(pb.cu), pb.nseq, pb.T, pb.max_len, L.ptr(act), act.numel(),
-                   L.ptr(dcls), L.ptr(dhidden), L.ptr(g), L.ptr(scratch), nbytes, hi, lo)
+            args = (L.stream_ptr(), C.byref(ccfg), L.ptr(self.flat), L.ptr(self.wcache), L.ptr(pb.ids), L.ptr(pb.pos), L.ptr(pb.cu),
+                    pb.nseq, pb.T, pb.max_len, L.ptr(act), act.numel(), L.ptr(dcls), L.ptr(dhidden), L.ptr(g), L.ptr(scratch), nbytes, hi, lo)
+            if taps is None:
+                L.call("simx_bert_bwd_range", *args)
+            else:                                    # (every part gets all taps: a part applies those inside its range)
+                L.call("simx_bert_bwd_taps", *args, taps[0], len(taps[0]), L.ptr(taps[1]))
             if hook is not None:
                 start = 0 if lo == 0 else int(self.lib.simx_bert_param_offset(C.byref(self.ccfg), lo, L.P_WQKV))
                 hook(self, start, end)
@@ -451,14 +492,26 @@ class BertEngine(object):
         if self.after_backward is not None:
             self.after_backward()
 
-    def encode(self, input_ids, attention_mask, want_hidden=False, requires_grad=None, training=False, pool=None):
+    def encode(self, input_ids, attention_mask, want_hidden=False, requires_grad=None, training=False, pool=None, tap_layers=None):
         """-> cls [n,H] f32; with want_hidden also the packed last hidden state + PackedBatch (both outputs carry
-        gradient); pool="mean" -> the masked mean over each sequence's real tokens [n,H] f32 instead of [CLS]."""
+        gradient); pool="mean" -> the masked mean over each sequence's real tokens [n,H] f32 instead of [CLS];
+        tap_layers (a list of ascending layer indices) -> (cls, taps): taps f32 [len,n,H] holds the [CLS] rows of those
+        layers' outputs, both differentiable."""
         pool = pool or ("hidden" if want_hidden else "cls")
+        if tap_layers is not None and pool != "cls":
+            raise ValueError("tap_layers come with the [CLS] embedding only (pool %r)" % pool)
         pb = PackedBatch(input_ids, attention_mask, getattr(self.cfg, "position_offset", 0))
         ccfg = self.call_cfg(training, pool != "cls")
         if requires_grad is None:
             requires_grad = torch.is_grad_enabled()
+        if tap_layers is not None:
+            tl = _tap_array(tap_layers, self.cfg.num_hidden_layers)
+            if requires_grad and torch.is_grad_enabled():
+                if self.anchor.device != self.flat.device:
+                    self.anchor = torch.zeros((), requires_grad=True, device=self.flat.device)
+                return _EncoderTapsFn.apply(self.anchor, self, pb, ccfg, tl)
+            cls, taps, _ = self._run_forward(pb, False, False, ccfg, tl)
+            return cls, taps
         if requires_grad and torch.is_grad_enabled():
             if self.anchor.device != self.flat.device:
                 self.anchor = torch.zeros((), requires_grad=True, device=self.flat.device)

@@ -167,6 +167,14 @@ class HFBertEncoder(nn.Module):
         """Fast path used by BiBertEncoder / Reranker: [CLS] embeddings [n,H] f32 only."""
         return self.engine.encode(input_ids, attention_mask, training=self.training)
 
+    def embed_layers(self, input_ids, attention_mask, layers):
+        """-> ([CLS] embeddings [n,H], [CLS] rows of the outputs of encoder layers ``layers`` [len,n,H]), f32, both
+        differentiable: what LEAD's layer-score distillation reads of all_hidden_states (LEAD/modeling_bert.py:575-646)."""
+        out = self.engine.encode(input_ids, attention_mask, training=self.training, tap_layers=layers)
+        if self.engine.flat_grad is not None:
+            self.attach_grads()
+        return out
+
     def embed_mean(self, input_ids, attention_mask):
         """EmbeddingMixin.masked_mean (models.py:296-299): mean of the last hidden state over each sequence's real tokens,
         [n,H] f32, computed on the packed layout (no padded sequence_output is materialised)."""

@@ -219,6 +219,72 @@ def fused_normal_inbatch_loss(q, ctx_vectors, reranker_logits, positive_idx_per_
     return loss_n + inbatch_weight * nll / grad_accum, normal, nll, correct
 
 
+# ------------------------------------------------------------------------------------------ L7 (LEAD)
+class _LeadScoresFn(torch.autograd.Function):
+    """simx_lead_scores_fwd_bwd: n slots of student / teacher all-pairs scores, gradients for all four inputs."""
+
+    @staticmethod
+    def forward(ctx, q, c, tq, tc, pos_idx, slots, T, LT, teacher_grad, loss_scale, q_lo, q_n, c_lo, c_n):
+        q, c, tq, tc = _f32c(q), _f32c(c), _f32c(tq), _f32c(tc)
+        n, Q, H = q.shape
+        Cn, HT = c.shape[1], tq.shape[2]
+        dev = q.device
+        pos = torch.as_tensor(pos_idx, dtype=torch.int32, device=dev).contiguous()
+        e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+        scores, tscores, slot_losses, weights, total = e(n, Q, Cn), e(n, Q, Cn), e(n, 4), e(n), e(1)
+        dq, dc = e(n, q_n, H), e(n, c_n, H)
+        dtq, dtc = (e(n, q_n, HT), e(n, c_n, HT)) if teacher_grad else (None, None)
+        wsb = int(L.load().simx_lead_scores_workspace_bytes(n, Q, Cn, H, HT, q_n, c_n))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        L.call("simx_lead_scores_fwd_bwd", L.stream_ptr(), n, Q, Cn, H, HT, L.ptr(q), L.ptr(c), L.ptr(tq), L.ptr(tc), L.ptr(pos),
+               float(T), float(LT), slots, int(bool(teacher_grad)), float(loss_scale or 1.0), q_lo, q_n, c_lo, c_n,
+               L.ptr(scores), L.ptr(tscores), L.ptr(slot_losses), L.ptr(weights), L.ptr(total), L.ptr(dq), L.ptr(dc),
+               L.ptr(dtq), L.ptr(dtc), L.ptr(ws), wsb)
+        ctx.slots_lo = (q_lo, Q, c_lo, Cn)
+        ctx.save_for_backward(*(t for t in (dq, dc, dtq, dtc) if t is not None))
+        ctx.mark_non_differentiable(slot_losses, weights)
+        return total[0], slot_losses, weights
+
+    @staticmethod
+    def backward(ctx, g, g_slots, g_weights):
+        q_lo, Q, c_lo, Cn = ctx.slots_lo
+
+        def full(d, lo, rows):                          # the local rows' gradient inside the gathered tensor's
+            if d.shape[1] == rows:
+                return d * g
+            out = torch.zeros(d.shape[0], rows, d.shape[2], dtype=d.dtype, device=d.device)
+            out[:, lo:lo + d.shape[1]] = d * g
+            return out
+        saved = ctx.saved_tensors
+        dq, dc = full(saved[0], q_lo, Q), full(saved[1], c_lo, Cn)
+        dtq, dtc = (full(saved[2], q_lo, Q), full(saved[3], c_lo, Cn)) if len(saved) == 4 else (None, None)
+        return (dq, dc, dtq, dtc) + (None,) * 10
+
+
+def lead_layer_score_loss(q, ctx, tq, tctx, positive_idx, slots, temperature, layer_temperature, teacher_grad=True,
+                          loss_scale=None, local_q=None, local_ctx=None):
+    """The slot objective of LEAD's distill_loss (LEAD/util.py:540-831; simx_lead_scores_fwd_bwd in include/simx.h) in one call:
+    q [n,Q,H], ctx [n,C,H] the student's and tq [n,Q,HT], tctx [n,C,HT] the teacher's vectors of n slots; ``slots`` a list of
+    n (a, b, w, x, reweight) = the weights of nll_s, nll_t, kl_ts, kl_st and whether w is the layer-score softmax weight.
+    -> (total, slot_losses [n,4], weights [n]); only ``total`` is differentiable, towards the teacher only with
+    ``teacher_grad``.  local_q / local_ctx = (lo, n): the rows that carry gradient, as in inbatch_nll_loss."""
+    if q.dim() != 3 or ctx.dim() != 3 or tq.dim() != 3 or tctx.dim() != 3:
+        raise ValueError("lead_layer_score_loss: q, ctx, tq, tctx must be [n, rows, width]")
+    n = q.shape[0]
+    if not (ctx.shape[0] == tq.shape[0] == tctx.shape[0] == n and tq.shape[1] == q.shape[1] and tctx.shape[1] == ctx.shape[1]
+            and ctx.shape[2] == q.shape[2] and tctx.shape[2] == tq.shape[2]):
+        raise ValueError("lead_layer_score_loss: shapes %s %s %s %s do not form n slots of Q x C scores"
+                         % (tuple(q.shape), tuple(ctx.shape), tuple(tq.shape), tuple(tctx.shape)))
+    if len(slots) != n or not 1 <= n <= L.LEAD_MAX_SLOTS:
+        raise ValueError("lead_layer_score_loss: %d slot weights for %d slots (1..%d)" % (len(slots), n, L.LEAD_MAX_SLOTS))
+    arr = (L.LeadSlot * n)(*[L.LeadSlot(float(a), float(b), float(w), float(x), int(bool(rw))) for a, b, w, x, rw in slots])
+    q_lo, q_n, c_lo, c_n = _slots(q[0], ctx[0], local_q, local_ctx)
+    if not teacher_grad:
+        tq, tctx = tq.detach(), tctx.detach()
+    return _LeadScoresFn.apply(q, ctx, tq, tctx, positive_idx, arr, temperature, layer_temperature, bool(teacher_grad), loss_scale,
+                               q_lo, q_n, c_lo, c_n)
+
+
 def dot_product_scores(q_vectors, ctx_vectors):
     """q @ ctx^T on the strided f32 GEMM kernel (no grad; the training path uses inbatch_nll_loss)."""
     q, c = _f32c(q_vectors.detach()), _f32c(ctx_vectors.detach())
