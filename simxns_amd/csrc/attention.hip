@@ -1,47 +1,21 @@
 // Fused multi-head self-attention (BertSelfAttention core, LEAD/modeling_bert.py:318-374) on the
 // packed token layout, forward and backward, for gfx950.
 //
-// bf16 / head_dim 64 path (MFMA 16x16x32):
-//   one workgroup (4 waves) per (sequence, head); that head's K and V (forward) or Q, K, V, dO
-//   (backward) are staged ONCE into LDS by global_load_lds and stay resident (S <= 512 forward,
-//   S <= 256 backward: 160 KB LDS per CU);  scores are produced TRANSPOSED (keys x queries) so that
-//   the softmax row of a query lives in one lane column and the probabilities feed the second MFMA
+// bf16 / fp16, head_dim 64 path (MFMA 16x16x32):
+//   S <= 256, forward and backward: one workgroup (4 waves) per (sequence, head); that head's K and V (forward) or
+//   Q, K, V, dO (backward) are staged ONCE into LDS by LDS-DMA and stay resident (2 / 8 / 10 / 16 tiles of 16 tokens for
+//   S <= 32 / 128 / 160 / 256: 160 KB LDS per CU);  256 < S <= 4096: 128-token chunks, one workgroup per (sequence, head,
+//   chunk), online softmax forward, dQ and dK / dV as two launches backward.  Scores are produced TRANSPOSED (keys x
+//   queries) so that the softmax row of a query lives in one lane column and the probabilities feed the second MFMA
 //   straight from registers; the operand whose contraction index is the LDS row index (V in PV,
 //   K in dS.K, dO / Q in the dV / dK products) is fetched with ds_read_b64_tr_b16.
-//   LDS image: 128-B rows, 16-B chunk c of row r stored at chunk c ^ f((r>>1)&7), f = (0,2,4,6,5,7,1,3):
-//   conflict-free for both the ds_read_b128 row-fragment pattern and the transpose-read pattern.
-// generic path (f32 parity mode, other head dims, longer sequences): one wave per query / key row.
+//   LDS image, its stager and fragment reads: att.h.
+// f32 with head_dim 64: attention_f32.hip.  generic path (other head dims, SIMX_MHA_F32=generic): one wave per query / key row.
 //
 // Keys are restricted to the sequence's own real tokens, which equals the reference's additive
 // (1-mask)*finfo.min bias (exp underflows to exactly 0).
-#include <type_traits>
-#include "common.h"
+#include "att.h"
 #include "prof.h"
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-#define LOG2E 1.4426950408889634f
-
-__device__ __forceinline__ int att_f(int row) {
-  const int i = (row >> 1) & 7;
-  return (((i << 1) & 7) + (i >> 2) * 5) & 7;
-}
-__device__ __forceinline__ int att_off(int row, int c16) { return row * 128 + ((c16 ^ att_f(row)) << 4); }
-
-// stage rows [0, rows_pad) x 64 bf16 of one head slice; rows >= len are clamped copies of row len-1
-__device__ __forceinline__ void att_stage(const bf16_t* __restrict__ G, int ld, int len, int rows_pad, char* lds,
-                                          int wave, int lane) {
-  for (int i = wave; i < (rows_pad >> 3); i += 4) {
-    const int r = i * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ att_f(r);
-    const int gr = r < len ? r : len - 1;
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(G + (long)gr * ld + c * 8), (lds_ptr_t)(lds + i * 1024), 16, 0, 0);
-  }
-}
-
-__device__ __forceinline__ bf16x8 lds_row_frag(const char* tile, int row, int c16) {
-  return *reinterpret_cast<const bf16x8*>(tile + att_off(row, c16));
-}
 
 // In the MFMA kernels below `bf16_t` is the raw 16-bit storage of EITHER operand format; the template parameter
 // F in {bf16_t, f16_t} (H16<F>, common.h) selects the conversions and the MFMA instruction.
@@ -77,6 +51,10 @@ __device__ __forceinline__ P* qkv_head(P* base, int heads, int h, int t0, int hm
 // query-tile loop without uniform branches: with them hipcc emitted one key tile at a time, ds_read -> wait -> two MFMAs -> wait
 // -> its share of the row maximum; as ONE basic block the sixteen QK^T MFMAs of a query tile issue back to back.  Dropout on /
 // off is a template parameter for the same reason.)
+// LDS: K | V, each NKT * 16 rows of 128 B
+template <int NKT>
+struct FwdLds { static constexpr int TILE = NKT * 16 * 128, OFF_K = 0, OFF_V = TILE, BYTES = 2 * TILE; };
+
 template <typename F, int NKT, bool DROP>
 __global__ __launch_bounds__(256, (NKT <= 8 ? 4 : NKT <= 10 ? 3 : NKT <= 16 ? 2 : 1)) void mha_fwd_h16_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                            float* __restrict__ lse, const int* __restrict__ cu,
@@ -95,23 +73,18 @@ __global__ __launch_bounds__(256, (NKT <= 8 ? 4 : NKT <= 10 ? 3 : NKT <= 16 ? 2 
   const bf16_t* Vg = Kg + lay.ws;
   const int nkt = (len + 15) >> 4;
   const int nkt2 = (nkt + 1) & ~1;
-  char* sK = smem;
-  char* sV = smem + NKT * 16 * 128;
-  att_stage(Kg, H3, len, nkt2 * 16, sK, wave, lane);
-  att_stage(Vg, H3, len, nkt2 * 16, sV, wave, lane);
+  using Lds = FwdLds<NKT>;
+  char* sK = smem + Lds::OFF_K;
+  char* sV = smem + Lds::OFF_V;
+  att_stage(Kg, H3, len, nkt2 * 16, sK, wave, lane, 4);
+  att_stage(Vg, H3, len, nkt2 * 16, sV, wave, lane, 4);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   const uint32_t sV_addr = (uint32_t)(uintptr_t)sV;
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * LOG2E;
-#define F2_RDTR(DST, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=&v"(DST) : "v"(ADDR) : "memory")
-#define F2_CAT(LO, HI) ((bf16x8){LO[0], LO[1], LO[2], LO[3], HI[0], HI[1], HI[2], HI[3]})
-  uint32_t vtr[4];                                 // transpose-fragment lane constants (see mha_bwd2_bf16_kernel)
-  {
-    const int rr = 4 * fg + (fr >> 2), tsw = att_f(rr), tx = (fr & 3) >> 1;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vtr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
-  }
+  const float c2 = scale * ATT_LOG2E;
+  uint32_t vtr[4];                                 // transpose-fragment lane constants
+  ATT_VTR(fr, fg, vtr);
 
   auto tiles = [&](auto allt_c) {
   constexpr bool ALLT = decltype(allt_c)::value;
@@ -127,8 +100,8 @@ __global__ __launch_bounds__(256, (NKT <= 8 ? 4 : NKT <= 10 ? 3 : NKT <= 16 ? 2 
     for (int kt = 0; kt < NKT; ++kt) {
       if (ALLT || kt < nkt) {
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        a = H16<F>::mfma(lds_row_frag(sK, kt * 16 + fr, fg), qf[0], a);
-        a = H16<F>::mfma(lds_row_frag(sK, kt * 16 + fr, 4 + fg), qf[1], a);
+        a = H16<F>::mfma(att_row_frag(sK, kt * 16 + fr, fg), qf[0], a);
+        a = H16<F>::mfma(att_row_frag(sK, kt * 16 + fr, 4 + fg), qf[1], a);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = kt * 16 + 4 * fg + r;
@@ -175,11 +148,11 @@ __global__ __launch_bounds__(256, (NKT <= 8 ? 4 : NKT <= 10 ? 3 : NKT <= 16 ? 2 
       if (ALLT || 2 * kb < nkt) {
         const uint32_t b0 = sV_addr + (uint32_t)(kb * 4096);
         bf16x4 a0l, a0h, a1l, a1h, a2l, a2h, a3l, a3h, c0l, c0h, c1l, c1h, c2l, c2h, c3l, c3h;
-        F2_RDTR(a0l, b0 + vtr[0], 0); F2_RDTR(a0h, b0 + vtr[0], 2048); F2_RDTR(a1l, b0 + vtr[1], 0); F2_RDTR(a1h, b0 + vtr[1], 2048);
-        F2_RDTR(a2l, b0 + vtr[2], 0); F2_RDTR(a2h, b0 + vtr[2], 2048); F2_RDTR(a3l, b0 + vtr[3], 0); F2_RDTR(a3h, b0 + vtr[3], 2048);
+        ATT_RDTR(a0l, b0 + vtr[0], 0); ATT_RDTR(a0h, b0 + vtr[0], 2048); ATT_RDTR(a1l, b0 + vtr[1], 0); ATT_RDTR(a1h, b0 + vtr[1], 2048);
+        ATT_RDTR(a2l, b0 + vtr[2], 0); ATT_RDTR(a2h, b0 + vtr[2], 2048); ATT_RDTR(a3l, b0 + vtr[3], 0); ATT_RDTR(a3h, b0 + vtr[3], 2048);
         if (kb + 1 < NKT / 2) {                       // compile-time: the second pair's slots exist in the LDS tile
-          F2_RDTR(c0l, b0 + vtr[0], 4096); F2_RDTR(c0h, b0 + vtr[0], 6144); F2_RDTR(c1l, b0 + vtr[1], 4096); F2_RDTR(c1h, b0 + vtr[1], 6144);
-          F2_RDTR(c2l, b0 + vtr[2], 4096); F2_RDTR(c2h, b0 + vtr[2], 6144); F2_RDTR(c3l, b0 + vtr[3], 4096); F2_RDTR(c3h, b0 + vtr[3], 6144);
+          ATT_RDTR(c0l, b0 + vtr[0], 4096); ATT_RDTR(c0h, b0 + vtr[0], 6144); ATT_RDTR(c1l, b0 + vtr[1], 4096); ATT_RDTR(c1h, b0 + vtr[1], 6144);
+          ATT_RDTR(c2l, b0 + vtr[2], 4096); ATT_RDTR(c2h, b0 + vtr[2], 6144); ATT_RDTR(c3l, b0 + vtr[3], 4096); ATT_RDTR(c3h, b0 + vtr[3], 6144);
           // (ONE wait names every register an asm read above is still filling: a register the wait does not name may be copied
           // by the compiler before it)
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0l), "+v"(a0h), "+v"(a1l), "+v"(a1h), "+v"(a2l), "+v"(a2h), "+v"(a3l), "+v"(a3h),
@@ -188,17 +161,17 @@ __global__ __launch_bounds__(256, (NKT <= 8 ? 4 : NKT <= 10 ? 3 : NKT <= 16 ? 2 
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0l), "+v"(a0h), "+v"(a1l), "+v"(a1h), "+v"(a2l), "+v"(a2h), "+v"(a3l), "+v"(a3h)::"memory");
         }
         const bf16x8 pf = pack8<F>(s[2 * kb], s[2 * kb + 1]);
-        o[0] = H16<F>::mfma(F2_CAT(a0l, a0h), pf, o[0]);
-        o[1] = H16<F>::mfma(F2_CAT(a1l, a1h), pf, o[1]);
-        o[2] = H16<F>::mfma(F2_CAT(a2l, a2h), pf, o[2]);
-        o[3] = H16<F>::mfma(F2_CAT(a3l, a3h), pf, o[3]);
+        o[0] = H16<F>::mfma(ATT_CAT(a0l, a0h), pf, o[0]);
+        o[1] = H16<F>::mfma(ATT_CAT(a1l, a1h), pf, o[1]);
+        o[2] = H16<F>::mfma(ATT_CAT(a2l, a2h), pf, o[2]);
+        o[3] = H16<F>::mfma(ATT_CAT(a3l, a3h), pf, o[3]);
         if (kb + 1 < NKT / 2) {
           if (ALLT || 2 * (kb + 1) < nkt) {           // rows past the padded length are uninitialised LDS: skip, never multiply
             const bf16x8 pg = pack8<F>(s[2 * kb + 2], s[2 * kb + 3]);
-            o[0] = H16<F>::mfma(F2_CAT(c0l, c0h), pg, o[0]);
-            o[1] = H16<F>::mfma(F2_CAT(c1l, c1h), pg, o[1]);
-            o[2] = H16<F>::mfma(F2_CAT(c2l, c2h), pg, o[2]);
-            o[3] = H16<F>::mfma(F2_CAT(c3l, c3h), pg, o[3]);
+            o[0] = H16<F>::mfma(ATT_CAT(c0l, c0h), pg, o[0]);
+            o[1] = H16<F>::mfma(ATT_CAT(c1l, c1h), pg, o[1]);
+            o[2] = H16<F>::mfma(ATT_CAT(c2l, c2h), pg, o[2]);
+            o[3] = H16<F>::mfma(ATT_CAT(c3l, c3h), pg, o[3]);
           }
         }
       }
@@ -241,17 +214,14 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_long_h16_kernel(const bf16_t* 
   const bf16_t* Kg = Qg + lay.ws;
   const bf16_t* Vg = Kg + lay.ws;
   const int nkc = (len + 127) >> 7;
-  char* sK = smem;
-  char* sV = smem + 16384;
+  using Lds = FwdLds<8>;                             // K and V of one 128-key chunk
+  char* sK = smem + Lds::OFF_K;
+  char* sV = smem + Lds::OFF_V;
   const uint32_t sV_addr = (uint32_t)(uintptr_t)sV;
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   uint32_t vtr[4];
-  {
-    const int rr = 4 * fg + (fr >> 2), tsw = att_f(rr), tx = (fr & 3) >> 1;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vtr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
-  }
+  ATT_VTR(fr, fg, vtr);
   bf16x8 qf[2][2];
   f32x4 o[2][4];
   float mrun[2], lrun[2];
@@ -271,8 +241,8 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_long_h16_kernel(const bf16_t* 
     const int nk = len - k0 < 128 ? len - k0 : 128;
     const int nkt = (nk + 15) >> 4, nkt2 = (nkt + 1) & ~1;
     __syncthreads();                                 // every wave is done with the previous chunk's tiles
-    att_stage(Kg + (long)k0 * H3, H3, nk, nkt2 * 16, sK, wave, lane);
-    att_stage(Vg + (long)k0 * H3, H3, nk, nkt2 * 16, sV, wave, lane);
+    att_stage(Kg + (long)k0 * H3, H3, nk, nkt2 * 16, sK, wave, lane, 4);
+    att_stage(Vg + (long)k0 * H3, H3, nk, nkt2 * 16, sV, wave, lane, 4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     auto chunk = [&](auto allt_c) {
@@ -287,8 +257,8 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_long_h16_kernel(const bf16_t* 
         for (int kt = 0; kt < 8; ++kt) {
           if (ALLT || kt < nkt) {
             f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            a = H16<F>::mfma(lds_row_frag(sK, kt * 16 + fr, fg), qf[j][0], a);
-            a = H16<F>::mfma(lds_row_frag(sK, kt * 16 + fr, 4 + fg), qf[j][1], a);
+            a = H16<F>::mfma(att_row_frag(sK, kt * 16 + fr, fg), qf[j][0], a);
+            a = H16<F>::mfma(att_row_frag(sK, kt * 16 + fr, 4 + fg), qf[j][1], a);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               if (!ALLT) a[r] = k0 + kt * 16 + 4 * fg + r < len ? a[r] : -INFINITY;
@@ -335,14 +305,14 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_long_h16_kernel(const bf16_t* 
           if (ALLT || 2 * kb < nkt) {                  // (rows past the padded length are uninitialised LDS: never multiplied)
             const uint32_t b0 = sV_addr + (uint32_t)(kb * 4096);
             bf16x4 a0l, a0h, a1l, a1h, a2l, a2h, a3l, a3h;
-            F2_RDTR(a0l, b0 + vtr[0], 0); F2_RDTR(a0h, b0 + vtr[0], 2048); F2_RDTR(a1l, b0 + vtr[1], 0); F2_RDTR(a1h, b0 + vtr[1], 2048);
-            F2_RDTR(a2l, b0 + vtr[2], 0); F2_RDTR(a2h, b0 + vtr[2], 2048); F2_RDTR(a3l, b0 + vtr[3], 0); F2_RDTR(a3h, b0 + vtr[3], 2048);
+            ATT_RDTR(a0l, b0 + vtr[0], 0); ATT_RDTR(a0h, b0 + vtr[0], 2048); ATT_RDTR(a1l, b0 + vtr[1], 0); ATT_RDTR(a1h, b0 + vtr[1], 2048);
+            ATT_RDTR(a2l, b0 + vtr[2], 0); ATT_RDTR(a2h, b0 + vtr[2], 2048); ATT_RDTR(a3l, b0 + vtr[3], 0); ATT_RDTR(a3h, b0 + vtr[3], 2048);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0l), "+v"(a0h), "+v"(a1l), "+v"(a1h), "+v"(a2l), "+v"(a2h), "+v"(a3l), "+v"(a3h)::"memory");
             const bf16x8 pf = pack8<F>(s[2 * kb], s[2 * kb + 1]);
-            o[j][0] = H16<F>::mfma(F2_CAT(a0l, a0h), pf, o[j][0]);
-            o[j][1] = H16<F>::mfma(F2_CAT(a1l, a1h), pf, o[j][1]);
-            o[j][2] = H16<F>::mfma(F2_CAT(a2l, a2h), pf, o[j][2]);
-            o[j][3] = H16<F>::mfma(F2_CAT(a3l, a3h), pf, o[j][3]);
+            o[j][0] = H16<F>::mfma(ATT_CAT(a0l, a0h), pf, o[j][0]);
+            o[j][1] = H16<F>::mfma(ATT_CAT(a1l, a1h), pf, o[j][1]);
+            o[j][2] = H16<F>::mfma(ATT_CAT(a2l, a2h), pf, o[j][2]);
+            o[j][3] = H16<F>::mfma(ATT_CAT(a3l, a3h), pf, o[j][3]);
           }
         }
       }
@@ -375,12 +345,6 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_long_h16_kernel(const bf16_t* 
 //   * delta = dO.O uses 16-B loads, two threads per row;
 //   * dQ / dK / dV leave through a 2 KB per-wave LDS patch as 16 B per lane = full 128-B (token, head) lines
 //     instead of 8-B stores (32-B segments).
-#define A2_RD128(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=&v"(DST) : "v"(ADDR) : "memory")
-#define A2_RDTR(DST, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=&v"(DST) : "v"(ADDR) : "memory")
-#define A2_RD128O(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
-#define A2_RDTRO(DST, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=&v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
-#define A2_CAT(LO, HI) ((bf16x8){LO[0], LO[1], LO[2], LO[3], HI[0], HI[1], HI[2], HI[3]})
-
 // stage a wave's 16x64 tile (MFMA layout: lane = row fr, 4 columns dt*16 + 4*fg) through its 2 KB LDS patch and store it
 // as full 128-B lines: rows t_row0 + r (r < nrows valid), column block h*64 of a [.., ld] bf16 matrix
 template <typename F>
@@ -427,6 +391,19 @@ __device__ __forceinline__ void a2_store_tile(const f32x4 (&acc)[4], char* patch
 //     adjacent LDS tiles and share one address register (the second through the instruction's immediate offset): 8
 //     address additions per iteration instead of 20;
 //   * 1/sqrt(d) multiplies the finished dQ / dK tiles, not every dS element.
+// LDS: Q | dO | K | V tiles (the V tile is last: absent with VG), then
+//   VEC: lse[NKT*16], delta[NKT*16] (f32);  MSK: dropout bits [key tile][query], 16 bits = the keys of the tile;
+//   PATCH: 2 KB per wave for the stores
+template <int NKT, bool VG>
+struct Bwd2Lds {
+  static constexpr int TILE = NKT * 16 * 128;
+  static constexpr int OFF_Q = 0, OFF_D = TILE, OFF_K = 2 * TILE, OFF_V = 3 * TILE;
+  static constexpr int VEC = (VG ? 3 : 4) * TILE;
+  static constexpr int MSK = VEC + 2 * NKT * 16 * 4;
+  static constexpr int PATCH = MSK + NKT * 16 * NKT * 2;
+  static constexpr int BYTES = PATCH + 4 * 2048;
+};
+
 template <typename F, int NKT, bool VG, bool DROP>
 __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ O,
                                                             const float* __restrict__ lse, const bf16_t* __restrict__ dO,
@@ -449,18 +426,16 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
   const bf16_t* dOg = dO + (long)t0 * H + h * 64;
   const int nkt = (len + 15) >> 4;
   const int nkt2 = (nkt + 1) & ~1;
-  constexpr int TILE = NKT * 16 * 128;
-  constexpr int OFF_Q = 0, OFF_D = TILE, OFF_K = 2 * TILE, OFF_V = 3 * TILE;      // (the V tile is last: absent with VG)
-  constexpr int VEC = (VG ? 3 : 4) * TILE;           // lse[NKT*16], delta[NKT*16] (f32)
-  constexpr int MSK = VEC + 2 * NKT * 16 * 4;        // dropout bits [key tile][query]: 16 bits = the keys of the tile
-  constexpr int PATCH = MSK + NKT * 16 * NKT * 2;
+  using Lds = Bwd2Lds<NKT, VG>;
+  constexpr int OFF_Q = Lds::OFF_Q, OFF_D = Lds::OFF_D, OFF_K = Lds::OFF_K, OFF_V = Lds::OFF_V;
+  constexpr int VEC = Lds::VEC, MSK = Lds::MSK, PATCH = Lds::PATCH;
   float* sLse = reinterpret_cast<float*>(smem + VEC);
   float* sDel = sLse + NKT * 16;
   char* patch = smem + PATCH + wave * 2048;
-  att_stage(Qg, H3, len, nkt2 * 16, smem + OFF_Q, wave, lane);
-  att_stage(Kg, H3, len, nkt2 * 16, smem + OFF_K, wave, lane);
-  if (!VG) att_stage(Vg, H3, len, nkt2 * 16, smem + OFF_V, wave, lane);
-  att_stage(dOg, H, len, nkt2 * 16, smem + OFF_D, wave, lane);
+  att_stage(Qg, H3, len, nkt2 * 16, smem + OFF_Q, wave, lane, 4);
+  att_stage(Kg, H3, len, nkt2 * 16, smem + OFF_K, wave, lane, 4);
+  if (!VG) att_stage(Vg, H3, len, nkt2 * 16, smem + OFF_V, wave, lane, 4);
+  att_stage(dOg, H, len, nkt2 * 16, smem + OFF_D, wave, lane, 4);
   // delta_i = dO_i . O_i (two threads per row, 16-B loads) ; lse_i in log2 units
   for (int idx = tid; idx < nkt2 * 32; idx += 256) {
     const int r = idx >> 1, half = idx & 1;
@@ -480,7 +455,7 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
     del += __shfl_xor(del, 1, 64);
     if (half == 0) {
       sDel[r] = del;
-      sLse[r] = r < len ? lse[(long)h * T + t0 + r] * LOG2E : 0.f;
+      sLse[r] = r < len ? lse[(long)h * T + t0 + r] * ATT_LOG2E : 0.f;
     }
   }
   if (DROP) {                                        // keep-bits of (query q, keys kt*16 .. +15): wave -> key tile, lane -> query
@@ -498,16 +473,14 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   const uint32_t patch_addr = lds0 + (uint32_t)(PATCH + wave * 2048);
   // lane constants: row-fragment offsets (chunks fg and 4+fg of row fr) and transpose-fragment offsets per 16-column tile
   const int fsw = att_f(fr);
   const uint32_t rf_lo = (uint32_t)(fr * 128 + ((fg ^ fsw) << 4)), rf_hi = (uint32_t)(fr * 128 + (((4 + fg) ^ fsw) << 4));
-  const int rr = 4 * fg + (fr >> 2), tsw = att_f(rr), tx = (fr & 3) >> 1;
   uint32_t tr[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) tr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
+  ATT_VTR(fr, fg, tr);
   const bool full = (len == nkt2 * 16);             // no ragged tail: the copies of the phases without per-element masks
   const int npair = nkt2 >> 1;
   // V row fragments of key pair KP from global memory (VG; rows past the end: copies of the last row)
@@ -528,8 +501,8 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
       bf16x8 qf0, qf1, df0, df1;
       {
         const uint32_t aq = lds0 + (uint32_t)(OFF_Q + qt * 2048);
-        A2_RD128O(qf0, aq + rf_lo, 0); A2_RD128O(qf1, aq + rf_hi, 0);
-        A2_RD128O(df0, aq + rf_lo, OFF_D - OFF_Q); A2_RD128O(df1, aq + rf_hi, OFF_D - OFF_Q);
+        ATT_RD128O(qf0, aq + rf_lo, 0); ATT_RD128O(qf1, aq + rf_hi, 0);
+        ATT_RD128O(df0, aq + rf_lo, OFF_D - OFF_Q); ATT_RD128O(df1, aq + rf_hi, OFF_D - OFF_Q);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qf0), "+v"(qf1), "+v"(df0), "+v"(df1)::"memory");
       }
       const float lq = sLse[q], dq_ = sDel[q];
@@ -545,16 +518,16 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
         const uint32_t a_t0 = lds0 + tr[0] + po, a_t1 = lds0 + tr[1] + po, a_t2 = lds0 + tr[2] + po, a_t3 = lds0 + tr[3] + po;
         bf16x8 k00, k01, k10, k11, v00, v01, v10, v11;
         bf16x4 t0l, t0h, t1l, t1h, t2l, t2h, t3l, t3h;
-        A2_RD128O(k00, a_lo, 0); A2_RD128O(k01, a_hi, 0); A2_RD128O(k10, a_lo, 2048); A2_RD128O(k11, a_hi, 2048);
+        ATT_RD128O(k00, a_lo, 0); ATT_RD128O(k01, a_hi, 0); ATT_RD128O(k10, a_lo, 2048); ATT_RD128O(k11, a_hi, 2048);
         if (VG) {
           v00 = vn00; v01 = vn01; v10 = vn10; v11 = vn11;
           A2_VLOAD(kp + 1 < npair ? kp + 1 : kp, vn00, vn01, vn10, vn11);
         } else {
-          A2_RD128O(v00, a_lo, OFF_V - OFF_K); A2_RD128O(v01, a_hi, OFF_V - OFF_K);
-          A2_RD128O(v10, a_lo, OFF_V - OFF_K + 2048); A2_RD128O(v11, a_hi, OFF_V - OFF_K + 2048);
+          ATT_RD128O(v00, a_lo, OFF_V - OFF_K); ATT_RD128O(v01, a_hi, OFF_V - OFF_K);
+          ATT_RD128O(v10, a_lo, OFF_V - OFF_K + 2048); ATT_RD128O(v11, a_hi, OFF_V - OFF_K + 2048);
         }
-        A2_RDTRO(t0l, a_t0, 0); A2_RDTRO(t0h, a_t0, 2048); A2_RDTRO(t1l, a_t1, 0); A2_RDTRO(t1h, a_t1, 2048);
-        A2_RDTRO(t2l, a_t2, 0); A2_RDTRO(t2h, a_t2, 2048); A2_RDTRO(t3l, a_t3, 0); A2_RDTRO(t3h, a_t3, 2048);
+        ATT_RDTRO(t0l, a_t0, 0); ATT_RDTRO(t0h, a_t0, 2048); ATT_RDTRO(t1l, a_t1, 0); ATT_RDTRO(t1h, a_t1, 2048);
+        ATT_RDTRO(t2l, a_t2, 0); ATT_RDTRO(t2h, a_t2, 2048); ATT_RDTRO(t3l, a_t3, 0); ATT_RDTRO(t3h, a_t3, 2048);
         uint32_t mwa0 = 0xFFFFu, mwa1 = 0xFFFFu;
         if (DROP) {
           const uint32_t ma = lds0 + (uint32_t)(MSK + (kp * 2 * NKT * 16 + q) * 2);
@@ -584,10 +557,10 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
           }
         }
         const bf16x8 dsf = pack8<F>(ds[0], ds[1]);
-        dq[0] = H16<F>::mfma(A2_CAT(t0l, t0h), dsf, dq[0]);
-        dq[1] = H16<F>::mfma(A2_CAT(t1l, t1h), dsf, dq[1]);
-        dq[2] = H16<F>::mfma(A2_CAT(t2l, t2h), dsf, dq[2]);
-        dq[3] = H16<F>::mfma(A2_CAT(t3l, t3h), dsf, dq[3]);
+        dq[0] = H16<F>::mfma(ATT_CAT(t0l, t0h), dsf, dq[0]);
+        dq[1] = H16<F>::mfma(ATT_CAT(t1l, t1h), dsf, dq[1]);
+        dq[2] = H16<F>::mfma(ATT_CAT(t2l, t2h), dsf, dq[2]);
+        dq[3] = H16<F>::mfma(ATT_CAT(t3l, t3h), dsf, dq[3]);
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
@@ -607,13 +580,13 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
       bf16x8 kf0, kf1, vf0, vf1;
       {
         const uint32_t ak = lds0 + (uint32_t)(OFF_K + kt * 2048);
-        A2_RD128O(kf0, ak + rf_lo, 0); A2_RD128O(kf1, ak + rf_hi, 0);
+        ATT_RD128O(kf0, ak + rf_lo, 0); ATT_RD128O(kf1, ak + rf_hi, 0);
         if (VG) {
           const bf16_t* pv = Vg + (long)(key < len ? key : len - 1) * H3 + fg * 8;
           vf0 = *reinterpret_cast<const bf16x8*>(pv); vf1 = *reinterpret_cast<const bf16x8*>(pv + 32);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kf0), "+v"(kf1)::"memory");
         } else {
-          A2_RD128O(vf0, ak + rf_lo, OFF_V - OFF_K); A2_RD128O(vf1, ak + rf_hi, OFF_V - OFF_K);
+          ATT_RD128O(vf0, ak + rf_lo, OFF_V - OFF_K); ATT_RD128O(vf1, ak + rf_hi, OFF_V - OFF_K);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kf0), "+v"(kf1), "+v"(vf0), "+v"(vf1)::"memory");
         }
       }
@@ -630,18 +603,18 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
         bf16x4 e0l, e0h, e1l, e1h, e2l, e2h, e3l, e3h, u0l, u0h, u1l, u1h, u2l, u2h, u3l, u3h;
         f32x4 ls0, ls1, de0, de1;
         uint2 mb[2] = {make_uint2(~0u, ~0u), make_uint2(~0u, ~0u)};          // keep-bits of the lane's four query rows (16 bits each), per tile of the pair
-        A2_RD128O(q00, a_lo, 0); A2_RD128O(q01, a_hi, 0); A2_RD128O(q10, a_lo, 2048); A2_RD128O(q11, a_hi, 2048);
-        A2_RD128O(d00, a_lo, OFF_D - OFF_Q); A2_RD128O(d01, a_hi, OFF_D - OFF_Q);
-        A2_RD128O(d10, a_lo, OFF_D - OFF_Q + 2048); A2_RD128O(d11, a_hi, OFF_D - OFF_Q + 2048);
-        A2_RD128O(ls0, bl, 0); A2_RD128O(ls1, bl, 64); A2_RD128O(de0, bl, NKT * 64); A2_RD128O(de1, bl, NKT * 64 + 64);
+        ATT_RD128O(q00, a_lo, 0); ATT_RD128O(q01, a_hi, 0); ATT_RD128O(q10, a_lo, 2048); ATT_RD128O(q11, a_hi, 2048);
+        ATT_RD128O(d00, a_lo, OFF_D - OFF_Q); ATT_RD128O(d01, a_hi, OFF_D - OFF_Q);
+        ATT_RD128O(d10, a_lo, OFF_D - OFF_Q + 2048); ATT_RD128O(d11, a_hi, OFF_D - OFF_Q + 2048);
+        ATT_RD128O(ls0, bl, 0); ATT_RD128O(ls1, bl, 64); ATT_RD128O(de0, bl, NKT * 64); ATT_RD128O(de1, bl, NKT * 64 + 64);
         if (DROP) {
           const uint32_t ma = lds0 + (uint32_t)(MSK + (kt * NKT * 16 + qp * 32 + 4 * fg) * 2);
           asm volatile("ds_read_b64 %0, %2\n\tds_read_b64 %1, %2 offset:32" : "=&v"(mb[0]), "=&v"(mb[1]) : "v"(ma) : "memory");
         }
-        A2_RDTRO(e0l, a_t0, OFF_D - OFF_Q); A2_RDTRO(e0h, a_t0, OFF_D - OFF_Q + 2048); A2_RDTRO(e1l, a_t1, OFF_D - OFF_Q); A2_RDTRO(e1h, a_t1, OFF_D - OFF_Q + 2048);
-        A2_RDTRO(e2l, a_t2, OFF_D - OFF_Q); A2_RDTRO(e2h, a_t2, OFF_D - OFF_Q + 2048); A2_RDTRO(e3l, a_t3, OFF_D - OFF_Q); A2_RDTRO(e3h, a_t3, OFF_D - OFF_Q + 2048);
-        A2_RDTRO(u0l, a_t0, 0); A2_RDTRO(u0h, a_t0, 2048); A2_RDTRO(u1l, a_t1, 0); A2_RDTRO(u1h, a_t1, 2048);
-        A2_RDTRO(u2l, a_t2, 0); A2_RDTRO(u2h, a_t2, 2048); A2_RDTRO(u3l, a_t3, 0); A2_RDTRO(u3h, a_t3, 2048);
+        ATT_RDTRO(e0l, a_t0, OFF_D - OFF_Q); ATT_RDTRO(e0h, a_t0, OFF_D - OFF_Q + 2048); ATT_RDTRO(e1l, a_t1, OFF_D - OFF_Q); ATT_RDTRO(e1h, a_t1, OFF_D - OFF_Q + 2048);
+        ATT_RDTRO(e2l, a_t2, OFF_D - OFF_Q); ATT_RDTRO(e2h, a_t2, OFF_D - OFF_Q + 2048); ATT_RDTRO(e3l, a_t3, OFF_D - OFF_Q); ATT_RDTRO(e3h, a_t3, OFF_D - OFF_Q + 2048);
+        ATT_RDTRO(u0l, a_t0, 0); ATT_RDTRO(u0h, a_t0, 2048); ATT_RDTRO(u1l, a_t1, 0); ATT_RDTRO(u1h, a_t1, 2048);
+        ATT_RDTRO(u2l, a_t2, 0); ATT_RDTRO(u2h, a_t2, 2048); ATT_RDTRO(u3l, a_t3, 0); ATT_RDTRO(u3h, a_t3, 2048);
         // (ONE wait names all 30 registers in flight -- the operand limit of an asm statement)
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(q00), "+v"(q01), "+v"(q10), "+v"(q11), "+v"(d00), "+v"(d01), "+v"(d10), "+v"(d11),
                      "+v"(ls0), "+v"(ls1), "+v"(de0), "+v"(de1), "+v"(mb[0]), "+v"(mb[1]),
@@ -674,14 +647,14 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
         }
         const bf16x8 pf = pack8<F>(pp[0], pp[1]);
         const bf16x8 dsf = pack8<F>(ds[0], ds[1]);
-        dv[0] = H16<F>::mfma(A2_CAT(e0l, e0h), pf, dv[0]);
-        dk[0] = H16<F>::mfma(A2_CAT(u0l, u0h), dsf, dk[0]);
-        dv[1] = H16<F>::mfma(A2_CAT(e1l, e1h), pf, dv[1]);
-        dk[1] = H16<F>::mfma(A2_CAT(u1l, u1h), dsf, dk[1]);
-        dv[2] = H16<F>::mfma(A2_CAT(e2l, e2h), pf, dv[2]);
-        dk[2] = H16<F>::mfma(A2_CAT(u2l, u2h), dsf, dk[2]);
-        dv[3] = H16<F>::mfma(A2_CAT(e3l, e3h), pf, dv[3]);
-        dk[3] = H16<F>::mfma(A2_CAT(u3l, u3h), dsf, dk[3]);
+        dv[0] = H16<F>::mfma(ATT_CAT(e0l, e0h), pf, dv[0]);
+        dk[0] = H16<F>::mfma(ATT_CAT(u0l, u0h), dsf, dk[0]);
+        dv[1] = H16<F>::mfma(ATT_CAT(e1l, e1h), pf, dv[1]);
+        dk[1] = H16<F>::mfma(ATT_CAT(u1l, u1h), dsf, dk[1]);
+        dv[2] = H16<F>::mfma(ATT_CAT(e2l, e2h), pf, dv[2]);
+        dk[2] = H16<F>::mfma(ATT_CAT(u2l, u2h), dsf, dk[2]);
+        dv[3] = H16<F>::mfma(ATT_CAT(e3l, e3h), pf, dv[3]);
+        dk[3] = H16<F>::mfma(ATT_CAT(u3l, u3h), dsf, dk[3]);
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
@@ -710,6 +683,18 @@ __global__ __launch_bounds__(256) void mha_bwd2_h16_kernel(const bf16_t* __restr
 // iteration is one basic block; dK / dV read the dropout keep-bits of the (key chunk, query chunk) pair from the LDS, hashed once
 // while the query chunk is staged: see mha_bwd2_h16_kernel)
 // CH: tokens per chunk.  256: one workgroup per CU (4 tiles of 32 KB), four tiles per wave; 128: two workgroups per CU, two tiles per wave.
+// LDS: Q | K | V | dO tiles of one chunk, lse[CH], delta[CH] (f32), a 2 KB store patch per wave, and the dropout bits of dK / dV:
+// [key tile of the own chunk][query of the staged chunk]
+template <int CH>
+struct BwdLongLds {
+  static constexpr int TILE = CH * 128;
+  static constexpr int OFF_Q = 0, OFF_K = TILE, OFF_V = 2 * TILE, OFF_D = 3 * TILE;
+  static constexpr int VEC = 4 * TILE;
+  static constexpr int PATCH = VEC + 2 * CH * 4;
+  static constexpr int MSK = PATCH + 4 * 2048;
+  static constexpr int BYTES = MSK + (CH / 16) * CH * 2;
+};
+
 template <typename F, bool DKV, bool DROP, int CH>
 __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ O,
                                                               const float* __restrict__ lse, const bf16_t* __restrict__ dO,
@@ -731,30 +716,29 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
   const bf16_t* Vg = Kg + H;
   const bf16_t* Og = O + (long)t0 * H + h * 64;
   const bf16_t* dOg = dO + (long)t0 * H + h * 64;
-  char* sQ = smem;
-  char* sK = smem + (CH * 128);
-  char* sV = smem + 2 * (CH * 128);
-  char* sD = smem + 3 * (CH * 128);
-  float* sLse = reinterpret_cast<float*>(smem + 4 * (CH * 128));
+  using Lds = BwdLongLds<CH>;
+  constexpr int MSK = Lds::MSK;
+  char* sQ = smem + Lds::OFF_Q;
+  char* sK = smem + Lds::OFF_K;
+  char* sV = smem + Lds::OFF_V;
+  char* sD = smem + Lds::OFF_D;
+  float* sLse = reinterpret_cast<float*>(smem + Lds::VEC);
   float* sDel = sLse + CH;
-  char* patch = smem + 4 * (CH * 128) + 2 * CH * 4 + wave * 2048;
-  constexpr int MSK = 4 * (CH * 128) + 2 * CH * 4 + 4 * 2048;   // dropout bits [key tile of the own chunk][query of the staged chunk]
+  char* patch = smem + Lds::PATCH + wave * 2048;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  const uint32_t patch_addr = lds0 + (uint32_t)(4 * (CH * 128) + 2 * CH * 4 + wave * 2048);
+  const uint32_t patch_addr = lds0 + (uint32_t)(Lds::PATCH + wave * 2048);
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const int fsw = att_f(fr);
   const uint32_t rf_lo = (uint32_t)(fr * 128 + ((fg ^ fsw) << 4)), rf_hi = (uint32_t)(fr * 128 + (((4 + fg) ^ fsw) << 4));
-  const int rr = 4 * fg + (fr >> 2), tsw = att_f(rr), tx = (fr & 3) >> 1;
   uint32_t tr[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) tr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
+  ATT_VTR(fr, fg, tr);
 
   // stage rows [r0, r0+n) of the query side (Q, dO, lse, delta) / key side (K, V); rows padded to a multiple of 32
   auto stage_q = [&](int r0, int n) {
     const int npad = ((n + 31) >> 5) << 5;
-    att_stage(Qg + (long)r0 * H3, H3, n, npad, sQ, wave, lane);
-    att_stage(dOg + (long)r0 * H, H, n, npad, sD, wave, lane);
+    att_stage(Qg + (long)r0 * H3, H3, n, npad, sQ, wave, lane, 4);
+    att_stage(dOg + (long)r0 * H, H, n, npad, sD, wave, lane, 4);
     for (int idx = tid; idx < npad * 2; idx += 256) {
       const int r = idx >> 1, half = idx & 1;
       float del = 0.f;
@@ -773,7 +757,7 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
       del += __shfl_xor(del, 1, 64);
       if (half == 0) {
         sDel[r] = del;
-        sLse[r] = r < n ? lse[(long)h * T + t0 + r0 + r] * LOG2E : 0.f;
+        sLse[r] = r < n ? lse[(long)h * T + t0 + r0 + r] * ATT_LOG2E : 0.f;
       }
     }
     if (DKV && DROP) {                               // keep-bits of (query r0 + q, keys own0 + kt*16 .. +15): wave -> key tile, lane -> query
@@ -791,8 +775,8 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
   };
   auto stage_k = [&](int r0, int n) {
     const int npad = ((n + 31) >> 5) << 5;
-    att_stage(Kg + (long)r0 * H3, H3, n, npad, sK, wave, lane);
-    att_stage(Vg + (long)r0 * H3, H3, n, npad, sV, wave, lane);
+    att_stage(Kg + (long)r0 * H3, H3, n, npad, sK, wave, lane, 4);
+    att_stage(Vg + (long)r0 * H3, H3, n, npad, sV, wave, lane, 4);
   };
 
   if (!DKV) {
@@ -821,21 +805,21 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
         const int q = qt * 16 + fr;
         bf16x8 qf0, qf1, df0, df1;
         {
-          const uint32_t aq = lds0 + (uint32_t)(qt * 2048), ad = aq + 3 * (CH * 128);
-          A2_RD128(qf0, aq + rf_lo, 0); A2_RD128(qf1, aq + rf_hi, 0);
-          A2_RD128(df0, ad + rf_lo, 0); A2_RD128(df1, ad + rf_hi, 0);
+          const uint32_t aq = lds0 + (uint32_t)(Lds::OFF_Q + qt * 2048), ad = aq + (Lds::OFF_D - Lds::OFF_Q);
+          ATT_RD128(qf0, aq + rf_lo, 0); ATT_RD128(qf1, aq + rf_hi, 0);
+          ATT_RD128(df0, ad + rf_lo, 0); ATT_RD128(df1, ad + rf_hi, 0);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qf0), "+v"(qf1), "+v"(df0), "+v"(df1)::"memory");
         }
         const float lq = sLse[q], dq_ = sDel[q];
         const bool qok = q < ownlen;
         for (int kp = 0; kp < nkp; ++kp) {
-          const uint32_t bk = lds0 + (uint32_t)((CH * 128) + kp * 4096), bv = bk + (CH * 128);
+          const uint32_t bk = lds0 + (uint32_t)(Lds::OFF_K + kp * 4096), bv = bk + (Lds::OFF_V - Lds::OFF_K);
           bf16x8 k00, k01, k10, k11, v00, v01, v10, v11;
           bf16x4 t0l, t0h, t1l, t1h, t2l, t2h, t3l, t3h;
-          A2_RD128(k00, bk + rf_lo, 0); A2_RD128(k01, bk + rf_hi, 0); A2_RD128(k10, bk + rf_lo, 2048); A2_RD128(k11, bk + rf_hi, 2048);
-          A2_RD128(v00, bv + rf_lo, 0); A2_RD128(v01, bv + rf_hi, 0); A2_RD128(v10, bv + rf_lo, 2048); A2_RD128(v11, bv + rf_hi, 2048);
-          A2_RDTR(t0l, bk + tr[0], 0); A2_RDTR(t0h, bk + tr[0], 2048); A2_RDTR(t1l, bk + tr[1], 0); A2_RDTR(t1h, bk + tr[1], 2048);
-          A2_RDTR(t2l, bk + tr[2], 0); A2_RDTR(t2h, bk + tr[2], 2048); A2_RDTR(t3l, bk + tr[3], 0); A2_RDTR(t3h, bk + tr[3], 2048);
+          ATT_RD128(k00, bk + rf_lo, 0); ATT_RD128(k01, bk + rf_hi, 0); ATT_RD128(k10, bk + rf_lo, 2048); ATT_RD128(k11, bk + rf_hi, 2048);
+          ATT_RD128(v00, bv + rf_lo, 0); ATT_RD128(v01, bv + rf_hi, 0); ATT_RD128(v10, bv + rf_lo, 2048); ATT_RD128(v11, bv + rf_hi, 2048);
+          ATT_RDTR(t0l, bk + tr[0], 0); ATT_RDTR(t0h, bk + tr[0], 2048); ATT_RDTR(t1l, bk + tr[1], 0); ATT_RDTR(t1h, bk + tr[1], 2048);
+          ATT_RDTR(t2l, bk + tr[2], 0); ATT_RDTR(t2h, bk + tr[2], 2048); ATT_RDTR(t3l, bk + tr[3], 0); ATT_RDTR(t3h, bk + tr[3], 2048);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(k00), "+v"(k01), "+v"(k10), "+v"(k11), "+v"(v00), "+v"(v01), "+v"(v10), "+v"(v11),
                        "+v"(t0l), "+v"(t0h), "+v"(t1l), "+v"(t1h), "+v"(t2l), "+v"(t2h), "+v"(t3l), "+v"(t3h)::"memory");
           f32x4 ds[2];
@@ -857,10 +841,10 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
             }
           }
           const bf16x8 dsf = pack8<F>(ds[0], ds[1]);
-          dq[t][0] = H16<F>::mfma(A2_CAT(t0l, t0h), dsf, dq[t][0]);
-          dq[t][1] = H16<F>::mfma(A2_CAT(t1l, t1h), dsf, dq[t][1]);
-          dq[t][2] = H16<F>::mfma(A2_CAT(t2l, t2h), dsf, dq[t][2]);
-          dq[t][3] = H16<F>::mfma(A2_CAT(t3l, t3h), dsf, dq[t][3]);
+          dq[t][0] = H16<F>::mfma(ATT_CAT(t0l, t0h), dsf, dq[t][0]);
+          dq[t][1] = H16<F>::mfma(ATT_CAT(t1l, t1h), dsf, dq[t][1]);
+          dq[t][2] = H16<F>::mfma(ATT_CAT(t2l, t2h), dsf, dq[t][2]);
+          dq[t][3] = H16<F>::mfma(ATT_CAT(t3l, t3h), dsf, dq[t][3]);
         }
       }
       };
@@ -898,24 +882,24 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
         const int key = kt * 16 + fr;
         bf16x8 kf0, kf1, vf0, vf1;
         {
-          const uint32_t ak = lds0 + (uint32_t)((CH * 128) + kt * 2048), av = ak + (CH * 128);
-          A2_RD128(kf0, ak + rf_lo, 0); A2_RD128(kf1, ak + rf_hi, 0);
-          A2_RD128(vf0, av + rf_lo, 0); A2_RD128(vf1, av + rf_hi, 0);
+          const uint32_t ak = lds0 + (uint32_t)(Lds::OFF_K + kt * 2048), av = ak + (Lds::OFF_V - Lds::OFF_K);
+          ATT_RD128(kf0, ak + rf_lo, 0); ATT_RD128(kf1, ak + rf_hi, 0);
+          ATT_RD128(vf0, av + rf_lo, 0); ATT_RD128(vf1, av + rf_hi, 0);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kf0), "+v"(kf1), "+v"(vf0), "+v"(vf1)::"memory");
         }
         const bool kok = key < ownlen;
         for (int qp = 0; qp < nqp; ++qp) {
-          // (dO tile = Q tile + 3 * CH * 128 bytes: as an instruction offset where it encodes -- 16 bits, the 128-token chunks -- so
+          // (dO tile = Q tile + OFF_D bytes: as an instruction offset where it encodes -- 16 bits, the 128-token chunks -- so
           // that Q and dO requests share their address registers)
-          constexpr int DOFF = CH == 128 ? 3 * (CH * 128) : 0;
-          const uint32_t bq = lds0 + (uint32_t)(qp * 4096), bd = bq + (uint32_t)(3 * (CH * 128) - DOFF);
-          const uint32_t bl = lds0 + (uint32_t)(4 * (CH * 128) + (qp * 32 + 4 * fg) * 4);
+          constexpr int DOFF = CH == 128 ? Lds::OFF_D - Lds::OFF_Q : 0;
+          const uint32_t bq = lds0 + (uint32_t)(Lds::OFF_Q + qp * 4096), bd = bq + (uint32_t)(Lds::OFF_D - Lds::OFF_Q - DOFF);
+          const uint32_t bl = lds0 + (uint32_t)(Lds::VEC + (qp * 32 + 4 * fg) * 4);
           bf16x8 q00, q01, q10, q11, d00, d01, d10, d11;
           bf16x4 e0l, e0h, e1l, e1h, e2l, e2h, e3l, e3h, u0l, u0h, u1l, u1h, u2l, u2h, u3l, u3h;
           f32x4 ls0, ls1, de0, de1;
           uint2 mb[2] = {make_uint2(~0u, ~0u), make_uint2(~0u, ~0u)};          // keep-bits of the lane's four query rows (16 bits each), per tile of the pair
-          A2_RD128(q00, bq + rf_lo, 0); A2_RD128(q01, bq + rf_hi, 0); A2_RD128(q10, bq + rf_lo, 2048); A2_RD128(q11, bq + rf_hi, 2048);
-          A2_RD128O(d00, bd + rf_lo, DOFF); A2_RD128O(d01, bd + rf_hi, DOFF); A2_RD128O(d10, bd + rf_lo, DOFF + 2048); A2_RD128O(d11, bd + rf_hi, DOFF + 2048);
+          ATT_RD128(q00, bq + rf_lo, 0); ATT_RD128(q01, bq + rf_hi, 0); ATT_RD128(q10, bq + rf_lo, 2048); ATT_RD128(q11, bq + rf_hi, 2048);
+          ATT_RD128O(d00, bd + rf_lo, DOFF); ATT_RD128O(d01, bd + rf_hi, DOFF); ATT_RD128O(d10, bd + rf_lo, DOFF + 2048); ATT_RD128O(d11, bd + rf_hi, DOFF + 2048);
           asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %5\n\tds_read_b128 %3, %5 offset:64"
                        : "=&v"(ls0), "=&v"(ls1), "=&v"(de0), "=&v"(de1) : "v"(bl), "v"(bl + (uint32_t)(CH * 4)) : "memory");
           if (DROP) {
@@ -939,10 +923,10 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
           }
           // (the empty asm orders the requests after the MFMA issue: it names the accumulators, it does not read them)
           asm volatile("" : "+v"(sv[0]), "+v"(sv[1]), "+v"(dpv[0]), "+v"(dpv[1]));
-          A2_RDTRO(e0l, bd + tr[0], DOFF); A2_RDTRO(e0h, bd + tr[0], DOFF + 2048); A2_RDTRO(e1l, bd + tr[1], DOFF); A2_RDTRO(e1h, bd + tr[1], DOFF + 2048);
-          A2_RDTRO(e2l, bd + tr[2], DOFF); A2_RDTRO(e2h, bd + tr[2], DOFF + 2048); A2_RDTRO(e3l, bd + tr[3], DOFF); A2_RDTRO(e3h, bd + tr[3], DOFF + 2048);
-          A2_RDTR(u0l, bq + tr[0], 0); A2_RDTR(u0h, bq + tr[0], 2048); A2_RDTR(u1l, bq + tr[1], 0); A2_RDTR(u1h, bq + tr[1], 2048);
-          A2_RDTR(u2l, bq + tr[2], 0); A2_RDTR(u2h, bq + tr[2], 2048); A2_RDTR(u3l, bq + tr[3], 0); A2_RDTR(u3h, bq + tr[3], 2048);
+          ATT_RDTRO(e0l, bd + tr[0], DOFF); ATT_RDTRO(e0h, bd + tr[0], DOFF + 2048); ATT_RDTRO(e1l, bd + tr[1], DOFF); ATT_RDTRO(e1h, bd + tr[1], DOFF + 2048);
+          ATT_RDTRO(e2l, bd + tr[2], DOFF); ATT_RDTRO(e2h, bd + tr[2], DOFF + 2048); ATT_RDTRO(e3l, bd + tr[3], DOFF); ATT_RDTRO(e3h, bd + tr[3], DOFF + 2048);
+          ATT_RDTR(u0l, bq + tr[0], 0); ATT_RDTR(u0h, bq + tr[0], 2048); ATT_RDTR(u1l, bq + tr[1], 0); ATT_RDTR(u1h, bq + tr[1], 2048);
+          ATT_RDTR(u2l, bq + tr[2], 0); ATT_RDTR(u2h, bq + tr[2], 2048); ATT_RDTR(u3l, bq + tr[3], 0); ATT_RDTR(u3h, bq + tr[3], 2048);
           f32x4 pp[2], ds[2];
 #pragma unroll
           for (int hf = 0; hf < 2; ++hf) {
@@ -966,14 +950,14 @@ __global__ __launch_bounds__(256, (CH == 128 ? 2 : 1)) void mha_bwd_long_kernel(
           bf16x8 dsf = pack8<F>(ds[0], ds[1]);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e0l), "+v"(e0h), "+v"(e1l), "+v"(e1h), "+v"(e2l), "+v"(e2h), "+v"(e3l), "+v"(e3h),
                        "+v"(u0l), "+v"(u0h), "+v"(u1l), "+v"(u1h), "+v"(u2l), "+v"(u2h), "+v"(u3l), "+v"(u3h), "+v"(pf), "+v"(dsf)::"memory");
-          dv[t][0] = H16<F>::mfma(A2_CAT(e0l, e0h), pf, dv[t][0]);
-          dk[t][0] = H16<F>::mfma(A2_CAT(u0l, u0h), dsf, dk[t][0]);
-          dv[t][1] = H16<F>::mfma(A2_CAT(e1l, e1h), pf, dv[t][1]);
-          dk[t][1] = H16<F>::mfma(A2_CAT(u1l, u1h), dsf, dk[t][1]);
-          dv[t][2] = H16<F>::mfma(A2_CAT(e2l, e2h), pf, dv[t][2]);
-          dk[t][2] = H16<F>::mfma(A2_CAT(u2l, u2h), dsf, dk[t][2]);
-          dv[t][3] = H16<F>::mfma(A2_CAT(e3l, e3h), pf, dv[t][3]);
-          dk[t][3] = H16<F>::mfma(A2_CAT(u3l, u3h), dsf, dk[t][3]);
+          dv[t][0] = H16<F>::mfma(ATT_CAT(e0l, e0h), pf, dv[t][0]);
+          dk[t][0] = H16<F>::mfma(ATT_CAT(u0l, u0h), dsf, dk[t][0]);
+          dv[t][1] = H16<F>::mfma(ATT_CAT(e1l, e1h), pf, dv[t][1]);
+          dk[t][1] = H16<F>::mfma(ATT_CAT(u1l, u1h), dsf, dk[t][1]);
+          dv[t][2] = H16<F>::mfma(ATT_CAT(e2l, e2h), pf, dv[t][2]);
+          dk[t][2] = H16<F>::mfma(ATT_CAT(u2l, u2h), dsf, dk[t][2]);
+          dv[t][3] = H16<F>::mfma(ATT_CAT(e3l, e3h), pf, dv[t][3]);
+          dk[t][3] = H16<F>::mfma(ATT_CAT(u3l, u3h), dsf, dk[t][3]);
         }
       }
       };
@@ -1130,19 +1114,11 @@ __global__ __launch_bounds__(256) void mha_bwd_simple_kernel(const TT* __restric
 }
 
 // ------------------------------------------------------------------------------------------ host
-template <typename K>
-static int set_lds(K kernel, size_t bytes, const char* name) {
-  if (bytes > 65536) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
-        hipSuccess) {
-      simx_set_error("%s: cannot raise dynamic LDS to %zu", name, bytes);
-      return SIMX_ERR_HIP;
-    }
-  }
-  return SIMX_OK;
-}
-
-static int check_common(int dtype, int nseq, int heads, int d, int max_len, int T, const char* who) {
+// what every entry point of the full attention requires; hm_rows > 0: the head-major qkv layout (the same limit forward and
+// backward: a forward the library accepts must have a backward it accepts)
+static int check_common(int dtype, int nseq, int heads, int d, int max_len, int T, const char* who, int hm_rows = 0) {
+  SIMX_REQUIRE(hm_rows == 0 || (simx_is16(dtype) && d == 64 && max_len <= 256 && hm_rows >= T), SIMX_ERR_UNSUPPORTED,
+               "%s: the head-major qkv layout needs a 16-bit dtype, head size 64, max_len <= 256 and hm_rows >= T", who);
   SIMX_REQUIRE(simx_dtype_ok(dtype), SIMX_ERR_BAD_DTYPE, "%s: dtype %d", who, dtype);
   SIMX_REQUIRE(nseq > 0 && heads > 0 && T > 0 && max_len > 0, SIMX_ERR_BAD_SHAPE, "%s: bad shape", who);
   SIMX_REQUIRE(d > 0 && d <= 128, SIMX_ERR_UNSUPPORTED, "%s: head_dim %d > 128", who, d);
@@ -1150,23 +1126,117 @@ static int check_common(int dtype, int nseq, int heads, int d, int max_len, int 
   return SIMX_OK;
 }
 
-extern "C" int simx_mha_fwd_ex(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, void* ctx, float* lse, const simx_dropout* dropd);
-extern "C" int simx_mha_bwd_ex(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv,
-                               const simx_dropout* dropd);
+// max_len -> the resident kernels' key tiles (of 16 tokens), forward and backward: f(std::integral_constant<int, NKT>{})
+template <typename Fn>
+static int h16_by_tiles(int max_len, Fn&& f) {
+  if (max_len <= 32) return f(std::integral_constant<int, 2>{});
+  if (max_len <= 128) return f(std::integral_constant<int, 8>{});
+  if (max_len <= 160) return f(std::integral_constant<int, 10>{});
+  return f(std::integral_constant<int, 16>{});
+}
+
+// LDS of the one-wave-per-row kernels: per wave `rows` rows of 128 floats (q; q or k, dO or v) and `rows` of max_len (scores; ds, p)
+static constexpr int simple_lds(int rows, int max_len) { return rows * 4 * (128 + max_len) * (int)sizeof(float); }
+
 extern "C" int simx_mha_fwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, void* ctx, float* lse, const simx_dropout* dropd, int hm_rows);
-extern "C" int simx_mha_bwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv,
-                               const simx_dropout* dropd, int hm_rows);
+                               int T, const void* qkv, void* ctx, float* lse, const simx_dropout* dropd, int hm_rows) {
+  hipStream_t s = (hipStream_t)stream;
+  const DropCtx drop = make_drop(dropd);
+  SIMX_PROF(SIMX_K_MHA_FWD, s, 4.0 * T * max_len * heads * d);
+  int rc = check_common(dtype, nseq, heads, d, max_len, T, "mha_fwd", hm_rows);
+  if (rc) return rc;
+  const float scale = 1.0f / sqrtf((float)d);
+  if (simx_is16(dtype) && d == 64 && max_len <= 256) {
+    SIMX_DISPATCH16(dtype, FF, return h16_by_tiles(max_len, [&](auto nkt) {
+      return by_flag(drop.thr != 0, [&](auto dr) {
+        constexpr int NKT = decltype(nkt)::value;
+        return att_launch<mha_fwd_h16_kernel<FF, NKT, decltype(dr)::value>, FwdLds<NKT>::BYTES>(
+            "mha_fwd_h16", s, dim3(nseq * heads), (const bf16_t*)qkv, (bf16_t*)ctx, lse, cu, heads, T, scale, drop, hm_rows);
+      });
+    }));
+  }
+  if (simx_is16(dtype) && d == 64 && max_len <= 4096) {            // 256 < max_len: chunked (768 x 16 blocks of 512 tokens: 2.33 ms against 2.41
+                                                                    // with K / V resident in 128 KB of LDS; 300 tokens: 1.12 against 1.91)
+    const int nchunk = cdiv(max_len, 128);
+    SIMX_DISPATCH16(dtype, FF, return by_flag(drop.thr != 0, [&](auto dr) {
+      return att_launch<mha_fwd_long_h16_kernel<FF, decltype(dr)::value>, FwdLds<8>::BYTES>(
+          "mha_fwd_long_h16", s, dim3(nseq * heads * nchunk), (const bf16_t*)qkv, (bf16_t*)ctx, lse, cu, heads, T, nchunk, scale, drop, hm_rows);
+    }));
+  }
+  if (dtype == SIMX_F32 && simx_mha_f32_ok(d, max_len))
+    return simx_mha_fwd_f32(s, nseq, heads, cu, max_len, T, (const float*)qkv, (float*)ctx, lse, scale, drop);
+  const dim3 grid(nseq * heads, cdiv(max_len, 4));
+  SIMX_DISPATCH3(dtype, TT, return (att_launch_upto<mha_fwd_simple_kernel<TT>, simple_lds(1, 4096)>(
+                                "mha_fwd_simple", s, grid, simple_lds(1, max_len), (const TT*)qkv, (TT*)ctx, lse, cu, heads, d, T, scale, max_len, drop)));
+}
+extern "C" int simx_mha_fwd_ex(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
+                               int T, const void* qkv, void* ctx, float* lse, const simx_dropout* dropd) {
+  return simx_mha_fwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, dropd, 0);
+}
 extern "C" int simx_mha_fwd(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
                             int T, const void* qkv, void* ctx, float* lse) {
-  return simx_mha_fwd_ex(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, nullptr);
+  return simx_mha_fwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, nullptr, 0);
+}
+
+extern "C" int simx_mha_bwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
+                               int T, const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv,
+                               const simx_dropout* dropd, int hm_rows) {
+  hipStream_t s = (hipStream_t)stream;
+  const DropCtx drop = make_drop(dropd);
+  SIMX_PROF(SIMX_K_MHA_BWD, s, 8.0 * T * max_len * heads * d);
+  int rc = check_common(dtype, nseq, heads, d, max_len, T, "mha_bwd", hm_rows);
+  if (rc) return rc;
+  const float scale = 1.0f / sqrtf((float)d);
+  if (simx_is16(dtype) && d == 64 && max_len <= 256) {               // (161-256 tokens on the chunked kernels instead: 4.20 vs 4.02 ms at 256, 3.60 vs 3.78 at 200 -- not taken)
+    SIMX_DISPATCH16(dtype, FF, return h16_by_tiles(max_len, [&](auto nkt) {
+      return by_flag(drop.thr != 0, [&](auto dr) {
+        constexpr int NKT = decltype(nkt)::value;
+        constexpr bool VG = NKT == 10;             // 74 KB: two workgroups per CU (93 KB with the V tile: one)
+        return att_launch<mha_bwd2_h16_kernel<FF, NKT, VG, decltype(dr)::value>, Bwd2Lds<NKT, VG>::BYTES>(
+            "mha_bwd_h16", s, dim3(nseq * heads), (const bf16_t*)qkv, (const bf16_t*)ctx, lse, (const bf16_t*)dctx, (bf16_t*)dqkv, cu, heads, T,
+            scale, drop, hm_rows);
+      });
+    }));
+  }
+  if (simx_is16(dtype) && d == 64) {                            // 256 < max_len <= 4096: chunked MFMA kernels
+    // 128-token chunks: two workgroups per CU, two tiles per wave (256-token chunks -- one workgroup per CU, four tiles per wave -- measured
+    // on the MS-Doc step, one box: attention backward 37.8 ms per step, 128-token chunks 30.5)
+    constexpr int ch = 128;
+    const int nchunk = cdiv(max_len, ch);
+    SIMX_DISPATCH16(dtype, FF, {
+      auto run = [&](auto dkv) {
+        return by_flag(drop.thr != 0, [&](auto dr) {
+          return att_launch<mha_bwd_long_kernel<FF, decltype(dkv)::value, decltype(dr)::value, ch>, BwdLongLds<ch>::BYTES>(
+              "mha_bwd_long", s, dim3(nseq * heads * nchunk), (const bf16_t*)qkv, (const bf16_t*)ctx, lse, (const bf16_t*)dctx, (bf16_t*)dqkv,
+              cu, heads, T, nchunk, scale, drop);
+        });
+      };
+      rc = run(std::false_type{});                             // dQ
+      return rc ? rc : run(std::true_type{});                  // dK, dV
+    });
+  }
+  if (dtype == SIMX_F32 && simx_mha_f32_ok(d, max_len))
+    return simx_mha_bwd_f32(s, nseq, heads, cu, max_len, T, (const float*)qkv, (const float*)ctx, lse, (const float*)dctx, (float*)dqkv, scale,
+                            drop);
+  const dim3 grid(nseq * heads, cdiv(max_len, 4));
+  SIMX_DISPATCH3(dtype, TT, {
+    auto run = [&](auto mode) {
+      return att_launch_upto<mha_bwd_simple_kernel<TT, decltype(mode)::value>, simple_lds(2, 4096)>(
+          "mha_bwd_simple", s, grid, simple_lds(2, max_len), (const TT*)qkv, (const TT*)ctx, lse, (const TT*)dctx, (TT*)dqkv, cu, heads, d, T, scale,
+          max_len, drop);
+    };
+    rc = run(std::integral_constant<int, 0>{});                // dQ
+    return rc ? rc : run(std::integral_constant<int, 1>{});    // dK, dV
+  });
+}
+extern "C" int simx_mha_bwd_ex(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
+                               int T, const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv,
+                               const simx_dropout* dropd) {
+  return simx_mha_bwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, dctx, dqkv, dropd, 0);
 }
 extern "C" int simx_mha_bwd(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
                             int T, const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv) {
-  return simx_mha_bwd_ex(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, dctx, dqkv, nullptr);
+  return simx_mha_bwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, dctx, dqkv, nullptr, 0);
 }
 
 // fp32 engine with operand planes (csrc/gemm_xp.hip): f32 q/k/v in; the context leaves as the fp16 plane pair the
@@ -1194,160 +1264,6 @@ extern "C" int simx_mha_bwd_planes(simx_stream_t stream, int nseq, int heads, in
                SIMX_ERR_UNSUPPORTED, "mha_bwd_planes: needs head size 64, max_len <= 4096 and plane strides %% 4 == 0");
   return simx_mha_bwd_f32(s, nseq, heads, cu, max_len, T, qkv, (const float*)ctx_planes, lse, dctx, (float*)dqkv_planes, 1.0f / sqrtf((float)d),
                           make_drop(dropd), ctx_plane_stride, dqkv_plane_stride);
-}
-
-extern "C" int simx_mha_fwd_ex(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, void* ctx, float* lse, const simx_dropout* dropd) {
-  return simx_mha_fwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, dropd, 0);
-}
-extern "C" int simx_mha_fwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, void* ctx, float* lse, const simx_dropout* dropd, int hm_rows) {
-  hipStream_t s = (hipStream_t)stream;
-  // (the same limit as simx_mha_bwd_hm: a forward the library accepts must have a backward it accepts)
-  SIMX_REQUIRE(hm_rows == 0 || (simx_is16(dtype) && d == 64 && max_len <= 256 && hm_rows >= T), SIMX_ERR_UNSUPPORTED,
-               "mha_fwd: the head-major qkv layout needs a 16-bit dtype, head size 64, max_len <= 256 and hm_rows >= T");
-  const DropCtx drop = make_drop(dropd);
-  SIMX_PROF(SIMX_K_MHA_FWD, s, 4.0 * T * max_len * heads * d);
-  int rc = check_common(dtype, nseq, heads, d, max_len, T, "mha_fwd");
-  if (rc) return rc;
-  const float scale = 1.0f / sqrtf((float)d);
-  if (simx_is16(dtype) && d == 64 && max_len <= 256) {
-#define LF(NKT)                                                                                                      \
-  do {                                                                                                               \
-    const size_t lds = (size_t)2 * NKT * 16 * 128;                                                                   \
-    if (drop.thr) {                                                                                                  \
-      rc = set_lds(mha_fwd_h16_kernel<FF, NKT, true>, lds, "mha_fwd");                                               \
-      if (rc) return rc;                                                                                             \
-      hipLaunchKernelGGL((mha_fwd_h16_kernel<FF, NKT, true>), dim3(nseq * heads), dim3(256), lds, s, (const bf16_t*)qkv, \
-                         (bf16_t*)ctx, lse, cu, heads, T, scale, drop, hm_rows);                                     \
-    } else {                                                                                                         \
-      rc = set_lds(mha_fwd_h16_kernel<FF, NKT, false>, lds, "mha_fwd");                                              \
-      if (rc) return rc;                                                                                             \
-      hipLaunchKernelGGL((mha_fwd_h16_kernel<FF, NKT, false>), dim3(nseq * heads), dim3(256), lds, s, (const bf16_t*)qkv, \
-                         (bf16_t*)ctx, lse, cu, heads, T, scale, drop, hm_rows);                                     \
-    }                                                                                                                \
-  } while (0)
-#define LF_ALL()                                                                                                     \
-  do {                                                                                                               \
-    if (max_len <= 32) LF(2);                                                                                        \
-    else if (max_len <= 128) LF(8);                                                                                  \
-    else if (max_len <= 160) LF(10);                                                                                 \
-    else LF(16);                                                                                                     \
-  } while (0)
-    SIMX_DISPATCH16(dtype, FF, LF_ALL());
-#undef LF_ALL
-#undef LF
-    SIMX_CHECK_LAUNCH("mha_fwd_h16");
-    return SIMX_OK;
-  }
-  if (simx_is16(dtype) && d == 64 && max_len <= 4096) {            // 256 < max_len: chunked (768 x 16 blocks of 512 tokens: 2.33 ms against 2.41
-                                                                    // with K / V resident in 128 KB of LDS; 300 tokens: 1.12 against 1.91)
-    const int nchunk = cdiv(max_len, 128);
-#define LFL(DR) hipLaunchKernelGGL((mha_fwd_long_h16_kernel<FF, DR>), dim3(nseq * heads * nchunk), dim3(256), 32768, s, (const bf16_t*)qkv, \
-                                   (bf16_t*)ctx, lse, cu, heads, T, nchunk, scale, drop, hm_rows)
-    SIMX_DISPATCH16(dtype, FF, if (drop.thr) LFL(true); else LFL(false));
-#undef LFL
-    SIMX_CHECK_LAUNCH("mha_fwd_long_h16");
-    return SIMX_OK;
-  }
-  if (dtype == SIMX_F32 && simx_mha_f32_ok(d, max_len))
-    return simx_mha_fwd_f32(s, nseq, heads, cu, max_len, T, (const float*)qkv, (float*)ctx, lse, scale, drop);
-  const size_t lds = (size_t)(4 * 128 + 4 * max_len) * sizeof(float);
-  dim3 grid(nseq * heads, cdiv(max_len, 4));
-#define LS(TT)                                                                                                       \
-  do {                                                                                                               \
-    rc = set_lds(mha_fwd_simple_kernel<TT>, lds, "mha_fwd");                                                         \
-    if (rc) return rc;                                                                                               \
-    hipLaunchKernelGGL((mha_fwd_simple_kernel<TT>), grid, dim3(256), lds, s, (const TT*)qkv, (TT*)ctx, lse, cu, heads, d, T, scale, \
-                       max_len, drop);                                                                               \
-  } while (0)
-  SIMX_DISPATCH3(dtype, TT, LS(TT));
-#undef LS
-  SIMX_CHECK_LAUNCH("mha_fwd_simple");
-  return SIMX_OK;
-}
-
-extern "C" int simx_mha_bwd_ex(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv,
-                               const simx_dropout* dropd) {
-  return simx_mha_bwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, qkv, ctx, lse, dctx, dqkv, dropd, 0);
-}
-extern "C" int simx_mha_bwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                               int T, const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv,
-                               const simx_dropout* dropd, int hm_rows) {
-  hipStream_t s = (hipStream_t)stream;
-  SIMX_REQUIRE(hm_rows == 0 || (simx_is16(dtype) && d == 64 && max_len <= 256 && hm_rows >= T), SIMX_ERR_UNSUPPORTED,
-               "mha_bwd: the head-major qkv layout needs a 16-bit dtype, head size 64, max_len <= 256 and hm_rows >= T");
-  const DropCtx drop = make_drop(dropd);
-  SIMX_PROF(SIMX_K_MHA_BWD, s, 8.0 * T * max_len * heads * d);
-  int rc = check_common(dtype, nseq, heads, d, max_len, T, "mha_bwd");
-  if (rc) return rc;
-  const float scale = 1.0f / sqrtf((float)d);
-  if (simx_is16(dtype) && d == 64 && max_len <= 256) {               // (161-256 tokens on the chunked kernels instead: 4.20 vs 4.02 ms at 256, 3.60 vs 3.78 at 200 -- not taken)
-#define LB(NKT, VG)                                                                                                  \
-  do {                                                                                                               \
-    const size_t lds = (size_t)((VG) ? 3 : 4) * NKT * 16 * 128 + 2 * NKT * 16 * sizeof(float) + (size_t)NKT * 16 * NKT * 2 + 4 * 2048; \
-    if (drop.thr) {                                                                                                  \
-      rc = set_lds(mha_bwd2_h16_kernel<FF, NKT, VG, true>, lds, "mha_bwd");                                          \
-      if (rc) return rc;                                                                                             \
-      hipLaunchKernelGGL((mha_bwd2_h16_kernel<FF, NKT, VG, true>), dim3(nseq * heads), dim3(256), lds, s, (const bf16_t*)qkv, \
-                         (const bf16_t*)ctx, lse, (const bf16_t*)dctx, (bf16_t*)dqkv, cu, heads, T, scale, drop, hm_rows); \
-    } else {                                                                                                         \
-      rc = set_lds(mha_bwd2_h16_kernel<FF, NKT, VG, false>, lds, "mha_bwd");                                         \
-      if (rc) return rc;                                                                                             \
-      hipLaunchKernelGGL((mha_bwd2_h16_kernel<FF, NKT, VG, false>), dim3(nseq * heads), dim3(256), lds, s, (const bf16_t*)qkv, \
-                         (const bf16_t*)ctx, lse, (const bf16_t*)dctx, (bf16_t*)dqkv, cu, heads, T, scale, drop, hm_rows); \
-    }                                                                                                                \
-  } while (0)
-#define LB_ALL()                                                                                                     \
-  do {                                                                                                               \
-    if (max_len <= 32) LB(2, false);                                                                                 \
-    else if (max_len <= 128) LB(8, false);                                                                           \
-    else if (max_len <= 160) LB(10, true);         /* 74 KB: two workgroups per CU (93 KB with the V tile: one) */   \
-    else LB(16, false);                                                                                              \
-  } while (0)
-    SIMX_DISPATCH16(dtype, FF, LB_ALL());
-#undef LB_ALL
-#undef LB
-    SIMX_CHECK_LAUNCH("mha_bwd_h16");
-    return SIMX_OK;
-  }
-  if (simx_is16(dtype) && d == 64) {                            // 256 < max_len <= 4096: chunked MFMA kernels
-    // 128-token chunks: two workgroups per CU, two tiles per wave (256-token chunks -- one workgroup per CU, four tiles per wave -- measured
-    // on the MS-Doc step, one box: attention backward 37.8 ms per step, 128-token chunks 30.5)
-    constexpr int ch = 128;
-    const int nchunk = cdiv(max_len, ch);
-    const size_t ldsl = (size_t)4 * ch * 128 + 2 * ch * sizeof(float) + 4 * 2048 + (size_t)(ch / 16) * ch * 2;   // (+ the dropout bits of dK / dV)
-#define LLD(DKV, DROP)                                                                                               \
-  do {                                                                                                               \
-    rc = set_lds(mha_bwd_long_kernel<FF, DKV, DROP, ch>, ldsl, "mha_bwd");                                           \
-    if (rc) return rc;                                                                                               \
-    hipLaunchKernelGGL((mha_bwd_long_kernel<FF, DKV, DROP, ch>), dim3(nseq * heads * nchunk), dim3(256), ldsl, s, (const bf16_t*)qkv, \
-                       (const bf16_t*)ctx, lse, (const bf16_t*)dctx, (bf16_t*)dqkv, cu, heads, T, nchunk, scale, drop); \
-  } while (0)
-#define LL(DKV) do { if (drop.thr) LLD(DKV, true); else LLD(DKV, false); } while (0)
-    SIMX_DISPATCH16(dtype, FF, LL(false); LL(true));
-#undef LL
-#undef LLD
-    SIMX_CHECK_LAUNCH("mha_bwd_long");
-    return SIMX_OK;
-  }
-  if (dtype == SIMX_F32 && simx_mha_f32_ok(d, max_len))
-    return simx_mha_bwd_f32(s, nseq, heads, cu, max_len, T, (const float*)qkv, (const float*)ctx, lse, (const float*)dctx, (float*)dqkv, scale,
-                            drop);
-  const size_t lds = (size_t)(8 * 128 + 8 * max_len) * sizeof(float);
-  dim3 grid(nseq * heads, cdiv(max_len, 4));
-#define LS(TT, MODE)                                                                                                 \
-  do {                                                                                                               \
-    rc = set_lds(mha_bwd_simple_kernel<TT, MODE>, lds, "mha_bwd");                                                   \
-    if (rc) return rc;                                                                                               \
-    hipLaunchKernelGGL((mha_bwd_simple_kernel<TT, MODE>), grid, dim3(256), lds, s, (const TT*)qkv, (const TT*)ctx, lse, \
-                       (const TT*)dctx, (TT*)dqkv, cu, heads, d, T, scale, max_len, drop);                           \
-  } while (0)
-  SIMX_DISPATCH3(dtype, TT, LS(TT, 0); LS(TT, 1));
-#undef LS
-  SIMX_CHECK_LAUNCH("mha_bwd_simple");
-  return SIMX_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1481,67 +1397,51 @@ __global__ __launch_bounds__(256) void mha_cls_bwd_kernel(int nitems, int heads,
   }
 }
 
-extern "C" int simx_mha_cls_fwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                                   int T, const void* q_cls, const void* qkv, void* ctx_cls, const simx_dropout* dropd, int hm_rows);
-extern "C" int simx_mha_cls_fwd(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                                int T, const void* q_cls, const void* qkv, void* ctx_cls, const simx_dropout* dropd) {
-  return simx_mha_cls_fwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, q_cls, qkv, ctx_cls, dropd, 0);
+// what both [CLS]-row entry points require
+static int check_cls(int dtype, int nseq, int heads, int d, int max_len, int T, int hm_rows, const char* who) {
+  SIMX_REQUIRE(hm_rows == 0 || (d == 64 && hm_rows >= T), SIMX_ERR_UNSUPPORTED, "%s: head-major layout needs head size 64, hm_rows >= T", who);
+  SIMX_REQUIRE(nseq > 0 && heads > 0 && d > 0 && d % 4 == 0 && max_len > 0 && T >= nseq, SIMX_ERR_BAD_SHAPE, "%s: bad shape", who);
+  SIMX_REQUIRE(simx_dtype_ok(dtype), SIMX_ERR_BAD_DTYPE, "%s: dtype %d", who, dtype);
+  return SIMX_OK;
 }
+// LDS of the [CLS]-row kernels: per wave `drows` rows of d floats (q; q, dO) and `lrows` of max_len (p; p, P~, ds).  max_len is not
+// bounded by the entry points: the kernels' limit is the LDS of a CU, a request above it is refused.
+static size_t cls_lds(int drows, int lrows, int d, int max_len) { return (size_t)4 * ((size_t)drows * d + (size_t)lrows * max_len) * sizeof(float); }
+
 extern "C" int simx_mha_cls_fwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
                                    int T, const void* q_cls, const void* qkv, void* ctx_cls, const simx_dropout* dropd, int hm_rows) {
-  SIMX_REQUIRE(hm_rows == 0 || (d == 64 && hm_rows >= T), SIMX_ERR_UNSUPPORTED, "mha_cls_fwd: head-major layout needs head size 64, hm_rows >= T");
-  SIMX_REQUIRE(nseq > 0 && heads > 0 && d > 0 && d % 4 == 0 && max_len > 0 && T >= nseq, SIMX_ERR_BAD_SHAPE, "mha_cls_fwd: bad shape");
-  SIMX_REQUIRE(simx_dtype_ok(dtype), SIMX_ERR_BAD_DTYPE, "mha_cls_fwd: dtype %d", dtype);
+  int rc = check_cls(dtype, nseq, heads, d, max_len, T, hm_rows, "mha_cls_fwd");
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   SIMX_PROF(SIMX_K_MHA_FWD, s, 4.0 * nseq * heads * max_len * d);
   const DropCtx drop = make_drop(dropd);
   const float scale = 1.0f / sqrtf((float)d);
   const int nitems = nseq * heads, H = heads * d;
-  const size_t lds = (size_t)4 * (d + max_len) * sizeof(float);
-  int rc;
-#define LC(TT)                                                                                                       \
-  do {                                                                                                               \
-    rc = set_lds(mha_cls_fwd_kernel<TT>, lds, "mha_cls_fwd");                                                        \
-    if (rc) return rc;                                                                                               \
-    hipLaunchKernelGGL((mha_cls_fwd_kernel<TT>), dim3(cdiv(nitems, 4)), dim3(256), lds, s, nitems, heads, d, H, T, max_len, scale, cu, \
-                       (const TT*)q_cls, (const TT*)qkv, (TT*)ctx_cls, drop, hm_rows);                               \
-  } while (0)
-  SIMX_DISPATCH3(dtype, TT, LC(TT));
-#undef LC
-  SIMX_CHECK_LAUNCH("mha_cls_fwd");
-  return SIMX_OK;
+  SIMX_DISPATCH3(dtype, TT, return (att_launch_upto<mha_cls_fwd_kernel<TT>, ATT_CU_LDS>(
+                                "mha_cls_fwd", s, dim3(cdiv(nitems, 4)), cls_lds(1, 1, d, max_len), nitems, heads, d, H, T, max_len, scale, cu,
+                                (const TT*)q_cls, (const TT*)qkv, (TT*)ctx_cls, drop, hm_rows)));
+}
+extern "C" int simx_mha_cls_fwd(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
+                                int T, const void* q_cls, const void* qkv, void* ctx_cls, const simx_dropout* dropd) {
+  return simx_mha_cls_fwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, q_cls, qkv, ctx_cls, dropd, 0);
 }
 
 extern "C" int simx_mha_cls_bwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
                                    int T, const void* q_cls, const void* qkv, const void* dctx_cls, void* dq_cls, void* dqkv,
-                                   const simx_dropout* dropd, int hm_rows);
-extern "C" int simx_mha_cls_bwd(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                                int T, const void* q_cls, const void* qkv, const void* dctx_cls, void* dq_cls, void* dqkv,
-                                const simx_dropout* dropd) {
-  return simx_mha_cls_bwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, q_cls, qkv, dctx_cls, dq_cls, dqkv, dropd, 0);
-}
-extern "C" int simx_mha_cls_bwd_hm(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
-                                   int T, const void* q_cls, const void* qkv, const void* dctx_cls, void* dq_cls, void* dqkv,
                                    const simx_dropout* dropd, int hm_rows) {
-  SIMX_REQUIRE(hm_rows == 0 || (d == 64 && hm_rows >= T), SIMX_ERR_UNSUPPORTED, "mha_cls_bwd: head-major layout needs head size 64, hm_rows >= T");
-  SIMX_REQUIRE(nseq > 0 && heads > 0 && d > 0 && d % 4 == 0 && max_len > 0 && T >= nseq, SIMX_ERR_BAD_SHAPE, "mha_cls_bwd: bad shape");
-  SIMX_REQUIRE(simx_dtype_ok(dtype), SIMX_ERR_BAD_DTYPE, "mha_cls_bwd: dtype %d", dtype);
+  int rc = check_cls(dtype, nseq, heads, d, max_len, T, hm_rows, "mha_cls_bwd");
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   SIMX_PROF(SIMX_K_MHA_BWD, s, 8.0 * nseq * heads * max_len * d);
   const DropCtx drop = make_drop(dropd);
   const float scale = 1.0f / sqrtf((float)d);
   const int nitems = nseq * heads, H = heads * d;
-  const size_t lds = (size_t)4 * (2 * d + 3 * max_len) * sizeof(float);
-  int rc;
-#define LC(TT)                                                                                                       \
-  do {                                                                                                               \
-    rc = set_lds(mha_cls_bwd_kernel<TT>, lds, "mha_cls_bwd");                                                        \
-    if (rc) return rc;                                                                                               \
-    hipLaunchKernelGGL((mha_cls_bwd_kernel<TT>), dim3(cdiv(nitems, 4)), dim3(256), lds, s, nitems, heads, d, H, T, max_len, scale, cu, \
-                       (const TT*)q_cls, (const TT*)qkv, (const TT*)dctx_cls, (TT*)dq_cls, (TT*)dqkv, drop, hm_rows); \
-  } while (0)
-  SIMX_DISPATCH3(dtype, TT, LC(TT));
-#undef LC
-  SIMX_CHECK_LAUNCH("mha_cls_bwd");
-  return SIMX_OK;
+  SIMX_DISPATCH3(dtype, TT, return (att_launch_upto<mha_cls_bwd_kernel<TT>, ATT_CU_LDS>(
+                                "mha_cls_bwd", s, dim3(cdiv(nitems, 4)), cls_lds(2, 3, d, max_len), nitems, heads, d, H, T, max_len, scale, cu,
+                                (const TT*)q_cls, (const TT*)qkv, (const TT*)dctx_cls, (TT*)dq_cls, (TT*)dqkv, drop, hm_rows)));
+}
+extern "C" int simx_mha_cls_bwd(simx_stream_t stream, int dtype, int nseq, int heads, int d, const int32_t* cu, int max_len,
+                                int T, const void* q_cls, const void* qkv, const void* dctx_cls, void* dq_cls, void* dqkv,
+                                const simx_dropout* dropd) {
+  return simx_mha_cls_bwd_hm(stream, dtype, nseq, heads, d, cu, max_len, T, q_cls, qkv, dctx_cls, dq_cls, dqkv, dropd, 0);
 }

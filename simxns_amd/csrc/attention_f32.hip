@@ -16,11 +16,19 @@
 //     k-step that pairs row(e, 0) with row(e, 1), so P / dS feed the second product straight from the accumulators.
 // Keys are restricted to the sequence's own tokens (== the reference's additive finfo.min mask); dropout masks are the
 // stateless hash of common.h, keyed as in attention.hip (row = head*T + query token, column = key index in the sequence).
-#include "common.h"
+#include "att.h"
 #include "prof.h"
 
 #define AF_PITCH 65
-#define AF_LOG2E 1.4426950408889634f
+
+// LDS (floats): two operand tiles of NKT * 32 rows at pitch PITCH -- K | V (forward, dQ) or Q | dO (dK / dV) -- and, for dK / dV,
+// lse[NKT*32], delta[NKT*32].  The chunked kernels use it with NKT = AFL_NKT.
+template <int NKT, int PITCH = AF_PITCH>
+struct AfLds {
+  static constexpr int TILE = NKT * 32 * PITCH;
+  static constexpr int OFF_B = TILE, OFF_LSE = 2 * TILE, OFF_DEL = OFF_LSE + NKT * 32;
+  static constexpr int BYTES = OFF_LSE * (int)sizeof(float), DKV_BYTES = (OFF_DEL + NKT * 32) * (int)sizeof(float);
+};
 
 __device__ __forceinline__ int af_row(int e, int half) { return 8 * (e >> 2) + 4 * half + (e & 3); }
 
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(256, DENSE ? 2 : 1) void mha_fwd_f32_kernel(const f
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int PITCH = DENSE ? 64 : AF_PITCH;
   float* sK = reinterpret_cast<float*>(smem);
-  float* sV = sK + NKT * 32 * PITCH;
+  float* sV = sK + AfLds<NKT, PITCH>::OFF_B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int seq = blockIdx.x / heads, h = blockIdx.x % heads;
@@ -103,7 +111,7 @@ __global__ __launch_bounds__(256, DENSE ? 2 : 1) void mha_fwd_f32_kernel(const f
   }
   __syncthreads();
   const int col = lane & 31, half = lane >> 5;
-  const float c2 = scale * AF_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   for (int qt = wave; qt < nkt; qt += 4) {
     const int q = qt * 32 + col;
     const int qc = q < len ? q : len - 1;
@@ -181,7 +189,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dq_f32_kernel(const float* __rest
                                                              float scale, DropCtx drop, long ops, long dps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sK = reinterpret_cast<float*>(smem);
-  float* sV = sK + NKT * 32 * AF_PITCH;
+  float* sV = sK + AfLds<NKT>::OFF_B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int seq = blockIdx.x / heads, h = blockIdx.x % heads;
@@ -198,7 +206,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dq_f32_kernel(const float* __rest
   af_stage(Qg + 2 * H, H3, len, nkt * 32, sV, tid);
   __syncthreads();
   const int col = lane & 31, half = lane >> 5;
-  const float c2 = scale * AF_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   for (int qt = wave; qt < nkt; qt += 4) {
     const int q = qt * 32 + col;
     const int qc = q < len ? q : len - 1;
@@ -215,7 +223,7 @@ __global__ __launch_bounds__(256) void mha_bwd_dq_f32_kernel(const float* __rest
       }
     }
     delta += __shfl_xor(delta, 32, 64);
-    const float lq = lse[(long)h * T + t0 + qc] * AF_LOG2E;
+    const float lq = lse[(long)h * T + t0 + qc] * ATT_LOG2E;
     const bool qok = q < len;
     f32x16 dq[2];
 #pragma unroll
@@ -262,9 +270,9 @@ __global__ __launch_bounds__(256) void mha_bwd_dkv_f32_kernel(const float* __res
                                                               float scale, DropCtx drop, long ops, long dps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sQ = reinterpret_cast<float*>(smem);
-  float* sD = sQ + NKT * 32 * AF_PITCH;
-  float* sLse = sD + NKT * 32 * AF_PITCH;
-  float* sDel = sLse + NKT * 32;
+  float* sD = sQ + AfLds<NKT>::OFF_B;
+  float* sLse = sQ + AfLds<NKT>::OFF_LSE;
+  float* sDel = sQ + AfLds<NKT>::OFF_DEL;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int seq = blockIdx.x / heads, h = blockIdx.x % heads;
@@ -289,14 +297,14 @@ __global__ __launch_bounds__(256) void mha_bwd_dkv_f32_kernel(const float* __res
         const float4 a = PL ? plane_ld4<f16_t>(Opl + (long)r * H + 4 * i, ops) : po[i], b = pd[i];
         del += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
       }
-      l = lse[(long)h * T + t0 + r] * AF_LOG2E;
+      l = lse[(long)h * T + t0 + r] * ATT_LOG2E;
     }
     sDel[r] = del;
     sLse[r] = l;
   }
   __syncthreads();
   const int col = lane & 31, half = lane >> 5;
-  const float c2 = scale * AF_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   for (int kt = wave; kt < nkt; kt += 4) {
     const int key = kt * 32 + col;
     const int kc = key < len ? key : len - 1;
@@ -370,7 +378,7 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_f32_long_kernel(const float* _
                                                                   DropCtx drop, long cps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sK = reinterpret_cast<float*>(smem);
-  float* sV = sK + AFL_NKT * 32 * AF_PITCH;
+  float* sV = sK + AfLds<AFL_NKT>::OFF_B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qc = blockIdx.x % nchunk, sh = blockIdx.x / nchunk;
@@ -381,7 +389,7 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_f32_long_kernel(const float* _
   const long H3 = 3L * H;
   const float* Qg = qkv + (long)t0 * H3 + h * 64;
   const int col = lane & 31, half = lane >> 5;
-  const float c2 = scale * AF_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const int q = qc * 128 + wave * 32 + col;
   const int qcl = q < len ? q : len - 1;
   float qr[32];
@@ -467,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_f32_long_kernel(const float
                                                                      int nchunk, float scale, DropCtx drop, long ops, long dps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sK = reinterpret_cast<float*>(smem);
-  float* sV = sK + AFL_NKT * 32 * AF_PITCH;
+  float* sV = sK + AfLds<AFL_NKT>::OFF_B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qc = blockIdx.x % nchunk, sh = blockIdx.x / nchunk;
@@ -481,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_f32_long_kernel(const float
   const bf16_t* Opl = reinterpret_cast<const bf16_t*>(O) + (long)t0 * H + h * 64;
   const float* dOg = dO + (long)t0 * H + h * 64;
   const int col = lane & 31, half = lane >> 5;
-  const float c2 = scale * AF_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const int q = qc * 128 + wave * 32 + col;
   const int qcl = q < len ? q : len - 1;
   const bool qok = q < len;
@@ -498,7 +506,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_f32_long_kernel(const float
     }
   }
   delta += __shfl_xor(delta, 32, 64);
-  const float lq = lse[(long)h * T + t0 + qcl] * AF_LOG2E;
+  const float lq = lse[(long)h * T + t0 + qcl] * ATT_LOG2E;
   f32x16 dq[2];
 #pragma unroll
   for (int e = 0; e < 16; ++e) { dq[0][e] = 0.f; dq[1][e] = 0.f; }
@@ -549,9 +557,9 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_f32_long_kernel(const floa
                                                                       int nchunk, float scale, DropCtx drop, long ops, long dps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sQ = reinterpret_cast<float*>(smem);
-  float* sD = sQ + AFL_NKT * 32 * AF_PITCH;
-  float* sLse = sD + AFL_NKT * 32 * AF_PITCH;
-  float* sDel = sLse + AFL_NKT * 32;
+  float* sD = sQ + AfLds<AFL_NKT>::OFF_B;
+  float* sLse = sQ + AfLds<AFL_NKT>::OFF_LSE;
+  float* sDel = sQ + AfLds<AFL_NKT>::OFF_DEL;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kc = blockIdx.x % nchunk, sh = blockIdx.x / nchunk;
@@ -565,7 +573,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_f32_long_kernel(const floa
   const bf16_t* Opl = reinterpret_cast<const bf16_t*>(O) + (long)t0 * H + h * 64;
   const float* dOg = dO + (long)t0 * H + h * 64;
   const int col = lane & 31, half = lane >> 5;
-  const float c2 = scale * AF_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const int key = kc * 128 + wave * 32 + col;
   const int kcl = key < len ? key : len - 1;
   const bool kok = key < len;
@@ -591,7 +599,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_f32_long_kernel(const floa
           const float4 a = PL ? plane_ld4<f16_t>(Opl + (long)(q0 + r) * H + 4 * i, ops) : po[i], b = pd[i];
           del += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
         }
-        l = lse[(long)h * T + t0 + q0 + r] * AF_LOG2E;
+        l = lse[(long)h * T + t0 + q0 + r] * ATT_LOG2E;
       }
       sDel[r] = del;
       sLse[r] = l;
@@ -643,102 +651,68 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_f32_long_kernel(const floa
 }
 
 // ------------------------------------------------------------------------------------------ host (called from attention.hip)
-template <typename K>
-static int af_set_lds(K kernel, size_t bytes, const char* name) {
-  if (bytes > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    simx_set_error("%s: cannot raise dynamic LDS to %zu", name, bytes);
-    return SIMX_ERR_HIP;
-  }
-  return SIMX_OK;
-}
-
 bool simx_mha_f32_ok(int d, int max_len) {
   static const char* pin = getenv("SIMX_MHA_F32");            // SIMX_MHA_F32=generic pins the one-wave-per-row kernels (A/B)
   return d == 64 && max_len <= 4096 && !(pin && pin[0] == 'g');
 }
 
+// max_len -> the resident kernels' key tiles (of 32 tokens), forward and backward: f(std::integral_constant<int, NKT>{}); 0: the
+// chunked kernels, one workgroup per (sequence, head, 128-token chunk)
+template <typename Fn>
+static int af_by_tiles(int max_len, Fn&& f) {
+  if (max_len > 256) return f(std::integral_constant<int, 0>{});
+  if (max_len <= 32) return f(std::integral_constant<int, 1>{});
+  if (max_len <= 128) return f(std::integral_constant<int, 4>{});
+  if (max_len <= 160) return f(std::integral_constant<int, 5>{});
+  return f(std::integral_constant<int, 8>{});
+}
+
 // ctx_ps > 0: ctx is an fp16 plane pair (hi at ctx, lo at + ctx_ps 16-bit elements) instead of an f32 matrix
 int simx_mha_fwd_f32(hipStream_t s, int nseq, int heads, const int32_t* cu, int max_len, int T, const float* qkv, float* ctx, float* lse,
                      float scale, DropCtx drop, long ctx_ps) {
-  int rc = SIMX_OK;
-#define LF(NKT, DENSE)                                                                                                     \
-  do {                                                                                                                     \
-    const size_t lds = (size_t)2 * NKT * 32 * (DENSE ? 64 : AF_PITCH) * sizeof(float);                                     \
-    if (ctx_ps > 0) {                                                                                                      \
-      rc = af_set_lds((mha_fwd_f32_kernel<NKT, DENSE, true>), lds, "mha_fwd_f32");                                         \
-      if (rc) return rc;                                                                                                   \
-      hipLaunchKernelGGL((mha_fwd_f32_kernel<NKT, DENSE, true>), dim3(nseq * heads), dim3(256), lds, s, qkv, ctx, lse, cu, heads, T, scale, drop, ctx_ps); \
-    } else {                                                                                                               \
-      rc = af_set_lds((mha_fwd_f32_kernel<NKT, DENSE, false>), lds, "mha_fwd_f32");                                        \
-      if (rc) return rc;                                                                                                   \
-      hipLaunchKernelGGL((mha_fwd_f32_kernel<NKT, DENSE, false>), dim3(nseq * heads), dim3(256), lds, s, qkv, ctx, lse, cu, heads, T, scale, drop, 0L); \
-    }                                                                                                                      \
-  } while (0)
   static const bool dense5 = [] { const char* e = getenv("SIMX_MHA_F32_DENSE"); return !e || e[0] != '0'; }();
-  if (max_len > 256) {                             // chunked kernels: one workgroup per (sequence, head, 128-query chunk)
-    const int nchunk = (max_len + 127) / 128;
-    const size_t lds = (size_t)2 * AFL_NKT * 32 * AF_PITCH * sizeof(float);
-    if (ctx_ps > 0) {
-      rc = af_set_lds(mha_fwd_f32_long_kernel<true>, lds, "mha_fwd_f32_long");
-      if (rc) return rc;
-      hipLaunchKernelGGL(mha_fwd_f32_long_kernel<true>, dim3(nseq * heads * nchunk), dim3(256), lds, s, qkv, ctx, lse, cu, heads, T, nchunk, scale, drop, ctx_ps);
-    } else {
-      rc = af_set_lds(mha_fwd_f32_long_kernel<false>, lds, "mha_fwd_f32_long");
-      if (rc) return rc;
-      hipLaunchKernelGGL(mha_fwd_f32_long_kernel<false>, dim3(nseq * heads * nchunk), dim3(256), lds, s, qkv, ctx, lse, cu, heads, T, nchunk, scale, drop, 0L);
-    }
-    SIMX_CHECK_LAUNCH("mha_fwd_f32_long");
-    return SIMX_OK;
-  }
-  if (max_len <= 32) LF(1, false);
-  else if (max_len <= 128) LF(4, false);
-  else if (max_len <= 160 && dense5) LF(5, true);   // exactly 80 KB: two workgroups per CU
-  else if (max_len <= 160) LF(5, false);
-  else LF(8, false);
-#undef LF
-  SIMX_CHECK_LAUNCH("mha_fwd_f32");
-  return SIMX_OK;
+  return af_by_tiles(max_len, [&](auto nkt) {
+    constexpr int NKT = decltype(nkt)::value;
+    return by_flag(NKT == 5 && dense5, [&](auto dense) {         // 5 tiles dense: exactly 80 KB, two workgroups per CU
+      return by_flag(ctx_ps > 0, [&](auto pl) {
+        constexpr bool DENSE = NKT == 5 && decltype(dense)::value, PL = decltype(pl)::value;
+        const long cps = PL ? ctx_ps : 0L;
+        if constexpr (NKT == 0) {
+          const int nchunk = (max_len + 127) / 128;
+          return att_launch<mha_fwd_f32_long_kernel<PL>, AfLds<AFL_NKT>::BYTES>("mha_fwd_f32_long", s, dim3(nseq * heads * nchunk), qkv, ctx, lse, cu,
+                                                                                heads, T, nchunk, scale, drop, cps);
+        } else {
+          return att_launch<mha_fwd_f32_kernel<NKT, DENSE, PL>, AfLds<NKT, DENSE ? 64 : AF_PITCH>::BYTES>("mha_fwd_f32", s, dim3(nseq * heads), qkv, ctx,
+                                                                                                          lse, cu, heads, T, scale, drop, cps);
+        }
+      });
+    });
+  });
 }
 
 // ctx_ps > 0 (planes form): ctx is the forward's fp16 plane pair and dqkv leaves as a bf16 plane pair (lo at + dqkv_ps elements)
 int simx_mha_bwd_f32(hipStream_t s, int nseq, int heads, const int32_t* cu, int max_len, int T, const float* qkv, const float* ctx,
                      const float* lse, const float* dctx, float* dqkv, float scale, DropCtx drop, long ctx_ps, long dqkv_ps) {
-  int rc = SIMX_OK;
-#define LB2(NKT, PL)                                                                                                       \
-  do {                                                                                                                     \
-    const size_t lds = (size_t)2 * NKT * 32 * AF_PITCH * sizeof(float);                                                    \
-    const size_t lds2 = lds + (size_t)2 * NKT * 32 * sizeof(float);                                                        \
-    rc = af_set_lds((mha_bwd_dq_f32_kernel<NKT, PL>), lds, "mha_bwd_f32");                                                 \
-    if (rc) return rc;                                                                                                     \
-    rc = af_set_lds((mha_bwd_dkv_f32_kernel<NKT, PL>), lds2, "mha_bwd_f32");                                               \
-    if (rc) return rc;                                                                                                     \
-    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<NKT, PL>), dim3(nseq * heads), dim3(256), lds, s, qkv, ctx, lse, dctx, dqkv, cu, heads, T, scale, drop, ctx_ps, dqkv_ps); \
-    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<NKT, PL>), dim3(nseq * heads), dim3(256), lds2, s, qkv, ctx, lse, dctx, dqkv, cu, heads, T, scale, drop, ctx_ps, dqkv_ps); \
-  } while (0)
-#define LB(NKT) do { if (ctx_ps > 0) LB2(NKT, true); else LB2(NKT, false); } while (0)
-  if (max_len > 256) {
-    const int nchunk = (max_len + 127) / 128;
-    const size_t lds = (size_t)2 * AFL_NKT * 32 * AF_PITCH * sizeof(float), lds2 = lds + (size_t)2 * AFL_NKT * 32 * sizeof(float);
-#define LBL(PL)                                                                                                            \
-  do {                                                                                                                     \
-    rc = af_set_lds(mha_bwd_dq_f32_long_kernel<PL>, lds, "mha_bwd_f32_long");                                              \
-    if (rc) return rc;                                                                                                     \
-    rc = af_set_lds(mha_bwd_dkv_f32_long_kernel<PL>, lds2, "mha_bwd_f32_long");                                            \
-    if (rc) return rc;                                                                                                     \
-    hipLaunchKernelGGL(mha_bwd_dq_f32_long_kernel<PL>, dim3(nseq * heads * nchunk), dim3(256), lds, s, qkv, ctx, lse, dctx, dqkv, cu, heads, T, nchunk, scale, drop, ctx_ps, dqkv_ps); \
-    hipLaunchKernelGGL(mha_bwd_dkv_f32_long_kernel<PL>, dim3(nseq * heads * nchunk), dim3(256), lds2, s, qkv, ctx, lse, dctx, dqkv, cu, heads, T, nchunk, scale, drop, ctx_ps, dqkv_ps); \
-  } while (0)
-    if (ctx_ps > 0) LBL(true); else LBL(false);
-#undef LBL
-    SIMX_CHECK_LAUNCH("mha_bwd_f32_long");
-    return SIMX_OK;
-  }
-  if (max_len <= 32) LB(1);
-  else if (max_len <= 128) LB(4);
-  else if (max_len <= 160) LB(5);
-  else LB(8);
-#undef LB
-#undef LB2
-  SIMX_CHECK_LAUNCH("mha_bwd_f32");
-  return SIMX_OK;
+  return af_by_tiles(max_len, [&](auto nkt) {
+    return by_flag(ctx_ps > 0, [&](auto pl) {
+      constexpr int NKT = decltype(nkt)::value;
+      constexpr bool PL = decltype(pl)::value;
+      if constexpr (NKT == 0) {
+        const int nchunk = (max_len + 127) / 128;
+        const dim3 grid(nseq * heads * nchunk);
+        const int rc = att_launch<mha_bwd_dq_f32_long_kernel<PL>, AfLds<AFL_NKT>::BYTES>("mha_bwd_f32_long", s, grid, qkv, ctx, lse, dctx, dqkv, cu, heads, T,
+                                                                                         nchunk, scale, drop, ctx_ps, dqkv_ps);
+        if (rc) return rc;
+        return att_launch<mha_bwd_dkv_f32_long_kernel<PL>, AfLds<AFL_NKT>::DKV_BYTES>("mha_bwd_f32_long", s, grid, qkv, ctx, lse, dctx, dqkv, cu, heads, T,
+                                                                                      nchunk, scale, drop, ctx_ps, dqkv_ps);
+      } else {
+        const dim3 grid(nseq * heads);
+        const int rc = att_launch<mha_bwd_dq_f32_kernel<NKT, PL>, AfLds<NKT>::BYTES>("mha_bwd_f32", s, grid, qkv, ctx, lse, dctx, dqkv, cu, heads, T, scale,
+                                                                                     drop, ctx_ps, dqkv_ps);
+        if (rc) return rc;
+        return att_launch<mha_bwd_dkv_f32_kernel<NKT, PL>, AfLds<NKT>::DKV_BYTES>("mha_bwd_f32", s, grid, qkv, ctx, lse, dctx, dqkv, cu, heads, T, scale,
+                                                                                  drop, ctx_ps, dqkv_ps);
+      }
+    });
+  });
 }

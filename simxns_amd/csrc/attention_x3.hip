@@ -16,34 +16,26 @@
 //     stage.  No loss scale, no overflow: |dS| <= 64 max|v| after the scaling.
 // Kernel structure = attention.hip's (scores transposed so that a softmax row is a lane column, P / dS feed the second product
 // from registers, token-contracted operands by ds_read_b64_tr_b16), with hi / lo tiles and three MFMAs per product.
-#include <type_traits>
-#include "common.h"
+#include "att.h"
 #include "prof.h"
 
-#define X3_LOG2E 1.4426950408889634f
-
-__device__ __forceinline__ int x3a_f(int row) {
-  const int i = (row >> 1) & 7;
-  return (((i << 1) & 7) + (i >> 2) * 5) & 7;
-}
-__device__ __forceinline__ int x3a_off(int row, int c16) { return row * 128 + ((c16 ^ x3a_f(row)) << 4); }
-// stage rows [0, rows_pad) x 64 16-bit values of one head slice by LDS-DMA; rows >= len are clamped copies of row len-1
-__device__ __forceinline__ void x3a_stage(const bf16_t* __restrict__ G, long ld, int len, int rows_pad, char* lds, int wave, int lane, int nwaves) {
-  for (int i = wave; i < (rows_pad >> 3); i += nwaves) {
-    const int r = i * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ x3a_f(r);
-    const int gr = r < len ? r : len - 1;
-    glds16(G + (long)gr * ld + c * 8, lds + i * 1024);
-  }
-}
-__device__ __forceinline__ bf16x8 x3a_row_frag(const char* tile, int row, int c16) {
-  return *reinterpret_cast<const bf16x8*>(tile + x3a_off(row, c16));
-}
-#define X3A_RDTR(DST, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=&v"(DST) : "v"(ADDR) : "memory")
-#define X3A_CAT(LO, HI) ((bf16x8){LO[0], LO[1], LO[2], LO[3], HI[0], HI[1], HI[2], HI[3]})
-
 // ------------------------------------------------------------------------------------------ forward
-// LDS: Khi | Klo | Vhi | Vlo, each NKT * 16 rows x 128 B.  One workgroup (4 waves) per (sequence, head).
+// LDS layouts (the chunked kernels use them with NKT = XL_CH / 16).  Every kernel holds four tiles of NKT * 16 rows x 128 B:
+// Khi | Klo | Vhi | Vlo (forward, dQ) or Qhi | Qlo | dOhi | dOlo (dK / dV); then
+//   dQ:      RED: 16 floats for the block maximum of |dO|;
+//   dK / dV: VEC: lse[NKT*16], delta[NKT*16] (f32) and the 16 floats of the block maximum;
+//            MSK: dropout bits [key tile][query], 16 bits = the keys of the tile (DROP only).
+template <int NKT>
+struct X3FwdLds { static constexpr int TILE = NKT * 16 * 128, BYTES = 4 * TILE; };
+template <int NKT>
+struct X3DqLds { static constexpr int TILE = NKT * 16 * 128, RED = 4 * TILE, BYTES = RED + 64; };
+template <int NKT, bool DROP>
+struct X3DkvLds {
+  static constexpr int TILE = NKT * 16 * 128, VEC = 4 * TILE, MSK = VEC + 2 * NKT * 16 * 4 + 64;
+  static constexpr int BYTES = MSK + (DROP ? NKT * 16 * NKT * 2 : 0);
+};
+
+// One workgroup (4 waves) per (sequence, head).
 // (DROP and ALLT -- every one of the NKT key tiles present -- are compile-time: the query-tile loop then has no uniform branch
 // inside and is scheduled as one block, see mha_fwd_h16_kernel)
 template <int NKT, bool DROP>
@@ -63,25 +55,21 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_kernel(const bf16_t* __rest
   const bf16_t* Vg = Kg + H;
   const int nkt = (len + 15) >> 4;
   const int nkt2 = (nkt + 1) & ~1;
-  constexpr int TILE = NKT * 16 * 128;
+  constexpr int TILE = X3FwdLds<NKT>::TILE;
   char* sKh = smem;
   char* sKl = smem + TILE;
   char* sVh = smem + 2 * TILE;
-  x3a_stage(Kg, H3, len, nkt2 * 16, sKh, wave, lane, 4);
-  x3a_stage(Kg + qps, H3, len, nkt2 * 16, sKl, wave, lane, 4);
-  x3a_stage(Vg, H3, len, nkt2 * 16, sVh, wave, lane, 4);
-  x3a_stage(Vg + qps, H3, len, nkt2 * 16, sVh + TILE, wave, lane, 4);
+  att_stage(Kg, H3, len, nkt2 * 16, sKh, wave, lane, 4);
+  att_stage(Kg + qps, H3, len, nkt2 * 16, sKl, wave, lane, 4);
+  att_stage(Vg, H3, len, nkt2 * 16, sVh, wave, lane, 4);
+  att_stage(Vg + qps, H3, len, nkt2 * 16, sVh + TILE, wave, lane, 4);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   const uint32_t sV_addr = (uint32_t)(uintptr_t)sVh;
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * X3_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   uint32_t vtr[4];
-  {
-    const int rr = 4 * fg + (fr >> 2), tsw = x3a_f(rr), tx = (fr & 3) >> 1;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vtr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
-  }
+  ATT_VTR(fr, fg, vtr);
   auto tiles = [&](auto allt_c) {
   constexpr bool ALLT = decltype(allt_c)::value;
   for (int qt = wave; qt < nkt; qt += 4) {
@@ -98,8 +86,8 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_kernel(const bf16_t* __rest
     for (int kt = 0; kt < NKT; ++kt) {
       if (ALLT || kt < nkt) {
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, fg), x3a_row_frag(sKl, kt * 16 + fr, fg), qh[0], ql[0], a);
-        a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, 4 + fg), x3a_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[1], ql[1], a);
+        a = plane_mfma3<f16_t>(att_row_frag(sKh, kt * 16 + fr, fg), att_row_frag(sKl, kt * 16 + fr, fg), qh[0], ql[0], a);
+        a = plane_mfma3<f16_t>(att_row_frag(sKh, kt * 16 + fr, 4 + fg), att_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[1], ql[1], a);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = kt * 16 + 4 * fg + r;
@@ -143,19 +131,19 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_kernel(const bf16_t* __rest
       if (ALLT || 2 * kb < nkt) {                    // (rows past the padded length are uninitialised LDS: never multiplied)
         const uint32_t b0 = sV_addr + (uint32_t)(kb * 4096);
         bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-        X3A_RDTR(h0l, b0 + vtr[0], 0); X3A_RDTR(h0h, b0 + vtr[0], 2048); X3A_RDTR(h1l, b0 + vtr[1], 0); X3A_RDTR(h1h, b0 + vtr[1], 2048);
-        X3A_RDTR(h2l, b0 + vtr[2], 0); X3A_RDTR(h2h, b0 + vtr[2], 2048); X3A_RDTR(h3l, b0 + vtr[3], 0); X3A_RDTR(h3h, b0 + vtr[3], 2048);
+        ATT_RDTR(h0l, b0 + vtr[0], 0); ATT_RDTR(h0h, b0 + vtr[0], 2048); ATT_RDTR(h1l, b0 + vtr[1], 0); ATT_RDTR(h1h, b0 + vtr[1], 2048);
+        ATT_RDTR(h2l, b0 + vtr[2], 0); ATT_RDTR(h2h, b0 + vtr[2], 2048); ATT_RDTR(h3l, b0 + vtr[3], 0); ATT_RDTR(h3h, b0 + vtr[3], 2048);
         const uint32_t b1 = b0 + (uint32_t)TILE;
-        X3A_RDTR(l0l, b1 + vtr[0], 0); X3A_RDTR(l0h, b1 + vtr[0], 2048); X3A_RDTR(l1l, b1 + vtr[1], 0); X3A_RDTR(l1h, b1 + vtr[1], 2048);
-        X3A_RDTR(l2l, b1 + vtr[2], 0); X3A_RDTR(l2h, b1 + vtr[2], 2048); X3A_RDTR(l3l, b1 + vtr[3], 0); X3A_RDTR(l3h, b1 + vtr[3], 2048);
+        ATT_RDTR(l0l, b1 + vtr[0], 0); ATT_RDTR(l0h, b1 + vtr[0], 2048); ATT_RDTR(l1l, b1 + vtr[1], 0); ATT_RDTR(l1h, b1 + vtr[1], 2048);
+        ATT_RDTR(l2l, b1 + vtr[2], 0); ATT_RDTR(l2h, b1 + vtr[2], 2048); ATT_RDTR(l3l, b1 + vtr[3], 0); ATT_RDTR(l3h, b1 + vtr[3], 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
         bf16x8 ph, pl;
         plane_split_frag<f16_t>(s[2 * kb], s[2 * kb + 1], ph, pl);
-        o[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, o[0]);
-        o[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, o[1]);
-        o[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, o[2]);
-        o[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, o[3]);
+        o[0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), ph, pl, o[0]);
+        o[1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), ph, pl, o[1]);
+        o[2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), ph, pl, o[2]);
+        o[3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), ph, pl, o[3]);
       }
     }
     if (q < len) {
@@ -173,7 +161,6 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_kernel(const bf16_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------ backward
-#define X3A_RD128(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=&v"(DST) : "v"(ADDR) : "memory")
 // power-of-two scale that brings g (> 0, finite) into [1, 2): returns {2^-floor(log2 g), 2^floor(log2 g)}; g == 0 / inf / nan -> {1, 1}
 __device__ __forceinline__ void x3a_pow2_scale(float g, float& sc, float& inv) {
   const uint32_t e = (__float_as_uint(g) >> 23) & 255u;
@@ -251,28 +238,27 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_kernel(const bf16_t* __r
   const float* dOg = dO + (long)t0 * H + h * 64;
   const int nkt = (len + 15) >> 4;
   const int nkt2 = (nkt + 1) & ~1;
-  constexpr int TILE = NKT * 16 * 128;
+  using Lds = X3DqLds<NKT>;
+  constexpr int TILE = Lds::TILE;
   f32x4 csq[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) csq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  x3a_stage(Kg, H3, len, nkt2 * 16, smem, wave, lane, 4);
-  x3a_stage(Kg + qps, H3, len, nkt2 * 16, smem + TILE, wave, lane, 4);
-  x3a_stage(Vg, H3, len, nkt2 * 16, smem + 2 * TILE, wave, lane, 4);
-  x3a_stage(Vg + qps, H3, len, nkt2 * 16, smem + 3 * TILE, wave, lane, 4);
-  float* red = reinterpret_cast<float*>(smem + 4 * TILE);
+  att_stage(Kg, H3, len, nkt2 * 16, smem, wave, lane, 4);
+  att_stage(Kg + qps, H3, len, nkt2 * 16, smem + TILE, wave, lane, 4);
+  att_stage(Vg, H3, len, nkt2 * 16, smem + 2 * TILE, wave, lane, 4);
+  att_stage(Vg + qps, H3, len, nkt2 * 16, smem + 3 * TILE, wave, lane, 4);
+  float* red = reinterpret_cast<float*>(smem + Lds::RED);
   float sc, isc;
   x3a_pow2_scale(x3a_block_absmax(dOg, H, len, tid, 256, red), sc, isc);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * X3_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  const int fsw = x3a_f(fr);
+  const int fsw = att_f(fr);
   const uint32_t rf_lo = (uint32_t)(fr * 128 + ((fg ^ fsw) << 4)), rf_hi = (uint32_t)(fr * 128 + (((4 + fg) ^ fsw) << 4));
-  const int rr = 4 * fg + (fr >> 2), tsw = x3a_f(rr), tx = (fr & 3) >> 1;
   uint32_t tr[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) tr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
+  ATT_VTR(fr, fg, tr);
   for (int qt = wave; qt < nkt; qt += 4) {
     const int q = qt * 16 + fr;
     const int qc = q < len ? q : len - 1;
@@ -298,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_kernel(const bf16_t* __r
     }
     delta += __shfl_xor(delta, 16, 64);
     delta += __shfl_xor(delta, 32, 64);
-    const float lq = lse[(long)h * T + t0 + qc] * X3_LOG2E;
+    const float lq = lse[(long)h * T + t0 + qc] * ATT_LOG2E;
     f32x4 dq[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -307,10 +293,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_kernel(const bf16_t* __r
       f32x4 ds[2];
       // both key tiles' row fragments in flight, one wait (the pair iteration is one basic block: DROP is compile-time)
       bf16x8 kh[2][2], kl[2][2], vh[2][2], vl[2][2];
-      X3A_RD128(kh[0][0], bkh + rf_lo, 0); X3A_RD128(kh[0][1], bkh + rf_hi, 0); X3A_RD128(kl[0][0], bkl + rf_lo, 0); X3A_RD128(kl[0][1], bkl + rf_hi, 0);
-      X3A_RD128(vh[0][0], bvh + rf_lo, 0); X3A_RD128(vh[0][1], bvh + rf_hi, 0); X3A_RD128(vl[0][0], bvl + rf_lo, 0); X3A_RD128(vl[0][1], bvl + rf_hi, 0);
-      X3A_RD128(kh[1][0], bkh + rf_lo, 2048); X3A_RD128(kh[1][1], bkh + rf_hi, 2048); X3A_RD128(kl[1][0], bkl + rf_lo, 2048); X3A_RD128(kl[1][1], bkl + rf_hi, 2048);
-      X3A_RD128(vh[1][0], bvh + rf_lo, 2048); X3A_RD128(vh[1][1], bvh + rf_hi, 2048); X3A_RD128(vl[1][0], bvl + rf_lo, 2048); X3A_RD128(vl[1][1], bvl + rf_hi, 2048);
+      ATT_RD128(kh[0][0], bkh + rf_lo, 0); ATT_RD128(kh[0][1], bkh + rf_hi, 0); ATT_RD128(kl[0][0], bkl + rf_lo, 0); ATT_RD128(kl[0][1], bkl + rf_hi, 0);
+      ATT_RD128(vh[0][0], bvh + rf_lo, 0); ATT_RD128(vh[0][1], bvh + rf_hi, 0); ATT_RD128(vl[0][0], bvl + rf_lo, 0); ATT_RD128(vl[0][1], bvl + rf_hi, 0);
+      ATT_RD128(kh[1][0], bkh + rf_lo, 2048); ATT_RD128(kh[1][1], bkh + rf_hi, 2048); ATT_RD128(kl[1][0], bkl + rf_lo, 2048); ATT_RD128(kl[1][1], bkl + rf_hi, 2048);
+      ATT_RD128(vh[1][0], bvh + rf_lo, 2048); ATT_RD128(vh[1][1], bvh + rf_hi, 2048); ATT_RD128(vl[1][0], bvl + rf_lo, 2048); ATT_RD128(vl[1][1], bvl + rf_hi, 2048);
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kh[0][0]), "+v"(kh[0][1]), "+v"(kl[0][0]), "+v"(kl[0][1]), "+v"(vh[0][0]), "+v"(vh[0][1]), "+v"(vl[0][0]), "+v"(vl[0][1]),
                    "+v"(kh[1][0]), "+v"(kh[1][1]), "+v"(kl[1][0]), "+v"(kl[1][1]), "+v"(vh[1][0]), "+v"(vh[1][1]), "+v"(vl[1][0]), "+v"(vl[1][1])::"memory");
 #pragma unroll
@@ -331,18 +317,18 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_kernel(const bf16_t* __r
         }
       }
       bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-      X3A_RDTR(h0l, bkh + tr[0], 0); X3A_RDTR(h0h, bkh + tr[0], 2048); X3A_RDTR(h1l, bkh + tr[1], 0); X3A_RDTR(h1h, bkh + tr[1], 2048);
-      X3A_RDTR(h2l, bkh + tr[2], 0); X3A_RDTR(h2h, bkh + tr[2], 2048); X3A_RDTR(h3l, bkh + tr[3], 0); X3A_RDTR(h3h, bkh + tr[3], 2048);
-      X3A_RDTR(l0l, bkl + tr[0], 0); X3A_RDTR(l0h, bkl + tr[0], 2048); X3A_RDTR(l1l, bkl + tr[1], 0); X3A_RDTR(l1h, bkl + tr[1], 2048);
-      X3A_RDTR(l2l, bkl + tr[2], 0); X3A_RDTR(l2h, bkl + tr[2], 2048); X3A_RDTR(l3l, bkl + tr[3], 0); X3A_RDTR(l3h, bkl + tr[3], 2048);
+      ATT_RDTR(h0l, bkh + tr[0], 0); ATT_RDTR(h0h, bkh + tr[0], 2048); ATT_RDTR(h1l, bkh + tr[1], 0); ATT_RDTR(h1h, bkh + tr[1], 2048);
+      ATT_RDTR(h2l, bkh + tr[2], 0); ATT_RDTR(h2h, bkh + tr[2], 2048); ATT_RDTR(h3l, bkh + tr[3], 0); ATT_RDTR(h3h, bkh + tr[3], 2048);
+      ATT_RDTR(l0l, bkl + tr[0], 0); ATT_RDTR(l0h, bkl + tr[0], 2048); ATT_RDTR(l1l, bkl + tr[1], 0); ATT_RDTR(l1h, bkl + tr[1], 2048);
+      ATT_RDTR(l2l, bkl + tr[2], 0); ATT_RDTR(l2h, bkl + tr[2], 2048); ATT_RDTR(l3l, bkl + tr[3], 0); ATT_RDTR(l3h, bkl + tr[3], 2048);
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                    "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
       bf16x8 sh, sl;
       plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
-      dq[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dq[0]);
-      dq[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dq[1]);
-      dq[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dq[2]);
-      dq[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dq[3]);
+      dq[0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), sh, sl, dq[0]);
+      dq[1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), sh, sl, dq[1]);
+      dq[2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), sh, sl, dq[2]);
+      dq[3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), sh, sl, dq[3]);
     }
     x3a_store_planes_bf16(dq, isc, dqkv + (long)(t0 + qt * 16) * H3 + h * 64, H3, dps, len - qt * 16, lane);
 #pragma unroll
@@ -378,19 +364,18 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
   const float* dOg = dO + (long)t0 * H + h * 64;
   const int nkt = (len + 15) >> 4;
   const int nkt2 = (nkt + 1) & ~1;
-  constexpr int TILE = NKT * 16 * 128;
+  using Lds = X3DkvLds<NKT, DROP>;
+  constexpr int TILE = Lds::TILE, VEC = Lds::VEC, MSK = Lds::MSK;
   char* sDh = smem + 2 * TILE;
   char* sDl = smem + 3 * TILE;
   f32x4 csk[4], csv[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) { csk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; csv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  float* sLse = reinterpret_cast<float*>(smem + 4 * TILE);
+  float* sLse = reinterpret_cast<float*>(smem + VEC);
   float* sDel = sLse + NKT * 16;
   float* red = sDel + NKT * 16;
-  constexpr int VEC = 4 * TILE;
-  constexpr int MSK = VEC + 2 * NKT * 16 * 4 + 64;   // dropout bits [key tile][query]: 16 bits = the keys of the tile
-  x3a_stage(Qg, H3, len, nkt2 * 16, smem, wave, lane, 4);
-  x3a_stage(Qg + qps, H3, len, nkt2 * 16, smem + TILE, wave, lane, 4);
+  att_stage(Qg, H3, len, nkt2 * 16, smem, wave, lane, 4);
+  att_stage(Qg + qps, H3, len, nkt2 * 16, smem + TILE, wave, lane, 4);
   float sc, isc;
   x3a_pow2_scale(x3a_block_absmax(dOg, H, len, tid, 256, red), sc, isc);
   // scaled dO pair into the swizzled tile image, delta_i = dO_i . O_i (8 threads per row), lse in log2 units
@@ -410,11 +395,11 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
     del += __shfl_xor(del, 4, 64);
     bf16x8 fh, fl;
     plane_split_frag<f16_t>(d, fh, fl);
-    *reinterpret_cast<bf16x8*>(sDh + x3a_off(r, c)) = fh;
-    *reinterpret_cast<bf16x8*>(sDl + x3a_off(r, c)) = fl;
+    *reinterpret_cast<bf16x8*>(sDh + att_off(r, c)) = fh;
+    *reinterpret_cast<bf16x8*>(sDl + att_off(r, c)) = fl;
     if (c == 0) {
       sDel[r] = r < len ? del : 0.f;
-      sLse[r] = r < len ? lse[(long)h * T + t0 + r] * X3_LOG2E : 0.f;
+      sLse[r] = r < len ? lse[(long)h * T + t0 + r] * ATT_LOG2E : 0.f;
     }
   }
   if (DROP) {                                        // keep-bits of (query q, keys kt*16 .. +15): wave -> key tile, lane -> query
@@ -432,14 +417,12 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * X3_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  const int fsw = x3a_f(fr);
+  const int fsw = att_f(fr);
   const uint32_t rf_lo = (uint32_t)(fr * 128 + ((fg ^ fsw) << 4)), rf_hi = (uint32_t)(fr * 128 + (((4 + fg) ^ fsw) << 4));
-  const int rr = 4 * fg + (fr >> 2), tsw = x3a_f(rr), tx = (fr & 3) >> 1;
   uint32_t tr[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) tr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
+  ATT_VTR(fr, fg, tr);
   for (int kt = wave; kt < nkt; kt += 4) {
     const int key = kt * 16 + fr;
     const int kc = key < len ? key : len - 1;
@@ -462,10 +445,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
       bf16x8 qhf[2][2], qlf[2][2], dhf[2][2], dlf[2][2];
       f32x4 lsv[2], dev[2];
       uint2 mb[2] = {make_uint2(~0u, ~0u), make_uint2(~0u, ~0u)};              // keep-bits of the lane's four query rows (16 bits each), per tile
-      X3A_RD128(qhf[0][0], bqh + rf_lo, 0); X3A_RD128(qhf[0][1], bqh + rf_hi, 0); X3A_RD128(qlf[0][0], bql + rf_lo, 0); X3A_RD128(qlf[0][1], bql + rf_hi, 0);
-      X3A_RD128(dhf[0][0], bdh + rf_lo, 0); X3A_RD128(dhf[0][1], bdh + rf_hi, 0); X3A_RD128(dlf[0][0], bdl + rf_lo, 0); X3A_RD128(dlf[0][1], bdl + rf_hi, 0);
-      X3A_RD128(qhf[1][0], bqh + rf_lo, 2048); X3A_RD128(qhf[1][1], bqh + rf_hi, 2048); X3A_RD128(qlf[1][0], bql + rf_lo, 2048); X3A_RD128(qlf[1][1], bql + rf_hi, 2048);
-      X3A_RD128(dhf[1][0], bdh + rf_lo, 2048); X3A_RD128(dhf[1][1], bdh + rf_hi, 2048); X3A_RD128(dlf[1][0], bdl + rf_lo, 2048); X3A_RD128(dlf[1][1], bdl + rf_hi, 2048);
+      ATT_RD128(qhf[0][0], bqh + rf_lo, 0); ATT_RD128(qhf[0][1], bqh + rf_hi, 0); ATT_RD128(qlf[0][0], bql + rf_lo, 0); ATT_RD128(qlf[0][1], bql + rf_hi, 0);
+      ATT_RD128(dhf[0][0], bdh + rf_lo, 0); ATT_RD128(dhf[0][1], bdh + rf_hi, 0); ATT_RD128(dlf[0][0], bdl + rf_lo, 0); ATT_RD128(dlf[0][1], bdl + rf_hi, 0);
+      ATT_RD128(qhf[1][0], bqh + rf_lo, 2048); ATT_RD128(qhf[1][1], bqh + rf_hi, 2048); ATT_RD128(qlf[1][0], bql + rf_lo, 2048); ATT_RD128(qlf[1][1], bql + rf_hi, 2048);
+      ATT_RD128(dhf[1][0], bdh + rf_lo, 2048); ATT_RD128(dhf[1][1], bdh + rf_hi, 2048); ATT_RD128(dlf[1][0], bdl + rf_lo, 2048); ATT_RD128(dlf[1][1], bdl + rf_hi, 2048);
       {
         const uint32_t bl = lds0 + (uint32_t)(VEC + (qp * 32 + 4 * fg) * 4);       // sLse[qp*32 + 4 fg ..]; sDel = + NKT * 64 B
         asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %5\n\tds_read_b128 %3, %5 offset:64"
@@ -503,29 +486,29 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
       plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
       {
         bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-        X3A_RDTR(h0l, bdh + tr[0], 0); X3A_RDTR(h0h, bdh + tr[0], 2048); X3A_RDTR(h1l, bdh + tr[1], 0); X3A_RDTR(h1h, bdh + tr[1], 2048);
-        X3A_RDTR(h2l, bdh + tr[2], 0); X3A_RDTR(h2h, bdh + tr[2], 2048); X3A_RDTR(h3l, bdh + tr[3], 0); X3A_RDTR(h3h, bdh + tr[3], 2048);
-        X3A_RDTR(l0l, bdl + tr[0], 0); X3A_RDTR(l0h, bdl + tr[0], 2048); X3A_RDTR(l1l, bdl + tr[1], 0); X3A_RDTR(l1h, bdl + tr[1], 2048);
-        X3A_RDTR(l2l, bdl + tr[2], 0); X3A_RDTR(l2h, bdl + tr[2], 2048); X3A_RDTR(l3l, bdl + tr[3], 0); X3A_RDTR(l3h, bdl + tr[3], 2048);
+        ATT_RDTR(h0l, bdh + tr[0], 0); ATT_RDTR(h0h, bdh + tr[0], 2048); ATT_RDTR(h1l, bdh + tr[1], 0); ATT_RDTR(h1h, bdh + tr[1], 2048);
+        ATT_RDTR(h2l, bdh + tr[2], 0); ATT_RDTR(h2h, bdh + tr[2], 2048); ATT_RDTR(h3l, bdh + tr[3], 0); ATT_RDTR(h3h, bdh + tr[3], 2048);
+        ATT_RDTR(l0l, bdl + tr[0], 0); ATT_RDTR(l0h, bdl + tr[0], 2048); ATT_RDTR(l1l, bdl + tr[1], 0); ATT_RDTR(l1h, bdl + tr[1], 2048);
+        ATT_RDTR(l2l, bdl + tr[2], 0); ATT_RDTR(l2h, bdl + tr[2], 2048); ATT_RDTR(l3l, bdl + tr[3], 0); ATT_RDTR(l3h, bdl + tr[3], 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
-        dv[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, dv[0]);
-        dv[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, dv[1]);
-        dv[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, dv[2]);
-        dv[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, dv[3]);
+        dv[0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), ph, pl, dv[0]);
+        dv[1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), ph, pl, dv[1]);
+        dv[2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), ph, pl, dv[2]);
+        dv[3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), ph, pl, dv[3]);
       }
       {
         bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-        X3A_RDTR(h0l, bqh + tr[0], 0); X3A_RDTR(h0h, bqh + tr[0], 2048); X3A_RDTR(h1l, bqh + tr[1], 0); X3A_RDTR(h1h, bqh + tr[1], 2048);
-        X3A_RDTR(h2l, bqh + tr[2], 0); X3A_RDTR(h2h, bqh + tr[2], 2048); X3A_RDTR(h3l, bqh + tr[3], 0); X3A_RDTR(h3h, bqh + tr[3], 2048);
-        X3A_RDTR(l0l, bql + tr[0], 0); X3A_RDTR(l0h, bql + tr[0], 2048); X3A_RDTR(l1l, bql + tr[1], 0); X3A_RDTR(l1h, bql + tr[1], 2048);
-        X3A_RDTR(l2l, bql + tr[2], 0); X3A_RDTR(l2h, bql + tr[2], 2048); X3A_RDTR(l3l, bql + tr[3], 0); X3A_RDTR(l3h, bql + tr[3], 2048);
+        ATT_RDTR(h0l, bqh + tr[0], 0); ATT_RDTR(h0h, bqh + tr[0], 2048); ATT_RDTR(h1l, bqh + tr[1], 0); ATT_RDTR(h1h, bqh + tr[1], 2048);
+        ATT_RDTR(h2l, bqh + tr[2], 0); ATT_RDTR(h2h, bqh + tr[2], 2048); ATT_RDTR(h3l, bqh + tr[3], 0); ATT_RDTR(h3h, bqh + tr[3], 2048);
+        ATT_RDTR(l0l, bql + tr[0], 0); ATT_RDTR(l0h, bql + tr[0], 2048); ATT_RDTR(l1l, bql + tr[1], 0); ATT_RDTR(l1h, bql + tr[1], 2048);
+        ATT_RDTR(l2l, bql + tr[2], 0); ATT_RDTR(l2h, bql + tr[2], 2048); ATT_RDTR(l3l, bql + tr[3], 0); ATT_RDTR(l3h, bql + tr[3], 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");   // (one wait names every register in flight)
-        dk[0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dk[0]);
-        dk[1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dk[1]);
-        dk[2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dk[2]);
-        dk[3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dk[3]);
+        dk[0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), sh, sl, dk[0]);
+        dk[1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), sh, sl, dk[1]);
+        dk[2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), sh, sl, dk[2]);
+        dk[3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), sh, sl, dk[3]);
       }
     }
     bf16_t* dst = dqkv + (long)(t0 + kt * 16) * H3 + H + h * 64;
@@ -554,7 +537,6 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_kernel(const bf16_t* __
 // The power-of-two scale of dO is the one of the whole (sequence, head) slice, as above.  No atomics (but the bias gradient's), no
 // f32 scratch; every wave takes part in every barrier.
 #define XL_CH 128
-#define XL_TILE (XL_CH * 128)
 
 template <bool DROP>
 __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* __restrict__ qkv, long qps, bf16_t* __restrict__ ctx, long cps,
@@ -575,17 +557,14 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* _
   const bf16_t* Vg = Kg + H;
   const int nkc = (len + XL_CH - 1) / XL_CH;
   char* sKh = smem;
-  char* sKl = smem + XL_TILE;
-  char* sVh = smem + 2 * XL_TILE;
+  constexpr int TILE = X3FwdLds<XL_CH / 16>::TILE;
+  char* sKl = smem + TILE;
+  char* sVh = smem + 2 * TILE;
   const uint32_t sV_addr = (uint32_t)(uintptr_t)sVh;
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * X3_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   uint32_t vtr[4];
-  {
-    const int rr = 4 * fg + (fr >> 2), tsw = x3a_f(rr), tx = (fr & 3) >> 1;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vtr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
-  }
+  ATT_VTR(fr, fg, vtr);
   bf16x8 qh[2][2], ql[2][2];
   f32x4 o[2][4];
   float mrun[2], lrun[2];
@@ -607,10 +586,10 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* _
     const int nk = len - k0 < XL_CH ? len - k0 : XL_CH;
     const int nkt = (nk + 15) >> 4, nkt2 = (nkt + 1) & ~1;
     __syncthreads();                                 // every wave is done with the previous chunk's tiles
-    x3a_stage(Kg + (long)k0 * H3, H3, nk, nkt2 * 16, sKh, wave, lane, 4);
-    x3a_stage(Kg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, sKl, wave, lane, 4);
-    x3a_stage(Vg + (long)k0 * H3, H3, nk, nkt2 * 16, sVh, wave, lane, 4);
-    x3a_stage(Vg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, sVh + XL_TILE, wave, lane, 4);
+    att_stage(Kg + (long)k0 * H3, H3, nk, nkt2 * 16, sKh, wave, lane, 4);
+    att_stage(Kg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, sKl, wave, lane, 4);
+    att_stage(Vg + (long)k0 * H3, H3, nk, nkt2 * 16, sVh, wave, lane, 4);
+    att_stage(Vg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, sVh + TILE, wave, lane, 4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     auto chunk = [&](auto allt_c) {
@@ -625,8 +604,8 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* _
         for (int kt = 0; kt < 8; ++kt) {
           if (ALLT || kt < nkt) {
             f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, fg), x3a_row_frag(sKl, kt * 16 + fr, fg), qh[j][0], ql[j][0], a);
-            a = plane_mfma3<f16_t>(x3a_row_frag(sKh, kt * 16 + fr, 4 + fg), x3a_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[j][1], ql[j][1], a);
+            a = plane_mfma3<f16_t>(att_row_frag(sKh, kt * 16 + fr, fg), att_row_frag(sKl, kt * 16 + fr, fg), qh[j][0], ql[j][0], a);
+            a = plane_mfma3<f16_t>(att_row_frag(sKh, kt * 16 + fr, 4 + fg), att_row_frag(sKl, kt * 16 + fr, 4 + fg), qh[j][1], ql[j][1], a);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               if (!ALLT) a[r] = k0 + kt * 16 + 4 * fg + r < len ? a[r] : -INFINITY;
@@ -673,19 +652,19 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_x3_long_kernel(const bf16_t* _
           if (ALLT || 2 * kb < nkt) {                  // (rows past the padded length are uninitialised LDS: never multiplied)
             const uint32_t b0 = sV_addr + (uint32_t)(kb * 4096);
             bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-            X3A_RDTR(h0l, b0 + vtr[0], 0); X3A_RDTR(h0h, b0 + vtr[0], 2048); X3A_RDTR(h1l, b0 + vtr[1], 0); X3A_RDTR(h1h, b0 + vtr[1], 2048);
-            X3A_RDTR(h2l, b0 + vtr[2], 0); X3A_RDTR(h2h, b0 + vtr[2], 2048); X3A_RDTR(h3l, b0 + vtr[3], 0); X3A_RDTR(h3h, b0 + vtr[3], 2048);
-            const uint32_t b1 = b0 + (uint32_t)XL_TILE;
-            X3A_RDTR(l0l, b1 + vtr[0], 0); X3A_RDTR(l0h, b1 + vtr[0], 2048); X3A_RDTR(l1l, b1 + vtr[1], 0); X3A_RDTR(l1h, b1 + vtr[1], 2048);
-            X3A_RDTR(l2l, b1 + vtr[2], 0); X3A_RDTR(l2h, b1 + vtr[2], 2048); X3A_RDTR(l3l, b1 + vtr[3], 0); X3A_RDTR(l3h, b1 + vtr[3], 2048);
+            ATT_RDTR(h0l, b0 + vtr[0], 0); ATT_RDTR(h0h, b0 + vtr[0], 2048); ATT_RDTR(h1l, b0 + vtr[1], 0); ATT_RDTR(h1h, b0 + vtr[1], 2048);
+            ATT_RDTR(h2l, b0 + vtr[2], 0); ATT_RDTR(h2h, b0 + vtr[2], 2048); ATT_RDTR(h3l, b0 + vtr[3], 0); ATT_RDTR(h3h, b0 + vtr[3], 2048);
+            const uint32_t b1 = b0 + (uint32_t)TILE;
+            ATT_RDTR(l0l, b1 + vtr[0], 0); ATT_RDTR(l0h, b1 + vtr[0], 2048); ATT_RDTR(l1l, b1 + vtr[1], 0); ATT_RDTR(l1h, b1 + vtr[1], 2048);
+            ATT_RDTR(l2l, b1 + vtr[2], 0); ATT_RDTR(l2h, b1 + vtr[2], 2048); ATT_RDTR(l3l, b1 + vtr[3], 0); ATT_RDTR(l3h, b1 + vtr[3], 2048);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                          "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
             bf16x8 ph, pl;
             plane_split_frag<f16_t>(s[2 * kb], s[2 * kb + 1], ph, pl);
-            o[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, o[j][0]);
-            o[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, o[j][1]);
-            o[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, o[j][2]);
-            o[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, o[j][3]);
+            o[j][0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), ph, pl, o[j][0]);
+            o[j][1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), ph, pl, o[j][1]);
+            o[j][2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), ph, pl, o[j][2]);
+            o[j][3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), ph, pl, o[j][3]);
           }
         }
       }
@@ -729,18 +708,18 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
   const bf16_t* Og = O + (long)t0 * H + h * 64;
   const float* dOg = dO + (long)t0 * H + h * 64;
   const int nkc = (len + XL_CH - 1) / XL_CH;
-  float* red = reinterpret_cast<float*>(smem + 4 * XL_TILE);
+  using Lds = X3DqLds<XL_CH / 16>;
+  constexpr int TILE = Lds::TILE;
+  float* red = reinterpret_cast<float*>(smem + Lds::RED);
   float sc, isc;
   x3a_pow2_scale(x3a_block_absmax(dOg, H, len, tid, 256, red), sc, isc);
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * X3_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  const int fsw = x3a_f(fr);
+  const int fsw = att_f(fr);
   const uint32_t rf_lo = (uint32_t)(fr * 128 + ((fg ^ fsw) << 4)), rf_hi = (uint32_t)(fr * 128 + (((4 + fg) ^ fsw) << 4));
-  const int rr = 4 * fg + (fr >> 2), tsw = x3a_f(rr), tx = (fr & 3) >> 1;
   uint32_t tr[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) tr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
+  ATT_VTR(fr, fg, tr);
   bf16x8 qh[2][2], ql[2][2], dh[2][2], dl[2][2];
   float delta[2], lq[2];
   f32x4 dq[2][4];
@@ -767,7 +746,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
     del += __shfl_xor(del, 16, 64);
     del += __shfl_xor(del, 32, 64);
     delta[j] = del;
-    lq[j] = lse[(long)h * T + t0 + qcl] * X3_LOG2E;
+    lq[j] = lse[(long)h * T + t0 + qcl] * ATT_LOG2E;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dq[j][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
@@ -776,10 +755,10 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
     const int nk = len - k0 < XL_CH ? len - k0 : XL_CH;
     const int nkt = (nk + 15) >> 4, nkt2 = (nkt + 1) & ~1;
     __syncthreads();
-    x3a_stage(Kg + (long)k0 * H3, H3, nk, nkt2 * 16, smem, wave, lane, 4);
-    x3a_stage(Kg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, smem + XL_TILE, wave, lane, 4);
-    x3a_stage(Vg + (long)k0 * H3, H3, nk, nkt2 * 16, smem + 2 * XL_TILE, wave, lane, 4);
-    x3a_stage(Vg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, smem + 3 * XL_TILE, wave, lane, 4);
+    att_stage(Kg + (long)k0 * H3, H3, nk, nkt2 * 16, smem, wave, lane, 4);
+    att_stage(Kg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, smem + TILE, wave, lane, 4);
+    att_stage(Vg + (long)k0 * H3, H3, nk, nkt2 * 16, smem + 2 * TILE, wave, lane, 4);
+    att_stage(Vg + qps + (long)k0 * H3, H3, nk, nkt2 * 16, smem + 3 * TILE, wave, lane, 4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
@@ -788,13 +767,13 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
       const int q = q0 + (wave + 4 * j) * 16 + fr;
       const bool qok = q < len;
       for (int kp = 0; kp < (nkt2 >> 1); ++kp) {
-        const uint32_t bkh = lds0 + (uint32_t)(kp * 4096), bkl = bkh + XL_TILE, bvh = bkh + 2 * XL_TILE, bvl = bkh + 3 * XL_TILE;
+        const uint32_t bkh = lds0 + (uint32_t)(kp * 4096), bkl = bkh + TILE, bvh = bkh + 2 * TILE, bvl = bkh + 3 * TILE;
         f32x4 ds[2];
         bf16x8 kh[2][2], kl[2][2], vh[2][2], vl[2][2];
-        X3A_RD128(kh[0][0], bkh + rf_lo, 0); X3A_RD128(kh[0][1], bkh + rf_hi, 0); X3A_RD128(kl[0][0], bkl + rf_lo, 0); X3A_RD128(kl[0][1], bkl + rf_hi, 0);
-        X3A_RD128(vh[0][0], bvh + rf_lo, 0); X3A_RD128(vh[0][1], bvh + rf_hi, 0); X3A_RD128(vl[0][0], bvl + rf_lo, 0); X3A_RD128(vl[0][1], bvl + rf_hi, 0);
-        X3A_RD128(kh[1][0], bkh + rf_lo, 2048); X3A_RD128(kh[1][1], bkh + rf_hi, 2048); X3A_RD128(kl[1][0], bkl + rf_lo, 2048); X3A_RD128(kl[1][1], bkl + rf_hi, 2048);
-        X3A_RD128(vh[1][0], bvh + rf_lo, 2048); X3A_RD128(vh[1][1], bvh + rf_hi, 2048); X3A_RD128(vl[1][0], bvl + rf_lo, 2048); X3A_RD128(vl[1][1], bvl + rf_hi, 2048);
+        ATT_RD128(kh[0][0], bkh + rf_lo, 0); ATT_RD128(kh[0][1], bkh + rf_hi, 0); ATT_RD128(kl[0][0], bkl + rf_lo, 0); ATT_RD128(kl[0][1], bkl + rf_hi, 0);
+        ATT_RD128(vh[0][0], bvh + rf_lo, 0); ATT_RD128(vh[0][1], bvh + rf_hi, 0); ATT_RD128(vl[0][0], bvl + rf_lo, 0); ATT_RD128(vl[0][1], bvl + rf_hi, 0);
+        ATT_RD128(kh[1][0], bkh + rf_lo, 2048); ATT_RD128(kh[1][1], bkh + rf_hi, 2048); ATT_RD128(kl[1][0], bkl + rf_lo, 2048); ATT_RD128(kl[1][1], bkl + rf_hi, 2048);
+        ATT_RD128(vh[1][0], bvh + rf_lo, 2048); ATT_RD128(vh[1][1], bvh + rf_hi, 2048); ATT_RD128(vl[1][0], bvl + rf_lo, 2048); ATT_RD128(vl[1][1], bvl + rf_hi, 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kh[0][0]), "+v"(kh[0][1]), "+v"(kl[0][0]), "+v"(kl[0][1]), "+v"(vh[0][0]), "+v"(vh[0][1]), "+v"(vl[0][0]), "+v"(vl[0][1]),
                      "+v"(kh[1][0]), "+v"(kh[1][1]), "+v"(kl[1][0]), "+v"(kl[1][1]), "+v"(vh[1][0]), "+v"(vh[1][1]), "+v"(vl[1][0]), "+v"(vl[1][1])::"memory");
 #pragma unroll
@@ -815,18 +794,18 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_x3_long_kernel(const bf16_t
           }
         }
         bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-        X3A_RDTR(h0l, bkh + tr[0], 0); X3A_RDTR(h0h, bkh + tr[0], 2048); X3A_RDTR(h1l, bkh + tr[1], 0); X3A_RDTR(h1h, bkh + tr[1], 2048);
-        X3A_RDTR(h2l, bkh + tr[2], 0); X3A_RDTR(h2h, bkh + tr[2], 2048); X3A_RDTR(h3l, bkh + tr[3], 0); X3A_RDTR(h3h, bkh + tr[3], 2048);
-        X3A_RDTR(l0l, bkl + tr[0], 0); X3A_RDTR(l0h, bkl + tr[0], 2048); X3A_RDTR(l1l, bkl + tr[1], 0); X3A_RDTR(l1h, bkl + tr[1], 2048);
-        X3A_RDTR(l2l, bkl + tr[2], 0); X3A_RDTR(l2h, bkl + tr[2], 2048); X3A_RDTR(l3l, bkl + tr[3], 0); X3A_RDTR(l3h, bkl + tr[3], 2048);
+        ATT_RDTR(h0l, bkh + tr[0], 0); ATT_RDTR(h0h, bkh + tr[0], 2048); ATT_RDTR(h1l, bkh + tr[1], 0); ATT_RDTR(h1h, bkh + tr[1], 2048);
+        ATT_RDTR(h2l, bkh + tr[2], 0); ATT_RDTR(h2h, bkh + tr[2], 2048); ATT_RDTR(h3l, bkh + tr[3], 0); ATT_RDTR(h3h, bkh + tr[3], 2048);
+        ATT_RDTR(l0l, bkl + tr[0], 0); ATT_RDTR(l0h, bkl + tr[0], 2048); ATT_RDTR(l1l, bkl + tr[1], 0); ATT_RDTR(l1h, bkl + tr[1], 2048);
+        ATT_RDTR(l2l, bkl + tr[2], 0); ATT_RDTR(l2h, bkl + tr[2], 2048); ATT_RDTR(l3l, bkl + tr[3], 0); ATT_RDTR(l3h, bkl + tr[3], 2048);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                      "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
         bf16x8 sh, sl;
         plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
-        dq[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dq[j][0]);
-        dq[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dq[j][1]);
-        dq[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dq[j][2]);
-        dq[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dq[j][3]);
+        dq[j][0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), sh, sl, dq[j][0]);
+        dq[j][1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), sh, sl, dq[j][1]);
+        dq[j][2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), sh, sl, dq[j][2]);
+        dq[j][3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), sh, sl, dq[j][3]);
       }
     }
   }
@@ -865,24 +844,22 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
   const bf16_t* Og = O + (long)t0 * H + h * 64;
   const float* dOg = dO + (long)t0 * H + h * 64;
   const int nqc = (len + XL_CH - 1) / XL_CH;
-  constexpr int VEC = 4 * XL_TILE;                    // lse[128], delta[128], red[16], dropout bits [key tile][query]
-  constexpr int MSK = VEC + 2 * XL_CH * 4 + 64;
-  char* sDh = smem + 2 * XL_TILE;
-  char* sDl = smem + 3 * XL_TILE;
+  using Lds = X3DkvLds<XL_CH / 16, DROP>;
+  constexpr int TILE = Lds::TILE, VEC = Lds::VEC, MSK = Lds::MSK;
+  char* sDh = smem + 2 * TILE;
+  char* sDl = smem + 3 * TILE;
   float* sLse = reinterpret_cast<float*>(smem + VEC);
   float* sDel = sLse + XL_CH;
   float* red = sDel + XL_CH;
   float sc, isc;
   x3a_pow2_scale(x3a_block_absmax(dOg, H, len, tid, 256, red), sc, isc);
   const int fr = lane & 15, fg = lane >> 4;
-  const float c2 = scale * X3_LOG2E;
+  const float c2 = scale * ATT_LOG2E;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  const int fsw = x3a_f(fr);
+  const int fsw = att_f(fr);
   const uint32_t rf_lo = (uint32_t)(fr * 128 + ((fg ^ fsw) << 4)), rf_hi = (uint32_t)(fr * 128 + (((4 + fg) ^ fsw) << 4));
-  const int rr = 4 * fg + (fr >> 2), tsw = x3a_f(rr), tx = (fr & 3) >> 1;
   uint32_t tr[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) tr[dt] = (uint32_t)(rr * 128 + (((dt * 2 + tx) ^ tsw) << 4) + (fr & 1) * 8);
+  ATT_VTR(fr, fg, tr);
   f32x4 dk[2][4], dv[2][4];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -893,8 +870,8 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
     const int nq = len - q0 < XL_CH ? len - q0 : XL_CH;
     const int nqt = (nq + 15) >> 4, nqt2 = (nqt + 1) & ~1;
     __syncthreads();                                 // every wave is done with the previous chunk's tiles
-    x3a_stage(Qg + (long)q0 * H3, H3, nq, nqt2 * 16, smem, wave, lane, 4);
-    x3a_stage(Qg + qps + (long)q0 * H3, H3, nq, nqt2 * 16, smem + XL_TILE, wave, lane, 4);
+    att_stage(Qg + (long)q0 * H3, H3, nq, nqt2 * 16, smem, wave, lane, 4);
+    att_stage(Qg + qps + (long)q0 * H3, H3, nq, nqt2 * 16, smem + TILE, wave, lane, 4);
     // scaled dO pair into the swizzled tile image, delta_i = dO_i . O_i (8 threads per row), lse in log2 units
     for (int idx = tid; idx < nqt2 * 16 * 8; idx += 256) {
       const int r = idx >> 3, c = idx & 7;
@@ -912,11 +889,11 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
       del += __shfl_xor(del, 4, 64);
       bf16x8 fh, fl;
       plane_split_frag<f16_t>(d, fh, fl);
-      *reinterpret_cast<bf16x8*>(sDh + x3a_off(r, c)) = fh;
-      *reinterpret_cast<bf16x8*>(sDl + x3a_off(r, c)) = fl;
+      *reinterpret_cast<bf16x8*>(sDh + att_off(r, c)) = fh;
+      *reinterpret_cast<bf16x8*>(sDl + att_off(r, c)) = fl;
       if (c == 0) {
         sDel[r] = r < nq ? del : 0.f;
-        sLse[r] = r < nq ? lse[(long)h * T + t0 + gr] * X3_LOG2E : 0.f;
+        sLse[r] = r < nq ? lse[(long)h * T + t0 + gr] * ATT_LOG2E : 0.f;
       }
     }
     if (DROP) {                                      // keep-bits of (query q0 + q, keys k0 + ktl*16 .. +15): wave -> key tile, lane -> query
@@ -950,15 +927,15 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
       vl0 = *reinterpret_cast<const bf16x8*>(Vg + qps + (long)kcl * H3 + fg * 8);
       vl1 = *reinterpret_cast<const bf16x8*>(Vg + qps + (long)kcl * H3 + 32 + fg * 8);
       for (int qp = 0; qp < (nqt2 >> 1); ++qp) {
-        const uint32_t bqh = lds0 + (uint32_t)(qp * 4096), bql = bqh + XL_TILE, bdh = bqh + 2 * XL_TILE, bdl = bqh + 3 * XL_TILE;
+        const uint32_t bqh = lds0 + (uint32_t)(qp * 4096), bql = bqh + TILE, bdh = bqh + 2 * TILE, bdl = bqh + 3 * TILE;
         f32x4 pp[2], ds[2];
         bf16x8 qhf[2][2], qlf[2][2], dhf[2][2], dlf[2][2];
         f32x4 lsv[2], dev[2];
         uint2 mb[2] = {make_uint2(~0u, ~0u), make_uint2(~0u, ~0u)};
-        X3A_RD128(qhf[0][0], bqh + rf_lo, 0); X3A_RD128(qhf[0][1], bqh + rf_hi, 0); X3A_RD128(qlf[0][0], bql + rf_lo, 0); X3A_RD128(qlf[0][1], bql + rf_hi, 0);
-        X3A_RD128(dhf[0][0], bdh + rf_lo, 0); X3A_RD128(dhf[0][1], bdh + rf_hi, 0); X3A_RD128(dlf[0][0], bdl + rf_lo, 0); X3A_RD128(dlf[0][1], bdl + rf_hi, 0);
-        X3A_RD128(qhf[1][0], bqh + rf_lo, 2048); X3A_RD128(qhf[1][1], bqh + rf_hi, 2048); X3A_RD128(qlf[1][0], bql + rf_lo, 2048); X3A_RD128(qlf[1][1], bql + rf_hi, 2048);
-        X3A_RD128(dhf[1][0], bdh + rf_lo, 2048); X3A_RD128(dhf[1][1], bdh + rf_hi, 2048); X3A_RD128(dlf[1][0], bdl + rf_lo, 2048); X3A_RD128(dlf[1][1], bdl + rf_hi, 2048);
+        ATT_RD128(qhf[0][0], bqh + rf_lo, 0); ATT_RD128(qhf[0][1], bqh + rf_hi, 0); ATT_RD128(qlf[0][0], bql + rf_lo, 0); ATT_RD128(qlf[0][1], bql + rf_hi, 0);
+        ATT_RD128(dhf[0][0], bdh + rf_lo, 0); ATT_RD128(dhf[0][1], bdh + rf_hi, 0); ATT_RD128(dlf[0][0], bdl + rf_lo, 0); ATT_RD128(dlf[0][1], bdl + rf_hi, 0);
+        ATT_RD128(qhf[1][0], bqh + rf_lo, 2048); ATT_RD128(qhf[1][1], bqh + rf_hi, 2048); ATT_RD128(qlf[1][0], bql + rf_lo, 2048); ATT_RD128(qlf[1][1], bql + rf_hi, 2048);
+        ATT_RD128(dhf[1][0], bdh + rf_lo, 2048); ATT_RD128(dhf[1][1], bdh + rf_hi, 2048); ATT_RD128(dlf[1][0], bdl + rf_lo, 2048); ATT_RD128(dlf[1][1], bdl + rf_hi, 2048);
         {
           const uint32_t bl = lds0 + (uint32_t)(VEC + (qp * 32 + 4 * fg) * 4);       // sLse[qp*32 + 4 fg ..]; sDel = + 512 B
           asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %5\n\tds_read_b128 %3, %5 offset:64"
@@ -995,29 +972,29 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
         plane_split_frag<f16_t>(ds[0], ds[1], sh, sl);
         {
           bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-          X3A_RDTR(h0l, bdh + tr[0], 0); X3A_RDTR(h0h, bdh + tr[0], 2048); X3A_RDTR(h1l, bdh + tr[1], 0); X3A_RDTR(h1h, bdh + tr[1], 2048);
-          X3A_RDTR(h2l, bdh + tr[2], 0); X3A_RDTR(h2h, bdh + tr[2], 2048); X3A_RDTR(h3l, bdh + tr[3], 0); X3A_RDTR(h3h, bdh + tr[3], 2048);
-          X3A_RDTR(l0l, bdl + tr[0], 0); X3A_RDTR(l0h, bdl + tr[0], 2048); X3A_RDTR(l1l, bdl + tr[1], 0); X3A_RDTR(l1h, bdl + tr[1], 2048);
-          X3A_RDTR(l2l, bdl + tr[2], 0); X3A_RDTR(l2h, bdl + tr[2], 2048); X3A_RDTR(l3l, bdl + tr[3], 0); X3A_RDTR(l3h, bdl + tr[3], 2048);
+          ATT_RDTR(h0l, bdh + tr[0], 0); ATT_RDTR(h0h, bdh + tr[0], 2048); ATT_RDTR(h1l, bdh + tr[1], 0); ATT_RDTR(h1h, bdh + tr[1], 2048);
+          ATT_RDTR(h2l, bdh + tr[2], 0); ATT_RDTR(h2h, bdh + tr[2], 2048); ATT_RDTR(h3l, bdh + tr[3], 0); ATT_RDTR(h3h, bdh + tr[3], 2048);
+          ATT_RDTR(l0l, bdl + tr[0], 0); ATT_RDTR(l0h, bdl + tr[0], 2048); ATT_RDTR(l1l, bdl + tr[1], 0); ATT_RDTR(l1h, bdl + tr[1], 2048);
+          ATT_RDTR(l2l, bdl + tr[2], 0); ATT_RDTR(l2h, bdl + tr[2], 2048); ATT_RDTR(l3l, bdl + tr[3], 0); ATT_RDTR(l3h, bdl + tr[3], 2048);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                        "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
-          dv[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), ph, pl, dv[j][0]);
-          dv[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), ph, pl, dv[j][1]);
-          dv[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), ph, pl, dv[j][2]);
-          dv[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), ph, pl, dv[j][3]);
+          dv[j][0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), ph, pl, dv[j][0]);
+          dv[j][1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), ph, pl, dv[j][1]);
+          dv[j][2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), ph, pl, dv[j][2]);
+          dv[j][3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), ph, pl, dv[j][3]);
         }
         {
           bf16x4 h0l, h0h, h1l, h1h, h2l, h2h, h3l, h3h, l0l, l0h, l1l, l1h, l2l, l2h, l3l, l3h;
-          X3A_RDTR(h0l, bqh + tr[0], 0); X3A_RDTR(h0h, bqh + tr[0], 2048); X3A_RDTR(h1l, bqh + tr[1], 0); X3A_RDTR(h1h, bqh + tr[1], 2048);
-          X3A_RDTR(h2l, bqh + tr[2], 0); X3A_RDTR(h2h, bqh + tr[2], 2048); X3A_RDTR(h3l, bqh + tr[3], 0); X3A_RDTR(h3h, bqh + tr[3], 2048);
-          X3A_RDTR(l0l, bql + tr[0], 0); X3A_RDTR(l0h, bql + tr[0], 2048); X3A_RDTR(l1l, bql + tr[1], 0); X3A_RDTR(l1h, bql + tr[1], 2048);
-          X3A_RDTR(l2l, bql + tr[2], 0); X3A_RDTR(l2h, bql + tr[2], 2048); X3A_RDTR(l3l, bql + tr[3], 0); X3A_RDTR(l3h, bql + tr[3], 2048);
+          ATT_RDTR(h0l, bqh + tr[0], 0); ATT_RDTR(h0h, bqh + tr[0], 2048); ATT_RDTR(h1l, bqh + tr[1], 0); ATT_RDTR(h1h, bqh + tr[1], 2048);
+          ATT_RDTR(h2l, bqh + tr[2], 0); ATT_RDTR(h2h, bqh + tr[2], 2048); ATT_RDTR(h3l, bqh + tr[3], 0); ATT_RDTR(h3h, bqh + tr[3], 2048);
+          ATT_RDTR(l0l, bql + tr[0], 0); ATT_RDTR(l0h, bql + tr[0], 2048); ATT_RDTR(l1l, bql + tr[1], 0); ATT_RDTR(l1h, bql + tr[1], 2048);
+          ATT_RDTR(l2l, bql + tr[2], 0); ATT_RDTR(l2h, bql + tr[2], 2048); ATT_RDTR(l3l, bql + tr[3], 0); ATT_RDTR(l3h, bql + tr[3], 2048);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0l), "+v"(h0h), "+v"(h1l), "+v"(h1h), "+v"(h2l), "+v"(h2h), "+v"(h3l), "+v"(h3h),
                        "+v"(l0l), "+v"(l0h), "+v"(l1l), "+v"(l1h), "+v"(l2l), "+v"(l2h), "+v"(l3l), "+v"(l3h)::"memory");
-          dk[j][0] = plane_mfma3<f16_t>(X3A_CAT(h0l, h0h), X3A_CAT(l0l, l0h), sh, sl, dk[j][0]);
-          dk[j][1] = plane_mfma3<f16_t>(X3A_CAT(h1l, h1h), X3A_CAT(l1l, l1h), sh, sl, dk[j][1]);
-          dk[j][2] = plane_mfma3<f16_t>(X3A_CAT(h2l, h2h), X3A_CAT(l2l, l2h), sh, sl, dk[j][2]);
-          dk[j][3] = plane_mfma3<f16_t>(X3A_CAT(h3l, h3h), X3A_CAT(l3l, l3h), sh, sl, dk[j][3]);
+          dk[j][0] = plane_mfma3<f16_t>(ATT_CAT(h0l, h0h), ATT_CAT(l0l, l0h), sh, sl, dk[j][0]);
+          dk[j][1] = plane_mfma3<f16_t>(ATT_CAT(h1l, h1h), ATT_CAT(l1l, l1h), sh, sl, dk[j][1]);
+          dk[j][2] = plane_mfma3<f16_t>(ATT_CAT(h2l, h2h), ATT_CAT(l2l, l2h), sh, sl, dk[j][2]);
+          dk[j][3] = plane_mfma3<f16_t>(ATT_CAT(h3l, h3h), ATT_CAT(l3l, l3h), sh, sl, dk[j][3]);
         }
       }
     }
@@ -1040,18 +1017,28 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkv_x3_long_kernel(const bf16_
 }
 
 // ------------------------------------------------------------------------------------------ host
-template <typename K>
-static int x3a_set_lds(K kernel, size_t bytes, const char* name) {
-  if (bytes > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    simx_set_error("%s: cannot raise dynamic LDS to %zu", name, bytes);
-    return SIMX_ERR_HIP;
-  }
-  return SIMX_OK;
-}
-
 extern "C" int simx_mha_x3_ok(int d, int max_len) {
   static const bool off = [] { const char* e = getenv("SIMX_MHA_X3"); return e && e[0] == '0'; }();     // SIMX_MHA_X3=0: the f32 MFMA kernels (A/B)
   return !off && d == 64 && max_len > 0 && max_len <= 4096 ? 1 : 0;
+}
+
+// what forward and backward require of the shape (the pointers and the strides of their own planes are checked by each)
+static int x3_check(int nseq, int heads, int d, int max_len, int T, bool ptrs_ok, bool strides_ok, const simx_dropout* dropd, const char* who,
+                    const char* needs) {
+  SIMX_REQUIRE(nseq > 0 && heads > 0 && T > 0 && ptrs_ok, SIMX_ERR_BAD_SHAPE, "%s: bad arguments", who);
+  SIMX_REQUIRE(simx_mha_x3_ok(d, max_len) && strides_ok, SIMX_ERR_UNSUPPORTED, "%s: needs head size 64, max_len <= 4096, %s", who, needs);
+  // (probabilities travel as 2^10 p / (1 - p_drop) in fp16 halves: finite only while 1 / (1 - p_drop) stays small)
+  SIMX_REQUIRE(!dropd || dropd->p <= 0.9f, SIMX_ERR_UNSUPPORTED, "mha_x3: attention dropout above 0.9 is not supported by the plane-pair kernels");
+  return SIMX_OK;
+}
+
+// max_len -> the resident kernels' key tiles (of 16 tokens), forward and backward: f(std::integral_constant<int, NKT>{}); 0: chunked
+template <typename Fn>
+static int x3_by_tiles(int max_len, Fn&& f) {
+  if (max_len <= 32) return f(std::integral_constant<int, 2>{});
+  if (max_len <= 128) return f(std::integral_constant<int, 8>{});
+  if (max_len <= 160) return f(std::integral_constant<int, 10>{});
+  return f(std::integral_constant<int, 0>{});
 }
 
 // q / k / v: fp16 plane pair [T, 3H] (lo at + qkv_plane_stride elements); ctx: fp16 plane pair [T, H]; lse: f32 [heads, T]
@@ -1059,104 +1046,74 @@ extern "C" int simx_mha_fwd_x3(simx_stream_t stream, int nseq, int heads, int d,
                                long qkv_plane_stride, void* ctx_planes, long ctx_plane_stride, float* lse, const simx_dropout* dropd) {
   hipStream_t s = (hipStream_t)stream;
   SIMX_PROF(SIMX_K_MHA_FWD, s, 4.0 * T * max_len * heads * d);
-  SIMX_REQUIRE(nseq > 0 && heads > 0 && T > 0 && qkv_planes && ctx_planes && lse && cu, SIMX_ERR_BAD_SHAPE, "mha_fwd_x3: bad arguments");
-  SIMX_REQUIRE(simx_mha_x3_ok(d, max_len) && qkv_plane_stride % 8 == 0 && ctx_plane_stride % 4 == 0, SIMX_ERR_UNSUPPORTED,
-               "mha_fwd_x3: needs head size 64, max_len <= 4096, plane strides %% 8 / %% 4 == 0");
-  // (probabilities travel as 2^10 p / (1 - p_drop) in fp16 halves: finite only while 1 / (1 - p_drop) stays small)
-  SIMX_REQUIRE(!dropd || dropd->p <= 0.9f, SIMX_ERR_UNSUPPORTED, "mha_x3: attention dropout above 0.9 is not supported by the plane-pair kernels");
+  int rc = x3_check(nseq, heads, d, max_len, T, qkv_planes && ctx_planes && lse && cu, qkv_plane_stride % 8 == 0 && ctx_plane_stride % 4 == 0, dropd,
+                    "mha_fwd_x3", "plane strides % 8 / % 4 == 0");
+  if (rc) return rc;
   const DropCtx drop = make_drop(dropd);
   const float scale = 1.0f / sqrtf((float)d);
-  int rc = SIMX_OK;
-#define LF(NKT)                                                                                                            \
-  do {                                                                                                                     \
-    const size_t lds = (size_t)4 * NKT * 16 * 128;                                                                         \
-    if (drop.thr) {                                                                                                        \
-      rc = x3a_set_lds(mha_fwd_x3_kernel<NKT, true>, lds, "mha_fwd_x3");                                                   \
-      if (rc) return rc;                                                                                                   \
-      hipLaunchKernelGGL((mha_fwd_x3_kernel<NKT, true>), dim3(nseq * heads), dim3(256), lds, s, (const bf16_t*)qkv_planes, qkv_plane_stride, \
-                         (bf16_t*)ctx_planes, ctx_plane_stride, lse, cu, heads, T, scale, drop);                           \
-    } else {                                                                                                               \
-      rc = x3a_set_lds(mha_fwd_x3_kernel<NKT, false>, lds, "mha_fwd_x3");                                                  \
-      if (rc) return rc;                                                                                                   \
-      hipLaunchKernelGGL((mha_fwd_x3_kernel<NKT, false>), dim3(nseq * heads), dim3(256), lds, s, (const bf16_t*)qkv_planes, qkv_plane_stride, \
-                         (bf16_t*)ctx_planes, ctx_plane_stride, lse, cu, heads, T, scale, drop);                           \
-    }                                                                                                                      \
-  } while (0)
-  if (max_len <= 32) LF(2);
-  else if (max_len <= 128) LF(8);
-  else if (max_len <= 160) LF(10);
-  else {                                               // chunked (161..256 tokens too: 2048 x 12 blocks of 256, 2.54 ms resident, 2.30 chunked): one workgroup per (sequence, head, 128-query chunk)
-    const int nchunk = (max_len + XL_CH - 1) / XL_CH;
-    const size_t lds = (size_t)4 * XL_TILE;
-    if (drop.thr)
-      hipLaunchKernelGGL((mha_fwd_x3_long_kernel<true>), dim3(nseq * heads * nchunk), dim3(256), lds, s, (const bf16_t*)qkv_planes, qkv_plane_stride,
-                         (bf16_t*)ctx_planes, ctx_plane_stride, lse, cu, heads, T, nchunk, scale, drop);
-    else
-      hipLaunchKernelGGL((mha_fwd_x3_long_kernel<false>), dim3(nseq * heads * nchunk), dim3(256), lds, s, (const bf16_t*)qkv_planes, qkv_plane_stride,
-                         (bf16_t*)ctx_planes, ctx_plane_stride, lse, cu, heads, T, nchunk, scale, drop);
-  }
-#undef LF
-  SIMX_CHECK_LAUNCH("mha_fwd_x3");
-  return SIMX_OK;
+  const bf16_t* qkv = (const bf16_t*)qkv_planes;
+  bf16_t* ctx = (bf16_t*)ctx_planes;
+  return x3_by_tiles(max_len, [&](auto nkt) {
+    return by_flag(drop.thr != 0, [&](auto dr) {
+      constexpr int NKT = decltype(nkt)::value;
+      constexpr bool DROP = decltype(dr)::value;
+      if constexpr (NKT > 0) {
+        return att_launch<mha_fwd_x3_kernel<NKT, DROP>, X3FwdLds<NKT>::BYTES>("mha_fwd_x3", s, dim3(nseq * heads), qkv, qkv_plane_stride, ctx,
+                                                                              ctx_plane_stride, lse, cu, heads, T, scale, drop);
+      } else {             // chunked (161..256 tokens too: 2048 x 12 blocks of 256, 2.54 ms resident, 2.30 chunked): one workgroup per (sequence, head, 128-query chunk)
+        const int nchunk = (max_len + XL_CH - 1) / XL_CH;
+        return att_launch<mha_fwd_x3_long_kernel<DROP>, X3FwdLds<XL_CH / 16>::BYTES>("mha_fwd_x3", s, dim3(nseq * heads * nchunk), qkv, qkv_plane_stride,
+                                                                                     ctx, ctx_plane_stride, lse, cu, heads, T, nchunk, scale, drop);
+      }
+    });
+  });
 }
 
 // dctx: f32 [T, H]; ctx: the forward's fp16 plane pair; dq / dk / dv leave as a bf16 plane pair [T, 3H]
-extern "C" int simx_mha_bwd_x3(simx_stream_t stream, int nseq, int heads, int d, const int32_t* cu, int max_len, int T, const void* qkv_planes,
-                               long qkv_plane_stride, const void* ctx_planes, long ctx_plane_stride, const float* lse, const float* dctx,
-                               void* dqkv_planes, long dqkv_plane_stride, const simx_dropout* dropd) {
-  return simx_mha_bwd_x3_bias(stream, nseq, heads, d, cu, max_len, T, qkv_planes, qkv_plane_stride, ctx_planes, ctx_plane_stride, lse, dctx,
-                              dqkv_planes, dqkv_plane_stride, dropd, nullptr);
-}
-// same; dbias [3H] (may be NULL) += column sums of dq | dk | dv over the T tokens (the QKV projection's bias gradient; atomics)
+// dbias [3H] (may be NULL) += column sums of dq | dk | dv over the T tokens (the QKV projection's bias gradient; atomics)
 extern "C" int simx_mha_bwd_x3_bias(simx_stream_t stream, int nseq, int heads, int d, const int32_t* cu, int max_len, int T, const void* qkv_planes,
                                     long qkv_plane_stride, const void* ctx_planes, long ctx_plane_stride, const float* lse, const float* dctx,
                                     void* dqkv_planes, long dqkv_plane_stride, const simx_dropout* dropd, float* dbias) {
   hipStream_t s = (hipStream_t)stream;
   SIMX_PROF(SIMX_K_MHA_BWD, s, 8.0 * T * max_len * heads * d);
-  SIMX_REQUIRE(nseq > 0 && heads > 0 && T > 0 && qkv_planes && ctx_planes && lse && dctx && dqkv_planes && cu, SIMX_ERR_BAD_SHAPE, "mha_bwd_x3: bad arguments");
-  SIMX_REQUIRE(simx_mha_x3_ok(d, max_len) && qkv_plane_stride % 8 == 0 && ctx_plane_stride % 8 == 0 && dqkv_plane_stride % 4 == 0 &&
-                   (heads * 64) % 8 == 0 && simx_al16(dctx), SIMX_ERR_UNSUPPORTED,
-               "mha_bwd_x3: needs head size 64, max_len <= 4096, aligned plane strides");
-  // (probabilities travel as 2^10 p / (1 - p_drop) in fp16 halves: finite only while 1 / (1 - p_drop) stays small)
-  SIMX_REQUIRE(!dropd || dropd->p <= 0.9f, SIMX_ERR_UNSUPPORTED, "mha_x3: attention dropout above 0.9 is not supported by the plane-pair kernels");
+  int rc = x3_check(nseq, heads, d, max_len, T, qkv_planes && ctx_planes && lse && dctx && dqkv_planes && cu,
+                    qkv_plane_stride % 8 == 0 && ctx_plane_stride % 8 == 0 && dqkv_plane_stride % 4 == 0 && (heads * 64) % 8 == 0 && simx_al16(dctx), dropd,
+                    "mha_bwd_x3", "aligned plane strides");
+  if (rc) return rc;
   const DropCtx drop = make_drop(dropd);
   const float scale = 1.0f / sqrtf((float)d);
-  int rc = SIMX_OK;
-#define LBD(NKT, DROP)                                                                                                     \
-  do {                                                                                                                     \
-    const size_t lds1 = (size_t)4 * NKT * 16 * 128 + 64;                                                                   \
-    const size_t lds2 = (size_t)4 * NKT * 16 * 128 + 2 * NKT * 16 * 4 + 64 + ((DROP) ? (size_t)NKT * 16 * NKT * 2 : 0);    \
-    rc = x3a_set_lds(mha_bwd_dq_x3_kernel<NKT, DROP>, lds1, "mha_bwd_x3");                                                 \
-    if (rc) return rc;                                                                                                     \
-    rc = x3a_set_lds(mha_bwd_dkv_x3_kernel<NKT, DROP>, lds2, "mha_bwd_x3");                                                \
-    if (rc) return rc;                                                                                                     \
-    hipLaunchKernelGGL((mha_bwd_dq_x3_kernel<NKT, DROP>), dim3(nseq * heads), dim3(256), lds1, s, (const bf16_t*)qkv_planes, qkv_plane_stride, \
-                       (const bf16_t*)ctx_planes, ctx_plane_stride, lse, dctx, (bf16_t*)dqkv_planes, dqkv_plane_stride, cu, heads, T, scale, drop, dbias); \
-    hipLaunchKernelGGL((mha_bwd_dkv_x3_kernel<NKT, DROP>), dim3(nseq * heads), dim3(256), lds2, s, (const bf16_t*)qkv_planes, qkv_plane_stride, \
-                       (const bf16_t*)ctx_planes, ctx_plane_stride, lse, dctx, (bf16_t*)dqkv_planes, dqkv_plane_stride, cu, heads, T, scale, drop, dbias); \
-  } while (0)
-#define LB(NKT) do { if (drop.thr) LBD(NKT, true); else LBD(NKT, false); } while (0)
-#define LBL(DROP)                                                                                                          \
-  do {                                                                                                                     \
-    const int nchunk = (max_len + XL_CH - 1) / XL_CH;                                                                      \
-    const size_t lds1 = (size_t)4 * XL_TILE + 64, lds2 = (size_t)4 * XL_TILE + 2 * XL_CH * 4 + 64 + ((DROP) ? (size_t)8 * XL_CH * 2 : 0); \
-    rc = x3a_set_lds(mha_bwd_dq_x3_long_kernel<DROP>, lds1, "mha_bwd_x3");                                                 \
-    if (rc) return rc;                                                                                                     \
-    rc = x3a_set_lds(mha_bwd_dkv_x3_long_kernel<DROP>, lds2, "mha_bwd_x3");                                                \
-    if (rc) return rc;                                                                                                     \
-    hipLaunchKernelGGL((mha_bwd_dq_x3_long_kernel<DROP>), dim3(nseq * heads * nchunk), dim3(256), lds1, s, (const bf16_t*)qkv_planes, qkv_plane_stride, \
-                       (const bf16_t*)ctx_planes, ctx_plane_stride, lse, dctx, (bf16_t*)dqkv_planes, dqkv_plane_stride, cu, heads, T, nchunk, scale, drop, dbias); \
-    hipLaunchKernelGGL((mha_bwd_dkv_x3_long_kernel<DROP>), dim3(nseq * heads * nchunk), dim3(256), lds2, s, (const bf16_t*)qkv_planes, qkv_plane_stride, \
-                       (const bf16_t*)ctx_planes, ctx_plane_stride, lse, dctx, (bf16_t*)dqkv_planes, dqkv_plane_stride, cu, heads, T, nchunk, scale, drop, dbias); \
-  } while (0)
-  if (max_len <= 32) LB(2);
-  else if (max_len <= 128) LB(8);
-  else if (max_len <= 160) LB(10);
-  else if (drop.thr) LBL(true);          // (161..256 tokens too: 2048 x 12 blocks of 256, 9.58 ms resident -- one workgroup per CU -- 8.57 chunked)
-  else LBL(false);
-#undef LBL
-#undef LB
-#undef LBD
-  SIMX_CHECK_LAUNCH("mha_bwd_x3");
-  return SIMX_OK;
+  const bf16_t* qkv = (const bf16_t*)qkv_planes;
+  const bf16_t* ctx = (const bf16_t*)ctx_planes;
+  bf16_t* dqkv = (bf16_t*)dqkv_planes;
+  return x3_by_tiles(max_len, [&](auto nkt) {
+    return by_flag(drop.thr != 0, [&](auto dr) {
+      constexpr int NKT = decltype(nkt)::value;
+      constexpr bool DROP = decltype(dr)::value;
+      if constexpr (NKT > 0) {
+        rc = att_launch<mha_bwd_dq_x3_kernel<NKT, DROP>, X3DqLds<NKT>::BYTES>("mha_bwd_x3", s, dim3(nseq * heads), qkv, qkv_plane_stride, ctx,
+                                                                              ctx_plane_stride, lse, dctx, dqkv, dqkv_plane_stride, cu, heads, T,
+                                                                              scale, drop, dbias);
+        if (rc) return rc;
+        return att_launch<mha_bwd_dkv_x3_kernel<NKT, DROP>, X3DkvLds<NKT, DROP>::BYTES>("mha_bwd_x3", s, dim3(nseq * heads), qkv, qkv_plane_stride, ctx,
+                                                                                        ctx_plane_stride, lse, dctx, dqkv, dqkv_plane_stride, cu,
+                                                                                        heads, T, scale, drop, dbias);
+      } else {             // (161..256 tokens too: 2048 x 12 blocks of 256, 9.58 ms resident -- one workgroup per CU -- 8.57 chunked)
+        constexpr int CT = XL_CH / 16;
+        const int nchunk = (max_len + XL_CH - 1) / XL_CH;
+        rc = att_launch<mha_bwd_dq_x3_long_kernel<DROP>, X3DqLds<CT>::BYTES>("mha_bwd_x3", s, dim3(nseq * heads * nchunk), qkv, qkv_plane_stride, ctx,
+                                                                             ctx_plane_stride, lse, dctx, dqkv, dqkv_plane_stride, cu, heads, T,
+                                                                             nchunk, scale, drop, dbias);
+        if (rc) return rc;
+        return att_launch<mha_bwd_dkv_x3_long_kernel<DROP>, X3DkvLds<CT, DROP>::BYTES>("mha_bwd_x3", s, dim3(nseq * heads * nchunk), qkv,
+                                                                                       qkv_plane_stride, ctx, ctx_plane_stride, lse, dctx, dqkv,
+                                                                                       dqkv_plane_stride, cu, heads, T, nchunk, scale, drop, dbias);
+      }
+    });
+  });
+}
+extern "C" int simx_mha_bwd_x3(simx_stream_t stream, int nseq, int heads, int d, const int32_t* cu, int max_len, int T, const void* qkv_planes,
+                               long qkv_plane_stride, const void* ctx_planes, long ctx_plane_stride, const float* lse, const float* dctx,
+                               void* dqkv_planes, long dqkv_plane_stride, const simx_dropout* dropd) {
+  return simx_mha_bwd_x3_bias(stream, nseq, heads, d, cu, max_len, T, qkv_planes, qkv_plane_stride, ctx_planes, ctx_plane_stride, lse, dctx,
+                              dqkv_planes, dqkv_plane_stride, dropd, nullptr);
 }

@@ -198,3 +198,43 @@ def test_mha_x3_long_dropout_and_speed(dev, S, nseq):
     assert np.abs(a - b).max() <= 4e-5 * np.abs(b).max(), (np.abs(a - b).max(), np.abs(b).max())
     print("mha S=%d x %d seqs x 16 heads: forward x3 %.3f ms, f32 MFMA %.3f ms; backward x3 %.3f ms, f32 MFMA %.3f ms"
           % (S, nseq, _ms(lambda: f3(None)), _ms(lambda: f32(None)), _ms(lambda: b3(None)), _ms(lambda: b32(None))))
+
+
+# one list per resident rung (2 / 8 / 10 tiles), one for the 161..256-token band and one chunked case with a ragged chunk and a
+# sequence shorter than a chunk
+DROP_LENS = [[31, 9], [128, 17], [160, 129], [250, 200], [300, 33]]
+
+
+@pytest.mark.parametrize("lens", DROP_LENS)
+def test_mha_x3_dropout_rungs(dev, lens):
+    """Dropout away from 128 tokens (the DROP = true kernels of every rung, whose LDS image differs from the DROP = false one) against
+    the planes form of the f32 unit: same stateless mask, the bounds of test_mha_fwd_x3_dropout_and_speed /
+    test_mha_bwd_x3_dropout_and_speed."""
+    import ctypes as C
+    lib = L()
+    heads, d, nseq, S = 2, 64, len(lens), max(lens)
+    T, H = sum(lens), heads * 64
+    qkv = torch.from_numpy(rnd((T, 3 * H), 3, 1.0)).to(dev)
+    dctx = torch.from_numpy(rnd((T, H), 4, 1e-3)).to(dev)
+    qp = planes_of(qkv, F16, dev)
+    cu = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)).to(dev)
+    drop = lib.Dropout(0.1, 99, 11)
+    ctxp, ctxq = torch.zeros(2, T, H, device=dev, dtype=torch.int16), torch.zeros(2, T, H, device=dev, dtype=torch.int16)
+    lse, lse2 = torch.zeros(heads, T, device=dev), torch.zeros(heads, T, device=dev)
+    lib.call("simx_mha_fwd_x3", lib.stream_ptr(), nseq, heads, d, lib.ptr(cu), S, T, lib.ptr(qp), T * 3 * H, lib.ptr(ctxp), T * H,
+             lib.ptr(lse), C.byref(drop))
+    lib.call("simx_mha_fwd_planes", lib.stream_ptr(), nseq, heads, d, lib.ptr(cu), S, T, lib.ptr(qkv), lib.ptr(ctxq), T * H,
+             lib.ptr(lse2), C.byref(drop))
+    torch.cuda.synchronize()
+    a, b = planes_value(ctxp, F16), planes_value(ctxq, F16)
+    assert np.abs(a - b).max() <= 5e-6 * max(1.0, np.abs(b).max()), np.abs(a - b).max()
+    assert np.abs(lse.cpu().numpy() - lse2.cpu().numpy()).max() <= 2e-5 * 20
+    g3, g32 = torch.zeros(2, T, 3 * H, device=dev, dtype=torch.int16), torch.zeros(2, T, 3 * H, device=dev, dtype=torch.int16)
+    lib.call("simx_mha_bwd_x3", lib.stream_ptr(), nseq, heads, d, lib.ptr(cu), S, T, lib.ptr(qp), T * 3 * H, lib.ptr(ctxp), T * H,
+             lib.ptr(lse), lib.ptr(dctx), lib.ptr(g3), T * 3 * H, C.byref(drop))
+    lib.call("simx_mha_bwd_planes", lib.stream_ptr(), nseq, heads, d, lib.ptr(cu), S, T, lib.ptr(qkv), lib.ptr(ctxp), T * H,
+             lib.ptr(lse), lib.ptr(dctx), lib.ptr(g32), T * 3 * H, C.byref(drop))
+    torch.cuda.synchronize()
+    a, b = planes_value(g3, BF16), planes_value(g32, BF16)
+    assert np.isfinite(a).all()
+    assert np.abs(a - b).max() <= 4e-5 * np.abs(b).max(), (np.abs(a - b).max(), np.abs(b).max())

@@ -449,8 +449,8 @@ def _mha_ref(qkv, lens, heads, d, dctx=None):
     (True, 3, 64, [9, 32, 4, 31]),              # NKT=2
     (True, 2, 64, [160, 129, 45]),              # NKT=10
     (True, 1, 64, [250, 200]),                  # NKT=16
-    (True, 1, 64, [300, 512, 33]),              # fwd NKT=32, bwd chunked (2 chunks of 256)
-    (True, 2, 64, [700, 257, 1024, 40, 256]),   # fwd generic, bwd chunked (up to 4 chunks, ragged tails, exact multiples)
+    (True, 1, 64, [300, 512, 33]),              # > 256: fwd and bwd chunked (128-token chunks, up to 4)
+    (True, 2, 64, [700, 257, 1024, 40, 256]),   # chunked (up to 8 chunks, ragged tails, exact multiples)
     ("f16", 4, 16, [5, 32, 17]),                # the same kernels on IEEE half
     ("f16", 2, 64, [128, 1, 17, 33, 16, 100]),
     ("f16", 3, 64, [9, 32, 4, 31]),
@@ -458,8 +458,8 @@ def _mha_ref(qkv, lens, heads, d, dctx=None):
     ("f16", 1, 64, [250, 200]),
     ("f16", 1, 64, [300, 512, 33]),
     ("f16", 2, 64, [700, 257, 1024, 40, 256]),
-    # >= 1024 (sequence, head) items of <= 128 tokens: the persistent double-buffered backward (mha_bwd3), ragged lengths,
-    # more items than workgroups so that every workgroup walks several
+    # >= 1024 (sequence, head) workgroups of <= 128 tokens on the resident 8-tile kernels (mha_fwd_h16 / mha_bwd2_h16): ragged
+    # lengths, complete and partial last tiles, more workgroups than the chip runs at once
     (True, 12, 64, [1 + (37 * i) % 128 for i in range(90)] + [128, 127, 113]),
     ("f16", 12, 64, [128] * 30 + [1 + (53 * i) % 128 for i in range(70)]),
 ])
@@ -482,6 +482,39 @@ def test_mha_fwd_bwd(dev, bf16, heads, d, lens):
              lib.ptr(lse), lib.ptr(dd_), lib.ptr(dqkv))
     tolb = pick(bf16, dict(rtol=1e-4, atol=1e-4), dict(rtol=3e-2, atol=6e-2), dict(rtol=4e-3, atol=8e-3))
     assert_close(back(dqkv), rdq, what="mha dqkv", **tolb)
+
+
+@pytest.mark.parametrize("bf16", H16)
+@pytest.mark.parametrize("lens", [[31, 9], [128, 17], [160, 129], [250, 200], [300, 33]])   # one per rung (2 / 8 / 10 / 16 tiles) + chunked
+def test_mha_h16_dropout_rungs(dev, bf16, lens):
+    """The DROP = true kernels of every rung of the 16-bit unit against the f32 unit on the same rounded inputs and the same
+    dropout (one stateless mask for both).  Tolerances: the 16-bit ones of test_mha_fwd_bwd x 1 / (1 - 0.1016) -- dropout scales
+    every kept probability by exactly that (p = 0.1 runs in steps of 1 / 256: 26 / 256)."""
+    lib = L()
+    heads, d = 2, 64
+    T, H = sum(lens), heads * d
+    qkv, dctx = rnd((T, 3 * H), 1, 1.0), rnd((T, H), 2)
+    dcu = to_dev(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), dev)
+    drop = lib.Dropout(0.1, 99, 11)
+
+    def run(fmt, q, g):
+        dq_, dd_ = to_dev(q, dev, fmt), to_dev(g, dev, fmt)
+        ctx, lse = torch.zeros(T, H, device=dev, dtype=tdt(fmt)), torch.zeros(heads, T, device=dev)
+        dqkv = torch.zeros(T, 3 * H, device=dev, dtype=tdt(fmt))
+        lib.call("simx_mha_fwd_ex", lib.stream_ptr(), code(fmt), len(lens), heads, d, lib.ptr(dcu), max(lens), T, lib.ptr(dq_), lib.ptr(ctx),
+                 lib.ptr(lse), C.byref(drop))
+        lib.call("simx_mha_bwd_ex", lib.stream_ptr(), code(fmt), len(lens), heads, d, lib.ptr(dcu), max(lens), T, lib.ptr(dq_), lib.ptr(ctx),
+                 lib.ptr(lse), lib.ptr(dd_), lib.ptr(dqkv), C.byref(drop))
+        return back(ctx), back(lse), back(dqkv)
+
+    gc, gl, gq = run(bf16, qkv, dctx)
+    rc, rl, rq = run(False, rounded(qkv, bf16).astype(np.float32), rounded(dctx, bf16).astype(np.float32))
+    k = 1.0 / (1.0 - 0.1016)
+    tol = pick(bf16, None, dict(rtol=2e-2 * k, atol=2e-2 * k), dict(rtol=2.5e-3 * k, atol=2.5e-3 * k))
+    assert_close(gc, rc, what="mha ctx", **tol)
+    assert_close(gl, rl, rtol=1e-5 * k, atol=pick(bf16, None, 5e-3, 1e-3) * k, what="mha lse")
+    tolb = pick(bf16, None, dict(rtol=3e-2 * k, atol=6e-2 * k), dict(rtol=4e-3 * k, atol=8e-3 * k))
+    assert_close(gq, rq, what="mha dqkv", **tolb)
 
 
 @pytest.mark.parametrize("bf16,heads,d,lens", [
